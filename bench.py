@@ -14,7 +14,8 @@ data-path collective -- SURVEY.md section 8e); value = all ranks' images / max-o
 
 Rank 0 prints ONE JSON line with `roofline` (dominant kernel: hipEvent time measured inside the
 timed steps on the launch stream, algorithmic FLOPs per launch) and `cpu_baseline` (the oracle,
-a CPU port of the reference path, on a bounded sample on this box's host cores).
+a CPU port of the reference path, on a bounded sample on this box's host cores).  `--dump-outputs DIR` also writes
+what the last timed step returned (logits, mask) as .npy files, for comparing two builds on the same inputs.
 """
 from __future__ import annotations
 
@@ -152,6 +153,28 @@ def parity_vs(gpu_logits, gpu_mask, logits, mask):
     return {"logits_max_abs_err": err, "mask_match": float((~differ).float().mean()),
             "mask_mismatch_at_stable_pixels": int((differ & stable).sum()),
             "unstable_pixels": float((~stable).float().mean()), "images_checked": n}
+
+
+DUMP_BYTES = 60 * 10**6   # float32 payload of one --dump-outputs directory, all files together (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, outputs, seed=0):
+    """--dump-outputs: each output of the timed path's last step as out_dir/<name>.npy in float32 (exact for the uint8
+    mask).  An output larger than its share of DUMP_BYTES is written as a fixed sample: its flat elements at ascending
+    positions drawn without replacement by numpy's default_rng(seed), the same positions in every run with the same
+    arguments, so that two builds compare element for element.  Returns what was written, for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // 4 // len(outputs)
+    written = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        shape, sampled = list(a.shape), a.size > share
+        if sampled:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"shape": shape, "dtype": str(t.dtype).replace("torch.", ""), "elements_written": int(a.size),
+                         "sample": f"default_rng({seed}) positions of the flat array" if sampled else None}
+    return written
 
 
 def run_tiled(precision, native, B, rank, dev, steps, warmup, barrier, procedural_weights=True):
@@ -822,7 +845,14 @@ def main():
                     help="N > 1: images per rank of the data-parallel training step appended to the line (train_bf16_path)")
     ap.add_argument("--mode", default="infer", choices=["infer", "train", "prep", "eval"],
                     help="train: one step = forward + CE + backward + gradient all-reduce + Adam (fp32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's logits and mask (rank 0) as DIR/<name>.npy in float32, "
+                         "a fixed seeded sample where the whole would exceed 64 MB (b16_512 inference only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload != "b16_512" or args.mode != "infer"):
+        ap.error("--dump-outputs covers the b16_512 inference step only")
     tiled = args.workload in ("l16_1024_tiled", "l16_1024_native")
     if args.precision is None:
         args.precision = "f16" if tiled else "f32"
@@ -893,6 +923,7 @@ def main():
         elapsed = time.perf_counter() - t0
     prof = _lib.profile_collect()
     _lib.profile_enable(False)
+    dumped = dump_outputs(args.dump_outputs, {"logits": logits, "mask": mask}) if args.dump_outputs and rank == 0 else None
 
     split_check = dist_train = None
     if world > 1:
@@ -948,6 +979,8 @@ def main():
             # the HBM-bound pieces against the 8 TB/s roof (algorithmic bytes / hipEvent time, same timed region)
             "roofline_hbm": hbm_rooflines(prof, ("layernorm", "upsample")),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if split_check is not None:
             out["inference_split"] = split_check
         if dist_train is not None:
