@@ -248,7 +248,9 @@ int vitseg_op_upsample_bwd(const float* grad_logits, float* grad_lowres, int bat
  * lowres: fp32 [B, C, g, g] low-resolution logits (VITSEG_BUF_LOWRES after vitseg_forward); target: class
  * indices [B, S, S], int64 (torch.long, as the reference passes them) or uint8.  Writes the mean loss to
  * *loss (device fp32).  scratch: >= vitseg_ce_scratch_bytes() device bytes.  grad_logits (optional, fp32
- * [B, C, S, S]) receives d loss / d logits. */
+ * [B, C, S, S]) receives d loss / d logits.  Labels must lie in [0, C); ignore_index is not supported: a pixel
+ * with any other label (uint8 255, int64 -100 or C) makes the loss NaN and gets a NaN gradient (also in
+ * vitseg_backward's fused loss). */
 size_t vitseg_ce_scratch_bytes(int batch, int S);
 int vitseg_ce_loss(const float* lowres, const void* target, int target_is_u8, float* grad_logits, void* scratch,
                    float* loss, int batch, int C, int g, int S, void* stream);

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from guard import check, guarded, snapshot, unchanged
 from oracle import bf16_model as BM
 from oracle import vitseg_oracle as O
 from util import CASES, Golden
@@ -33,9 +34,27 @@ def _rand(*shape, seed=0, scale=1.0):
     return (torch.randn(*shape, generator=g) * scale).float()
 
 
+def _dev(t, dtype=None, name=None):
+    """guard-banded device copy of a CPU tensor (tests/guard.py)"""
+    return guarded(tuple(t.shape), dtype or t.dtype, t, device=DEV, name=name)
+
+
+def _out(shape, dtype=torch.float32, fill="nan", name=None):
+    return guarded(shape, dtype, fill, device=DEV, name=name)
+
+
+def _after(snap, *outs):
+    """after a call: every guard (inputs and outputs) intact, every input bitwise unchanged"""
+    torch.cuda.synchronize()
+    check(*[t for t, _ in snap], *outs)
+    unchanged(snap)
+
+
 @pytest.mark.parametrize("M,N,K,ta,tb,epi", [
     (257, 192, 96, 0, 1, 0), (1025, 768, 2304, 0, 1, 0), (300, 3072, 768, 0, 1, 5),
-    (192, 576, 1025, 1, 1, 0), (768, 3072, 2050, 1, 1, 0), (256, 6912, 300, 1, 1, 0), (64, 100, 37, 1, 1, 0)])
+    (192, 576, 1025, 1, 1, 0), (768, 3072, 2050, 1, 1, 0), (256, 6912, 300, 1, 1, 0), (64, 100, 37, 1, 1, 0),
+    (1, 132, 36, 0, 1, 0), (132, 4, 100, 1, 1, 0), (124, 252, 1, 1, 1, 0)])   # M = 1, N = 4, K = 1 against 128-wide tiles
+    # (leading dimensions are multiples of 4)
 def test_gemm_operand_forms(M, N, K, ta, tb, epi):
     A = _rand(K, M, seed=1) if ta else _rand(M, K, seed=1)
     W = _rand(K, N, seed=2, scale=0.05) if tb else _rand(N, K, seed=2, scale=0.05)
@@ -46,15 +65,19 @@ def test_gemm_operand_forms(M, N, K, ta, tb, epi):
     if epi == 5:
         u = R.double()
         ref = ref * (0.5 * (1 + torch.erf(u / 2 ** 0.5)) + u * torch.exp(-0.5 * u * u) / (2 * np.pi) ** 0.5)
-    Ad, Wd, Rd = A.to(DEV), W.to(DEV), R.to(DEV)
-    C = torch.full((M, N), float("nan"), device=DEV)
+    Ad, Wd, Rd = _dev(A, name="A"), _dev(W, name="W"), _dev(R, name="R")
+    C = _out((M, N), name="C")
+    snap = snapshot(Ad, Wd, Rd)
     _lib.check(_lib.lib().vitseg_op_gemm_f32(Ad.data_ptr(), Wd.data_ptr(), Rd.data_ptr(), C.data_ptr(), M, N, K, ta, tb,
                                              epi, _stream()))
+    _after(snap, C)
     bound = 4e-7 * (a64.abs() @ w64.abs()).max().item() + 1e-6
     assert (C.cpu().double() - ref).abs().max().item() < bound
 
 
-@pytest.mark.parametrize("rows,D", [(7, 192), (1025, 768), (130, 1024), (64, 512), (788, 768), (20000, 192)])
+@pytest.mark.parametrize("rows,D", [(7, 192), (1025, 768), (130, 1024), (64, 512), (788, 768), (20000, 192),
+                                    (1, 192),   # one row
+                                    (16383, 192), (16385, 192)])   # either side of 64 x CUs rows (lnb_blocks: 8 / 64 rows per block)
 def test_layernorm_backward(rows, D):
     x = (_rand(rows, D, seed=1, scale=2.0) + 0.3).double().requires_grad_(True)
     w = (_rand(D, seed=2) + 1.0).double().requires_grad_(True)
@@ -62,18 +85,23 @@ def test_layernorm_backward(rows, D):
     g, dres = _rand(rows, D, seed=4), _rand(rows, D, seed=5)
     y = O.layer_norm(x, w, b, 1e-12)
     y.backward(g.double())
-    xd, wd, gd, rd = x.detach().float().to(DEV), w.detach().float().to(DEV), g.to(DEV), dres.to(DEV)
-    out, dw, db = torch.empty(rows, D, device=DEV), torch.empty(D, device=DEV), torch.empty(D, device=DEV)
-    scratch = torch.empty(_lib.lib().vitseg_op_layernorm_bwd_scratch_floats(rows, D), device=DEV)
+    xd, wd, gd, rd = _dev(x.detach().float(), name="x"), _dev(w.detach().float(), name="w"), _dev(g, name="g"), \
+        _dev(dres, name="dres")
+    out, dw, db = _out((rows, D), name="dx"), _out((D,), name="dw"), _out((D,), name="db")
+    scratch = _out((_lib.lib().vitseg_op_layernorm_bwd_scratch_floats(rows, D),), name="layernorm_bwd scratch")
+    snap = snapshot(xd, wd, gd, rd)
     _lib.check(_lib.lib().vitseg_op_layernorm_bwd_f32(xd.data_ptr(), wd.data_ptr(), gd.data_ptr(), rd.data_ptr(),
                                                       out.data_ptr(), dw.data_ptr(), db.data_ptr(), scratch.data_ptr(),
                                                       rows, D, 1e-12, _stream()))
+    _after(snap, out, dw, db, scratch)
     assert (out.cpu().double() - (dres.double() + x.grad)).abs().max().item() < 2e-5
     assert (dw.cpu().double() - w.grad).abs().max().item() < 1e-5 * max(1.0, w.grad.abs().max().item())
     assert (db.cpu().double() - b.grad).abs().max().item() < 1e-5 * max(1.0, b.grad.abs().max().item())
 
 
-@pytest.mark.parametrize("B,Np,A", [(2, 196, 3), (1, 1024, 2), (1, 64, 1), (2, 100, 2)])
+@pytest.mark.parametrize("B,Np,A", [(2, 196, 3), (1, 1024, 2), (1, 64, 1), (2, 100, 2),
+                                    # ragged against the query / key blocks: below one block, one either side of 128
+                                    (1, 4, 1), (2, 31, 2), (3, 127, 1), (1, 129, 3), (2, 200, 2)])
 def test_attention_backward(B, Np, A):
     D, Mt = 64 * A, B * Np + B
     qkv = _rand(Mt, 3 * D, seed=Np + A, scale=1.2)
@@ -86,13 +114,15 @@ def test_attention_backward(B, Np, A):
         s = torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1)
         outs.append(((s @ v).transpose(0, 1).reshape(Np + 1, D) * dctx.double()[r]).sum())
     torch.stack(outs).sum().backward()
-    qd, dd = qkv.to(DEV), dctx.to(DEV)
-    ctx = torch.empty(Mt, D, device=DEV)
-    lse = torch.empty(B * A * (Np + 1), device=DEV)
-    scr = torch.empty(B * A * (Np + 1), device=DEV)
-    dqkv = torch.full((Mt, 3 * D), float("nan"), device=DEV)
+    qd, dd = _dev(qkv, name="qkv"), _dev(dctx, name="dctx")
+    ctx = _out((Mt, D), name="ctx")
+    lse = _out((B * A * (Np + 1),), name="lse")
+    scr = _out((B * A * (Np + 1),), name="attention_bwd scratch")   # delta [B, A, Np + 1]: what the fp32 kernels use
+    dqkv = _out((Mt, 3 * D), name="dqkv")
+    snap = snapshot(qd, dd)
     _lib.check(_lib.lib().vitseg_op_attention_bwd_f32(qd.data_ptr(), dd.data_ptr(), ctx.data_ptr(), lse.data_ptr(),
                                                       scr.data_ptr(), dqkv.data_ptr(), B, Np, A, _stream()))
+    _after(snap, ctx, lse, scr, dqkv)
     err = (dqkv.cpu().double() - x.grad).abs().max().item()
     assert err < 5e-5 * max(1.0, x.grad.abs().max().item()), err
 
@@ -693,7 +723,10 @@ def test_training_step_reproducible_at_the_training_size():
 
 @pytest.mark.parametrize("B,Np,A,p", [(2, 256, 2, 0.0), (1, 1024, 2, 0.0), (2, 196, 3, 0.0), (1, 64, 1, 0.0), (2, 100, 2, 0.0),
                                       (1, 1024, 1, 0.1), (2, 196, 2, 0.1), (2, 256, 3, 0.1),
-                                      (1, 1024, 1, -0.1), (2, 256, 3, -0.1)])
+                                      (1, 1024, 1, -0.1), (2, 256, 3, -0.1),
+                                      # ragged against the query / key blocks: below one block, one either side of 128 and 256
+                                      (1, 4, 1, 0.0), (2, 31, 2, 0.0), (3, 127, 1, 0.0), (1, 129, 3, 0.0), (2, 255, 2, 0.1),
+                                      (1, 257, 1, 0.0), (1, 128, 2, -0.1)])
 def test_attention_backward_bf16(B, Np, A, p):
     """bf16 attention core, forward (ctx, log-sum-exp) + backward (dq | dk | dv), with and without the attention-probability
     dropout (the kernels' counter-based mask regenerated in numpy and injected into the reference), against fp64 autograd
@@ -724,16 +757,18 @@ def test_attention_backward_bf16(B, Np, A, p):
         ctx_ref[r] = o.detach()
         outs.append((o * dctx.double()[r]).sum())
     torch.stack(outs).sum().backward()
-    qd, dd = qkv.to(DEV), dctx.to(DEV)
-    ctx = torch.zeros(Mt, D, device=DEV, dtype=torch.bfloat16)
-    lse = torch.empty(B * A * N, device=DEV)
-    scr = torch.empty(_lib.lib().vitseg_attention_bwd_scratch_floats(B, Np, A), device=DEV)
-    dqkv = torch.full((Mt, 3 * D), float("nan"), device=DEV, dtype=torch.bfloat16)
-    mw = torch.empty(_lib.lib().vitseg_attention_dropmask_bytes(B, Np, A), dtype=torch.uint8, device=DEV) if words else None
-    dbias = torch.full((3 * D,), float("nan"), device=DEV)
+    qd, dd = _dev(qkv, name="qkv"), _dev(dctx, name="dctx")
+    ctx = _out((Mt, D), torch.bfloat16, name="ctx")
+    lse = _out((B * A * N,), name="lse")
+    scr = _out((_lib.lib().vitseg_attention_bwd_scratch_floats(B, Np, A),), name="attention_bwd scratch")
+    dqkv = _out((Mt, 3 * D), torch.bfloat16, name="dqkv")
+    mw = _out((_lib.lib().vitseg_attention_dropmask_bytes(B, Np, A),), torch.uint8, name="dropmask words") if words else None
+    dbias = _out((3 * D,), name="dbias_qkv")
+    snap = snapshot(qd, dd)
     _lib.check(_lib.lib().vitseg_op_attention_bwd_bf16(qd.data_ptr(), dd.data_ptr(), ctx.data_ptr(), lse.data_ptr(),
                                                        scr.data_ptr(), dqkv.data_ptr(), B, Np, A, p, seed, stream_id,
                                                        mw.data_ptr() if words else None, dbias.data_ptr(), _stream()))
+    _after(snap, ctx, lse, scr, dqkv, mw, dbias)
     got, ref = dqkv.float().cpu().double(), x.grad
     assert torch.isfinite(got).all()
     # the fused QKV bias gradient = the column sums of dqkv (the kernels sum their fp32 accumulators, the stored values are
@@ -743,10 +778,11 @@ def test_attention_backward_bf16(B, Np, A, p):
     assert torch.isfinite(db).all()
     assert float((db - csum).norm() / got.abs().sum(dim=0).norm()) < 1e-3, float((db - csum).norm() / got.abs().sum(dim=0).norm())
     assert float((db - ref.sum(dim=0)).norm() / ref.abs().sum(dim=0).norm()) < 5e-3
-    dqkv2 = torch.full((Mt, 3 * D), float("nan"), device=DEV, dtype=torch.bfloat16)
+    dqkv2 = _out((Mt, 3 * D), torch.bfloat16, name="dqkv (second call)")
     _lib.check(_lib.lib().vitseg_op_attention_bwd_bf16(qd.data_ptr(), dd.data_ptr(), ctx.data_ptr(), lse.data_ptr(),
                                                        scr.data_ptr(), dqkv2.data_ptr(), B, Np, A, p, seed, stream_id,
                                                        mw.data_ptr() if words else None, None, _stream()))
+    _after(snap, ctx, lse, scr, dqkv2, mw)
     assert torch.equal(dqkv.view(torch.int16), dqkv2.view(torch.int16))
     assert (ctx.float().cpu().double() - ctx_ref).abs().max().item() < 4e-2
     # P, dS and the outputs are rounded to bf16 (2^-9): a few 1e-3 relative to the gradient scale, per slot
@@ -780,15 +816,17 @@ def test_attention_backward_bf16_is_its_rounding_model(Np, A, spread, p):
     qkv = (base + spread * 0.55 * torch.randn(Mt, 3 * D, generator=gen)).to(torch.bfloat16)
     dctx = (torch.randn(1, D, generator=gen) + torch.randn(Mt, D, generator=gen)).to(torch.bfloat16)
     seed, stream_id = 0xBEEF1234, 3 * 8 + 1
-    qd, dd = qkv.to(DEV), dctx.to(DEV)
-    ctx = torch.zeros(Mt, D, device=DEV, dtype=torch.bfloat16)
-    lse = torch.empty(B * A * N, device=DEV)
-    scr = torch.empty(_lib.lib().vitseg_attention_bwd_scratch_floats(B, Np, A), device=DEV)
-    dqkv = torch.full((Mt, 3 * D), float("nan"), device=DEV, dtype=torch.bfloat16)
-    mw = torch.empty(_lib.lib().vitseg_attention_dropmask_bytes(B, Np, A), dtype=torch.uint8, device=DEV) if words else None
+    qd, dd = _dev(qkv, name="qkv"), _dev(dctx, name="dctx")
+    ctx = _out((Mt, D), torch.bfloat16, name="ctx")
+    lse = _out((B * A * N,), name="lse")
+    scr = _out((_lib.lib().vitseg_attention_bwd_scratch_floats(B, Np, A),), name="attention_bwd scratch")
+    dqkv = _out((Mt, 3 * D), torch.bfloat16, name="dqkv")
+    mw = _out((_lib.lib().vitseg_attention_dropmask_bytes(B, Np, A),), torch.uint8, name="dropmask words") if words else None
+    snap = snapshot(qd, dd)
     _lib.check(_lib.lib().vitseg_op_attention_bwd_bf16(qd.data_ptr(), dd.data_ptr(), ctx.data_ptr(), lse.data_ptr(),
                                                        scr.data_ptr(), dqkv.data_ptr(), B, Np, A, p, seed, stream_id,
                                                        mw.data_ptr() if words else None, None, _stream()))
+    _after(snap, ctx, lse, scr, dqkv, mw)
     got = dqkv.float().cpu().double()
     assert torch.isfinite(got).all()
     # reference token order (CLS first) <- patches-first rows; [1, A, N, hd] views

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from guard import check, guarded, snapshot, unchanged
 from oracle import vitseg_oracle as O
 from visiontransformer_amd import _lib
 
@@ -19,20 +20,41 @@ def _rand(*shape, seed=0, scale=1.0):
     return (torch.randn(*shape, generator=g) * scale).float()
 
 
+def _dev(t, dtype=None, name=None):
+    """guard-banded device copy of a CPU tensor (tests/guard.py)"""
+    return guarded(tuple(t.shape), dtype or t.dtype, t, device=DEV, name=name)
+
+
+def _out(shape, dtype=torch.float32, fill="nan", name=None):
+    return guarded(shape, dtype, fill, device=DEV, name=name)
+
+
+def _after(snap, *outs):
+    """after a call: every guard (inputs and outputs) intact, every input bitwise unchanged"""
+    torch.cuda.synchronize()
+    check(*[t for t, _ in snap], *outs)
+    unchanged(snap)
+
+
 @pytest.mark.parametrize("rows,D", [(7, 192), (1025, 768), (33, 1024), (5, 2048), (9, 512)])
 def test_layernorm(rows, D):
     x, w, b = _rand(rows, D, seed=1, scale=3.0) + 0.5, _rand(D, seed=2) + 1.0, _rand(D, seed=3)
     ref = O.layer_norm(x.double(), w.double(), b.double(), 1e-12)
-    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
-    y = torch.empty_like(xd)
+    xd, wd, bd = _dev(x, name="x"), _dev(w, name="w"), _dev(b, name="b")
+    y = _out((rows, D), name="y")
+    snap = snapshot(xd, wd, bd)
     _lib.check(_lib.lib().vitseg_op_layernorm_f32(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), y.data_ptr(), rows, D,
                                                   1e-12, _stream()))
+    _after(snap, y)
     assert (y.cpu().double() - ref).abs().max().item() < 5e-6  # tolerance: fp32 rounding of O(1) outputs
 
 
 @pytest.mark.parametrize("M,N,K,epi", [
     (128, 128, 32, 0), (257, 192, 64, 0), (788, 576, 192, 0), (300, 768, 768, 1), (1025, 768, 3072, 2),
-    (130, 3072, 768, 1), (64, 256, 6912, 3), (33, 100, 48, 0), (2050, 2304, 768, 0)])
+    (130, 3072, 768, 1), (64, 256, 6912, 3), (33, 100, 48, 0), (2050, 2304, 768, 0),
+    # ragged against gemm.hip's 128x128 tiles and 32-deep K steps: M = 1, less than one tile, rows / columns either side
+    # of a tile edge (N and ldc are multiples of 4), K not a multiple of 32
+    (1, 64, 32, 0), (1, 768, 768, 2), (127, 132, 36, 1), (129, 124, 100, 0), (255, 260, 132, 2), (257, 388, 68, 3)])
 def test_linear_epilogues(M, N, K, epi):
     A, W, bias = _rand(M, K, seed=M), _rand(N, K, seed=N + 1, scale=0.05), _rand(N, seed=7, scale=0.1)
     R = _rand(M, N, seed=11)
@@ -45,15 +67,17 @@ def test_linear_epilogues(M, N, K, epi):
         ref = torch.relu(acc)
     else:
         ref = acc
-    Ad, Wd, bd, Rd = A.to(DEV), W.to(DEV), bias.to(DEV), R.to(DEV)
-    C = torch.full((M, N), float("nan"), device=DEV)
+    Ad, Wd, bd, Rd = _dev(A, name="A"), _dev(W, name="W"), _dev(bias, name="bias"), _dev(R, name="R")
+    C = _out((M, N), name="C")
     if epi == 2:  # in-place residual, as the forward uses it
         C.copy_(Rd)
         Rp = C.data_ptr()
     else:
         Rp = None
+    snap = snapshot(Ad, Wd, bd, Rd)
     _lib.check(_lib.lib().vitseg_op_linear_f32(Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), Rp, C.data_ptr(), M, N, K,
                                                epi, _stream()))
+    _after(snap, C)
     err = (C.cpu().double() - ref).abs().max().item()
     # fp32 fmaf chain over K terms of magnitude ~|a||w|: error ~ 1e-7 * sum|a w|
     bound = 4e-7 * (A.abs().double() @ W.abs().double().T).max().item() + 1e-6
@@ -70,6 +94,8 @@ def test_linear_epilogues(M, N, K, epi):
     (16384, 256, 96, 3, ""),             # ReLU, the minimum of 3 K steps (no inline epilogue below 4)
     (65536, 256, 128, 3, ""),            # ReLU, 4 K steps, 2 tiles per block
     (33024, 768, 64 * 5, 0, "nobias"),   # uneven tile counts per block, no bias
+    (8193, 640, 100, 0, ""),             # one row past a 256-row tile edge, K not a multiple of 32
+    (4097, 384, 36, 2, ""),              # ... a single K step short of one whole step, residual
 ])
 def test_linear_f32_persistent_kernel(M, N, K, epi, extra, monkeypatch):
     """csrc/gemm_f32p.hip (persistent 256x128 kernel of the fp32 linears) against a float64 product, and BITWISE against
@@ -88,20 +114,21 @@ def test_linear_f32_persistent_kernel(M, N, K, epi, extra, monkeypatch):
         ref = torch.relu(acc)
     else:
         ref = acc
-    Ad, Wd, Rd = A.to(DEV), W.to(DEV), R.to(DEV)
-    bd = bias.to(DEV) if bias is not None else None
+    Ad, Wd, Rd = _dev(A, name="A"), _dev(W, name="W"), _dev(R, name="R")
+    bd = _dev(bias, name="bias") if bias is not None else None
 
     def run():
-        C = torch.full((M, N), float("nan"), device=DEV)
-        aux = torch.full((M, N), float("nan"), device=DEV) if "aux" in extra else None
+        C = _out((M, N), name="C")
+        aux = _out((M, N), name="aux") if "aux" in extra else None
         Rp = None
         if epi == 2:  # in-place residual, as the forward uses it
             C.copy_(Rd)
             Rp = C.data_ptr()
+        snap = snapshot(Ad, Wd, Rd, bd)
         _lib.check(L.vitseg_op_linear_f32_ex(Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr() if bd is not None else None, Rp,
                                              C.data_ptr(), aux.data_ptr() if aux is not None else None, M, N, K, epi, p,
                                              seed, stream_id, _stream()))
-        torch.cuda.synchronize()
+        _after(snap, C, aux)
         return C, aux
 
     C, aux = run()
@@ -121,14 +148,18 @@ def test_linear_matches_fp32_fmaf_semantics_exactly_small():
     M = N = K = 128
     A = torch.eye(M)
     W = torch.arange(N * K, dtype=torch.float32).reshape(N, K) / 1024.0
-    C = torch.empty(M, N, device=DEV)
-    Ad, Wd = A.to(DEV), W.to(DEV)  # keep the device tensors alive across the call
+    C = _out((M, N), name="C")
+    Ad, Wd = _dev(A, name="A"), _dev(W, name="W")  # keep the device tensors alive across the call
+    snap = snapshot(Ad, Wd)
     _lib.check(_lib.lib().vitseg_op_linear_f32(Ad.data_ptr(), Wd.data_ptr(), None, None, C.data_ptr(),
                                                M, N, K, 0, _stream()))
+    _after(snap, C)
     assert torch.equal(C.cpu(), W.T.contiguous())
 
 
-@pytest.mark.parametrize("B,Np,A", [(2, 196, 3), (1, 1024, 2), (3, 784, 1), (1, 64, 1), (2, 128, 12), (1, 200, 2)])
+@pytest.mark.parametrize("B,Np,A", [(2, 196, 3), (1, 1024, 2), (3, 784, 1), (1, 64, 1), (2, 128, 12), (1, 200, 2),
+                                    # ragged against the query / key blocks: below one block, one either side of 128
+                                    (1, 4, 1), (2, 31, 2), (3, 127, 1), (1, 129, 3), (2, 200, 2)])
 def test_attention(B, Np, A):
     D = 64 * A
     Mt = B * Np + B
@@ -147,9 +178,11 @@ def test_attention(B, Np, A):
         q, k, v = [x64[r][:, i * D:(i + 1) * D].reshape(Np + 1, A, 64).transpose(0, 1) for i in range(3)]
         s = torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1)
         ref[r] = (s @ v).transpose(0, 1).reshape(Np + 1, D)
-    qd = qkv.to(DEV)
-    ctx = torch.full((Mt, D), float("nan"), device=DEV)
+    qd = _dev(qkv, name="qkv")
+    ctx = _out((Mt, D), name="ctx")
+    snap = snapshot(qd)
     _lib.check(_lib.lib().vitseg_op_attention_f32(qd.data_ptr(), ctx.data_ptr(), B, Np, A, _stream()))
+    _after(snap, ctx)
     err = (ctx.cpu().double() - ref).abs().max().item()
     assert err < 2e-5, err  # fp32 exp2/softmax on O(1) values
 
@@ -163,18 +196,21 @@ def test_upsample_sigmoid_argmax_bit_exact(B, C, g, S):
     ref_logits = O.upsample_bilinear(z, (S, S))
     assert torch.equal(ref_logits, torch.nn.functional.interpolate(z, size=(S, S), mode="bilinear", align_corners=False))
     ref_mask = O.predict_mask(ref_logits)
-    zd = z.to(DEV)
-    logits = torch.empty(B, C, S, S, device=DEV)
-    mask = torch.empty(B, S, S, dtype=torch.uint8, device=DEV)
+    zd = _dev(z, name="lowres")
+    logits = _out((B, C, S, S), name="logits")
+    mask = _out((B, S, S), torch.uint8, name="mask")
+    snap = snapshot(zd)
     _lib.check(_lib.lib().vitseg_op_upsample_argmax(zd.data_ptr(), logits.data_ptr(), mask.data_ptr(), B, C, g, S,
                                                     _stream()))
+    _after(snap, logits, mask)
     assert torch.equal(logits.cpu(), ref_logits)  # bit-exact: same fma placement as ATen's CPU kernel
     # every pixel, ties and saturated classes included: the kernel restates ATen's fp32 sigmoid (Sleef u10 exp, exact
     # add and divide) operation by operation, as the oracle does (pinned against torch.sigmoid on the CPU)
     assert torch.equal(mask.cpu().long(), ref_mask)
     # mask-only call (logits pointer NULL) gives the same mask
-    mask2 = torch.empty_like(mask)
+    mask2 = _out((B, S, S), torch.uint8, name="mask2")
     _lib.check(_lib.lib().vitseg_op_upsample_argmax(zd.data_ptr(), None, mask2.data_ptr(), B, C, g, S, _stream()))
+    _after(snap, mask2)
     assert torch.equal(mask, mask2)
 
 
@@ -187,11 +223,13 @@ def test_upsample_backward_is_the_adjoint(B, C, g, S):
     gl = _rand(B, C, S, S, seed=S + g + C)
     z = torch.zeros(B, C, g, g, dtype=torch.float64, requires_grad=True)
     torch.nn.functional.interpolate(z, size=(S, S), mode="bilinear", align_corners=False).backward(gl.double())
-    gd = gl.to(DEV)
-    out = torch.full((B, C, g, g), float("nan"), device=DEV)
+    gd = _dev(gl, name="grad_logits")
+    snap = snapshot(gd)
+    out = _out((B, C, g, g), name="grad_lowres")
     _lib.check(_lib.lib().vitseg_op_upsample_bwd(gd.data_ptr(), out.data_ptr(), B, C, g, S, _stream()))
-    out2 = torch.full((B, C, g, g), float("nan"), device=DEV)
+    out2 = _out((B, C, g, g), name="grad_lowres 2")
     _lib.check(_lib.lib().vitseg_op_upsample_bwd(gd.data_ptr(), out2.data_ptr(), B, C, g, S, _stream()))
+    _after(snap, out, out2)
     ref = z.grad
     err = (out.cpu().double() - ref).abs().max().item()
     assert err <= 2e-6 * max(1.0, ref.abs().max().item()) * (S // g), (err, ref.abs().max().item())   # fp32 sums of (S/g)^2 ... 4 (S/g)^2 terms
@@ -203,12 +241,14 @@ def test_upsample_backward_adjoint_identity_full_size():
     <upsample(z), G> = <z, upsample_bwd(G)> with the HIP forward kernel (itself bit-exact against ATen) on the left."""
     B, C, g, S = 64, 2, 32, 512
     gen = torch.Generator(device="cpu").manual_seed(11)
-    z = torch.randn(B, C, g, g, generator=gen).to(DEV)
-    G = torch.randn(B, C, S, S, generator=gen).to(DEV)
-    up = torch.empty(B, C, S, S, device=DEV)
+    z = _dev(torch.randn(B, C, g, g, generator=gen), name="z")
+    G = _dev(torch.randn(B, C, S, S, generator=gen), name="G")
+    snap = snapshot(z, G)
+    up = _out((B, C, S, S), name="up")
     _lib.check(_lib.lib().vitseg_op_upsample_argmax(z.data_ptr(), up.data_ptr(), None, B, C, g, S, _stream()))
-    dz = torch.empty(B, C, g, g, device=DEV)
+    dz = _out((B, C, g, g), name="dz")
     _lib.check(_lib.lib().vitseg_op_upsample_bwd(G.data_ptr(), dz.data_ptr(), B, C, g, S, _stream()))
+    _after(snap, up, dz)
     lhs = (up.double() * G.double()).sum().item()
     rhs = (z.double() * dz.double()).sum().item()
     scale = (up.double() * G.double()).abs().sum().item()
@@ -227,12 +267,15 @@ def test_upsample_mask_only_two_classes(scale, delta, S, g):
     z0 = _rand(B, 1, g, g, seed=S + g, scale=scale)
     z = torch.cat([z0, z0 + delta * _rand(B, 1, g, g, seed=7)], dim=1).contiguous()
     ref_mask = O.predict_mask(O.upsample_bilinear(z, (S, S)))
-    zd = z.to(DEV)
-    m_fast = torch.full((B, S, S), 7, dtype=torch.uint8, device=DEV)
+    zd = _dev(z, name="lowres")
+    snap = snapshot(zd)
+    sevens = torch.full((B, S, S), 7, dtype=torch.uint8)
+    m_fast = _dev(sevens, name="mask")
     _lib.check(_lib.lib().vitseg_op_upsample_argmax(zd.data_ptr(), None, m_fast.data_ptr(), B, 2, g, S, _stream()))
     with _lib.option("no_mask2", 1):
-        m_gen = torch.full((B, S, S), 7, dtype=torch.uint8, device=DEV)
+        m_gen = _dev(sevens, name="mask (general kernel)")
         _lib.check(_lib.lib().vitseg_op_upsample_argmax(zd.data_ptr(), None, m_gen.data_ptr(), B, 2, g, S, _stream()))
+    _after(snap, m_fast, m_gen)
     assert torch.equal(m_fast.cpu().long(), ref_mask)
     assert torch.equal(m_fast, m_gen)
     if delta == 0.0:
@@ -248,7 +291,11 @@ FMT = {"bf16": (torch.bfloat16, 2 ** -8, "vitseg_op_linear_bf16", "vitseg_op_att
                                        (2050, 2304, 768, 0), (33, 96, 64, 2), (130, 3072, 768, 1),
                                        (4129, 768, 768, 0), (4608, 384, 192, 1), (5000, 200, 3072, 2), (8224, 2304, 768, 0),
                                        (16584, 2304, 768, 0),   # 585 tiles: three per block of gemm_h16p.hip, ragged last row tile
-                                       (66048, 768, 512, 0)])   # 774 tiles of a short reduction (8 K steps per tile)
+                                       (66048, 768, 512, 0),    # 774 tiles of a short reduction (8 K steps per tile)
+                                       # ragged: M = 1, less than one tile, and both sides of the 8-phase / h16p kernels'
+                                       # conditions (M >= 2048, N % 256, K % 128, K <= 1024 for h16p)
+                                       (1, 64, 64, 0), (127, 132, 64, 1), (2047, 512, 256, 0), (2048, 512, 256, 0),
+                                       (2049, 512, 256, 0), (2049, 520, 256, 0), (2049, 512, 320, 2), (2049, 512, 1152, 0)])
 @pytest.mark.parametrize("fmt", ["bf16", "fp16"])
 def test_linear_bf16(M, N, K, epi, fmt):
     dt, ulp, fn, _ = FMT[fmt]
@@ -256,16 +303,18 @@ def test_linear_bf16(M, N, K, epi, fmt):
     bias, R = _rand(N, seed=7, scale=0.1), _rand(M, N, seed=11)
     acc = A.double() @ W.double().T + bias.double()  # exact products of bf16 values, fp32-accumulated on device
     ref = O.gelu_erf(acc) if epi == 1 else (R.double() + acc if epi == 2 else acc)
-    Ad, Wd = A.to(DEV).to(dt), W.to(DEV).to(dt)
-    bd, Rd = bias.to(DEV), R.to(DEV)
+    Ad, Wd = _dev(A, dt, name="A"), _dev(W, dt, name="W")
+    bd = _dev(bias, name="bias")
     if epi == 2:
-        C = Rd.clone()
+        C = _dev(R, name="C")
         Rp = C.data_ptr()
     else:
-        C = torch.zeros(M, N, device=DEV, dtype=dt)
+        C = _out((M, N), dt, name="C")
         Rp = None
+    snap = snapshot(Ad, Wd, bd)
     _lib.check(getattr(_lib.lib(), fn)(Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), Rp, C.data_ptr(), M, N, K, epi,
                                        _stream()))
+    _after(snap, C)
     got = C.float().cpu().double()
     scale = (A.abs().double() @ W.abs().double().T).max().item()
     if epi == 2:   # fp32 output: only fp32 accumulation error
@@ -274,7 +323,9 @@ def test_linear_bf16(M, N, K, epi, fmt):
         assert ((got - ref).abs() <= ulp * ref.abs() + 4e-7 * scale + 1e-6).all()
 
 
-@pytest.mark.parametrize("B,Np,A", [(2, 196, 3), (1, 1024, 2), (3, 784, 1), (1, 64, 1), (2, 128, 12), (1, 200, 2)])
+@pytest.mark.parametrize("B,Np,A", [(2, 196, 3), (1, 1024, 2), (3, 784, 1), (1, 64, 1), (2, 128, 12), (1, 200, 2),
+                                    # ragged against the query / key blocks: below one block, one either side of 128
+                                    (1, 4, 1), (2, 31, 2), (3, 127, 1), (1, 129, 3), (2, 200, 2)])
 @pytest.mark.parametrize("fmt", ["bf16", "fp16"])
 def test_attention_bf16(B, Np, A, fmt):
     dt, ulp, _, fn = FMT[fmt]
@@ -290,9 +341,11 @@ def test_attention_bf16(B, Np, A, fmt):
         q, k, v = [x64[r][:, i * D:(i + 1) * D].reshape(Np + 1, A, 64).transpose(0, 1) for i in range(3)]
         s = torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1)
         ref[r] = (s @ v).transpose(0, 1).reshape(Np + 1, D)
-    qd = qkv.to(DEV).to(dt)
-    ctx = torch.zeros(Mt, D, device=DEV, dtype=dt)
+    qd = _dev(qkv, dt, name="qkv")
+    ctx = _out((Mt, D), dt, name="ctx")
+    snap = snapshot(qd)
     _lib.check(getattr(_lib.lib(), fn)(qd.data_ptr(), ctx.data_ptr(), B, Np, A, _stream()))
+    _after(snap, ctx)
     err = (ctx.float().cpu().double() - ref).abs().max().item()
     # P is rounded to the operand format (2^-9 / 2^-12 relative) before P.V and the output is rounded too: |v| <= ~6
     assert err < 4e-2 * ulp * 2 ** 8, err
@@ -311,22 +364,27 @@ def test_linear_f32x3_is_fp32_grade(M, N, K, epi):
     bias, R = _rand(N, seed=7, scale=0.1), _rand(M, N, seed=11)
     acc = A.double() @ W.double().T + bias.double()
     ref = O.gelu_erf(acc) if epi == 1 else (R.double() + acc if epi == 2 else acc)
-    Ad, Wd, bd, Rd = A.to(DEV), W.to(DEV), bias.to(DEV), R.to(DEV)
-    C = Rd.clone() if epi == 2 else torch.zeros(M, N, device=DEV)
+    Ad, Wd, bd, Rd = _dev(A, name="A"), _dev(W, name="W"), _dev(bias, name="bias"), _dev(R, name="R")
+    C = _dev(R, name="C") if epi == 2 else _out((M, N), name="C")
+    snap = snapshot(Ad, Wd, bd, Rd)
     _lib.check(_lib.lib().vitseg_op_linear_f32x3(Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), C.data_ptr() if epi == 2 else None,
                                                  C.data_ptr(), M, N, K, epi, _stream()))
+    _after(snap, C)
     scale = (A.abs().double() @ W.abs().double().T)
     err = ((C.cpu().double() - ref).abs() / (scale + 1e-3)).max().item()
     assert err < 1e-6, err
     # against the true-fp32 kernel: they agree to fp32 accumulation noise (which grows with sqrt(K) in that kernel's
     # sequential 32x32x2 chains; the 16-wide half MFMAs of the split path accumulate fewer, wider steps)
-    C32 = Rd.clone() if epi == 2 else torch.zeros(M, N, device=DEV)
+    C32 = _dev(R, name="C32") if epi == 2 else _out((M, N), name="C32")
     _lib.check(_lib.lib().vitseg_op_linear_f32(Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), C32.data_ptr() if epi == 2 else None,
                                                C32.data_ptr(), M, N, K, epi, _stream()))
+    _after(snap, C32)
     assert ((C - C32).abs().cpu().double() / (scale + 1e-3)).max().item() < 1e-5
 
 
-@pytest.mark.parametrize("B,Np,A", [(2, 196, 3), (1, 1024, 2), (3, 784, 1), (1, 64, 1), (2, 128, 12), (1, 200, 2)])
+@pytest.mark.parametrize("B,Np,A", [(2, 196, 3), (1, 1024, 2), (3, 784, 1), (1, 64, 1), (2, 128, 12), (1, 200, 2),
+                                    # ragged against the query / key blocks: below one block, one either side of 128
+                                    (1, 4, 1), (2, 31, 2), (3, 127, 1), (1, 129, 3), (2, 200, 2)])
 def test_attention_f32x3_is_fp32_grade(B, Np, A):
     """Split-operand attention (attention_x3.hip): fp32 in / fp32 out, QK^T and PV as 3 half MFMAs per product.
     Same inputs and same tolerance as the exact-fp32 kernel's test."""
@@ -342,13 +400,16 @@ def test_attention_f32x3_is_fp32_grade(B, Np, A):
         q, k, v = [x64[r][:, i * D:(i + 1) * D].reshape(Np + 1, A, 64).transpose(0, 1) for i in range(3)]
         s = torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1)
         ref[r] = (s @ v).transpose(0, 1).reshape(Np + 1, D)
-    qd = qkv.to(DEV)
-    ctx = torch.full((Mt, D), float("nan"), device=DEV)
+    qd = _dev(qkv, name="qkv")
+    ctx = _out((Mt, D), name="ctx")
+    snap = snapshot(qd)
     _lib.check(_lib.lib().vitseg_op_attention_f32x3(qd.data_ptr(), ctx.data_ptr(), B, Np, A, _stream()))
+    _after(snap, ctx)
     err = (ctx.cpu().double() - ref).abs().max().item()
     assert err < 2e-5, err
-    ctx32 = torch.empty_like(ctx)
+    ctx32 = _out((Mt, D), name="ctx32")
     _lib.check(_lib.lib().vitseg_op_attention_f32(qd.data_ptr(), ctx32.data_ptr(), B, Np, A, _stream()))
+    _after(snap, ctx32)
     print(f"attention x3 max err {err:.2e}, exact-fp32 kernel {(ctx32.cpu().double() - ref).abs().max().item():.2e}")
 
 
@@ -403,18 +464,18 @@ def test_linear_h16_tile_variants(M, N, K, epi, extra, fmt, request):
     bias = _rand(N, seed=7, scale=0.1)
     acc = A.double() @ W.double().T
     scale = float((A.abs().double() @ W.abs().double().T).max())
-    Ad, Wd, bd = A.to(DEV).to(dt), W.to(DEV).to(dt), bias.to(DEV)
+    Ad, Wd, bd = _dev(A, dt, name="A"), _dev(W, dt, name="W"), _dev(bias, name="bias")
     thin = M % 256 if "thin" in extra else 0             # the trailing "CLS" rows; the body is whole 256-row tiles
-    scratch = torch.empty(16 * 64 * max(N, 3072), device=DEV) if thin else None
+    scratch = _out((16 * 64 * max(N, 3072),), name="thin scratch") if thin else None
     p, seed, stream_id = (0.1, 0x1234ABCD, 13) if "drop" in extra else (0.0, 0, 0)
-    aux = torch.zeros(M, N, device=DEV, dtype=dt) if "aux" in extra else None
-    cs_out = cs_scr = None
+    aux = _out((M, N), dt, name="aux") if "aux" in extra else None
+    cs_out = cs_scr = Ud = None
     if epi == 5 and fmt == "bf16":   # every dGELU case also asks for the fused column sums (all dispatch paths)
-        cs_out = torch.full((N,), float("nan"), device=DEV)
-        cs_scr = torch.empty(_lib.lib().vitseg_op_colsum_scratch_floats(M, N), device=DEV)
+        cs_out = _out((N,), name="colsum")
+        cs_scr = _out((_lib.lib().vitseg_op_colsum_scratch_floats(M, N),), name="colsum scratch")
     if epi == 2:
         R = _rand(M, N, seed=11)
-        C = R.to(DEV)
+        C = _dev(R, name="C")
         Rp = C.data_ptr()                                  # in place, as the forward uses it
         y = acc + bias.double()
         if p:
@@ -422,20 +483,22 @@ def test_linear_h16_tile_variants(M, N, K, epi, extra, fmt, request):
         ref = R.double() + y
     elif epi == 5:
         U = _gelu_grad64(_rand(M, N, seed=12).double()).float().to(dt)   # the saved 16-bit gelu'(pre-activation)
-        Ud = U.to(DEV)
+        Ud = _dev(U, name="gelu'")
         Rp = Ud.data_ptr()
-        C = torch.zeros(M, N, device=DEV, dtype=dt)
+        C = _out((M, N), dt, name="C")
         bd = None
         ref = acc * U.double()
     else:
-        C = torch.zeros(M, N, device=DEV, dtype=dt)
+        C = _out((M, N), dt, name="C")
         Rp = None
         ref = O.gelu_erf(acc + bias.double()) if epi == 1 else acc + bias.double()
+    snap = snapshot(Ad, Wd, bd, Ud)
     _lib.check(_lib.lib().vitseg_op_linear_h16_ex(
         Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr() if bd is not None else None, Rp, C.data_ptr(),
         aux.data_ptr() if aux is not None else None, M, N, K, epi, int(fmt == "fp16"), thin,
         scratch.data_ptr() if thin else None, scratch.numel() if thin else 0, p, seed, stream_id,
         cs_out.data_ptr() if cs_out is not None else None, cs_scr.data_ptr() if cs_out is not None else None, _stream()))
+    _after(snap, C, aux, scratch, cs_out, cs_scr)
     got = C.float().cpu().double()
     if cs_out is not None:   # the bias gradient from the epilogue's per-tile partial sums (unrounded fp32 values), fixed order
         # (the paths without the 8-phase kernel sum the bf16-rounded C instead: independent roundings of 2^-9 relative)
@@ -467,11 +530,13 @@ def test_wgrad_bf16_both_operands_token_major(M, N, K):
     X = _rand(K, N, seed=N + 3, scale=0.5).to(torch.bfloat16)
     ref = dY.double().T @ X.double()
     scale = float((dY.abs().double().T @ X.abs().double()).max())
-    dYd, Xd = dY.to(DEV), X.to(DEV)
-    dW = torch.full((M, N), float("nan"), device=DEV)
-    zeros = torch.zeros(256, dtype=torch.uint8, device=DEV)
+    dYd, Xd = _dev(dY, name="dY"), _dev(X, name="X")
+    dW = _out((M, N), name="dW")
+    zeros = _out((256,), torch.uint8, "zero", name="zero page")
     n = _lib.lib().vitseg_op_wgrad_bf16_scratch_floats(M, N, K)
-    scratch = torch.empty(n, device=DEV)
+    scratch = _out((n,), name="wgrad scratch")
+    snap = snapshot(dYd, Xd, zeros)
     _lib.check(_lib.lib().vitseg_op_wgrad_bf16(dYd.data_ptr(), Xd.data_ptr(), dW.data_ptr(), scratch.data_ptr(),
                                                zeros.data_ptr(), M, N, K, _stream()))
+    _after(snap, dW, scratch)
     assert (dW.cpu().double() - ref).abs().max().item() < 4e-7 * scale + 1e-5

@@ -364,7 +364,11 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
         float wy0, wy1, wx0, wx1;
         taps(Y, scale, g, y0, y1, wy0, wy1);
         taps(X, scale, g, x0, x1, wx0, wx1);
-        const int t = (int)target[idx];
+        // a label outside [0, C) (uint8 255, the reference's ignore_index -100, C itself) is not a class: its pixel's loss
+        // and gradient are NaN, so the mean loss is NaN rather than a plausible wrong number (ignore_index is not supported)
+        const long long tl = (long long)target[idx];
+        const bool bad = tl < 0 || tl >= C;
+        const int t = bad ? -1 : (int)tl;
         auto logit = [&](int c) {
             const float* zt = Z + (((size_t)b * C + c) * g + y0) * g;
             const float* zb = Z + (((size_t)b * C + c) * g + y1) * g;
@@ -381,12 +385,12 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
             m = mn;
         }
         const float lse = m + logf(ssum);
-        local = (double)(lse - picked);
+        local = bad ? (double)NAN : (double)(lse - picked);
         if (G) {
             const float inv = gscale / (float)npx;   // gscale: the upstream d(total loss) / d(this loss), e.g. 1 / accumulation
             for (int c = 0; c < C; ++c) {
                 const float pc = expf(logit(c) - lse);
-                G[(((size_t)b * C + c) * S + Y) * S + X] = (pc - (c == t ? 1.f : 0.f)) * inv;
+                G[(((size_t)b * C + c) * S + Y) * S + X] = bad ? NAN : (pc - (c == t ? 1.f : 0.f)) * inv;
             }
         }
     }

@@ -441,7 +441,8 @@ class ViTSegmentationModel(nn.Module):
     def ce_loss(self, x: torch.Tensor, target: torch.Tensor, grad_scale: Optional[float] = None) -> torch.Tensor:
         """`nn.CrossEntropyLoss()(self(x), target)` (model/CE/classes.py:268,280) as a device scalar, without
         materialising the [B, C, S, S] logits: forward to the low-res map, then the fused upsample+CE kernel.
-        `target`: class indices [B, S, S], torch.long (reference) or torch.uint8, on the model's device.
+        `target`: class indices [B, S, S], torch.long (reference) or torch.uint8, on the model's device.  Labels must lie
+        in [0, C): `ignore_index` is not supported, and any other label (255, -100, C) makes the loss NaN.
         `grad_scale` (optional): the gradient `loss.backward()` deposits is grad_scale * d loss / d params, folded into
         the CE gradient inside the kernel (e.g. 1 / accumulate_grad_batches); call `.backward()` on the returned loss
         itself then -- an upstream factor is ignored in this mode."""
