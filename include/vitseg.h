@@ -147,6 +147,28 @@ int vitseg_workspace_offset(const vitseg_config* cfg, int batch, int precision, 
 int vitseg_forward(const vitseg_config* cfg, const float* params, const void* params_bf16, const float* x, int batch,
                    int precision, float* logits, uint8_t* mask, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- other input sizes (Hugging Face ViTModel.forward(..., interpolate_pos_encoding=True)) ----
+ * The same calls for an input of side image_size_in through the arena of cfg: the arena, its layout
+ * (vitseg_param_offset) and its [1 + g0^2, D] position table keep cfg's geometry (g0 = cfg->image_size / P); the
+ * activations, x, logits and mask take the input's (S = image_size_in, g1 = S / P).  When g1 != g0 the forward first
+ * resamples the table into the workspace (vitseg_pos_interp) and the embeddings add that one; when g1 == g0 every call
+ * here is exactly its plain form (same workspace size and offsets, same launches, same bits).  image_size_in must be a
+ * positive multiple of P whose derived configuration passes the usual checks (VITSEG_ESHAPE otherwise).
+ * vitseg_forward_route takes a cfg whose image_size is the input's: the route depends on the activations only. */
+int vitseg_query_workspace_at(const vitseg_config* cfg, int image_size_in, int batch, int precision, size_t* bytes);
+int vitseg_workspace_offset_at(const vitseg_config* cfg, int image_size_in, int batch, int precision, int buffer,
+                               size_t* offset_bytes, size_t* bytes);
+int vitseg_forward_at(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16,
+                      const float* x, int batch, int precision, float* logits, uint8_t* mask, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* The resampling on its own: pos_out [1 + g1^2, D] from pos_in [1 + g0^2, D] -- row 0 (CLS) copied, the g0 x g0 grid
+ * through F.interpolate(size=(g1, g1), mode="bicubic", align_corners=False) per channel (A = -0.75, taps clamped to the
+ * grid), each output summed in a fixed order.  vitseg_pos_interp_bwd is its adjoint: dpos_in [1 + g0^2, D] (overwritten)
+ * from dpos_out [1 + g1^2, D], two separable passes (x, then y) through scratch (>= g1 * g0 * D floats), no atomics:
+ * reproducible bit for bit. */
+int vitseg_pos_interp(const float* pos_in, float* pos_out, int g0, int g1, int D, void* stream);
+int vitseg_pos_interp_bwd(const float* dpos_out, float* dpos_in, float* scratch, int g0, int g1, int D, void* stream);
+
 /* ---- single-operator entry points (same kernels the forward uses; exported so each
  *      stage can be checked against the oracle in isolation) ---- */
 int vitseg_op_layernorm_f32(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps,
@@ -285,6 +307,18 @@ int vitseg_backward(const vitseg_config* cfg, const float* params, const void* p
  * vitseg_backward records bucket_events[i] (hipEvent_t, created by the caller; NULL array or NULL entries = skip)
  * on `stream` right after the last kernel that writes bucket i, so a communication stream can wait on it and
  * reduce that range while the rest of the backward still runs. */
+/* The training calls for an input of side image_size_in (see vitseg_forward_at): the forward adds the resampled table,
+ * the backward maps the position-embedding gradient back to the arena's grid (vitseg_pos_interp_bwd) before the
+ * embeddings' gradient bucket is recorded; `grads` has the arena's layout.  With image_size_in == cfg->image_size
+ * exactly the plain calls. */
+int vitseg_train_workspace_at(const vitseg_config* cfg, int image_size_in, int batch, int precision, size_t* bytes);
+int vitseg_forward_train_at(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16,
+                            const float* x, int batch, int precision, float dropout_p, uint64_t dropout_seed, float* logits,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int vitseg_backward_at(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16,
+                       const float* x, int batch, int precision, float dropout_p, uint64_t dropout_seed, const void* target,
+                       int target_is_u8, const float* grad_logits, float* grads, float* loss, float loss_scale,
+                       void* const* bucket_events, void* workspace, size_t workspace_bytes, void* stream);
 int vitseg_grad_bucket_count(const vitseg_config* cfg);
 int vitseg_grad_bucket_range(const vitseg_config* cfg, int bucket, size_t* offset_floats, size_t* n_floats);
 /* ---- pre-processing (replaces transforms.Resize((S, S)) + transforms.ToTensor() on the PIL image,

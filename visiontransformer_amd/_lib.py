@@ -38,6 +38,13 @@ EXPORTS = [
     "vitseg_small_splits", "vitseg_op_linear_f32_small", "vitseg_op_linear_resln_f32_small", "vitseg_op_attention_f32_small", "vitseg_op_attention_bwd_f32_small", "vitseg_op_linear_h16_small", "vitseg_op_attention_h16_small", "vitseg_forward_route", "vitseg_op_layernorm_bwd_f32_small",
     "vitseg_dbg_linear_f32_small", "vitseg_adamw_step", "vitseg_op_dgrad_f32_small", "vitseg_op_wgrad_f32_small", "vitseg_op_layernorm_bwd_scratch_floats",
 ]
+# other input sizes (interpolated position embeddings): bound on first use, so that a library built before them still
+# serves everything else; the new path alone raises a "rebuild" error against it (`at_symbol`)
+AT_EXPORTS = [
+    "vitseg_query_workspace_at", "vitseg_workspace_offset_at", "vitseg_forward_at", "vitseg_train_workspace_at",
+    "vitseg_forward_train_at", "vitseg_backward_at", "vitseg_pos_interp", "vitseg_pos_interp_bwd",
+]
+EXPORTS += AT_EXPORTS   # every symbol include/vitseg.h declares
 VERSION = 110   # include/vitseg.h VITSEG_VERSION this binding was written against
 KERNEL_KINDS = ["gemm_bias", "gemm_gelu", "gemm_resadd", "gemm_patch", "gemm_conv3", "attention", "layernorm",
                 "head1x1", "upsample", "train_gemm_fwd", "train_dgrad", "train_wgrad", "train_attn_fwd", "train_attn_bwd"]
@@ -148,12 +155,44 @@ def lib() -> C.CDLL:
         l.vitseg_profile_enable.argtypes = [i32]
         l.vitseg_profile_collect.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
         for name in EXPORTS:
-            getattr(l, name)  # raises AttributeError if the build is stale
+            if name not in AT_EXPORTS:
+                getattr(l, name)  # raises AttributeError if the build is stale
+        for name, args in _at_argtypes(vp, sz, i32, pcfg, psz).items():
+            fn = getattr(l, name, None)
+            if fn is not None:
+                fn.argtypes = args
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
         _lib = l
     return _lib
+
+
+def _at_argtypes(vp, sz, i32, pcfg, psz) -> dict:
+    f32 = C.c_float
+    return {
+        "vitseg_query_workspace_at": [pcfg, i32, i32, i32, psz],
+        "vitseg_workspace_offset_at": [pcfg, i32, i32, i32, i32, psz, psz],
+        "vitseg_forward_at": [pcfg, i32, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp],
+        "vitseg_train_workspace_at": [pcfg, i32, i32, i32, psz],
+        "vitseg_forward_train_at": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, vp, sz, vp],
+        "vitseg_backward_at": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp],
+        "vitseg_pos_interp": [vp, vp, i32, i32, i32, vp],
+        "vitseg_pos_interp_bwd": [vp, vp, vp, i32, i32, i32, vp],
+    }
+
+
+def at_symbol(name: str):
+    """One of AT_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before interpolated position embeddings): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def _native(cfg: ViTSegConfig, image_size) -> bool:
+    return image_size is None or int(image_size) == cfg.image_size
 
 
 def check(rc: int) -> None:
@@ -206,30 +245,47 @@ def param_offset(cfg: ViTSegConfig, tensor: int, layer: int = 0):
     return off.value, n.value
 
 
-def query_workspace(cfg: ViTSegConfig, batch: int, precision: int) -> int:
+def query_workspace(cfg: ViTSegConfig, batch: int, precision: int, image_size=None) -> int:
+    """Bytes of the forward workspace; `image_size`: the input's side when it differs from cfg's (vitseg_query_workspace_at)."""
     n = C.c_size_t()
-    check(lib().vitseg_query_workspace(C.byref(CConfig.from_config(cfg)), batch, precision, C.byref(n)))
+    if _native(cfg, image_size):
+        check(lib().vitseg_query_workspace(C.byref(CConfig.from_config(cfg)), batch, precision, C.byref(n)))
+    else:
+        check(at_symbol("vitseg_query_workspace_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
+                                                     C.byref(n)))
     return n.value
 
 
-def forward_route(cfg: ViTSegConfig, batch: int, precision: int) -> str:
-    """"small" (the small-batch route of csrc/small.hpp) or "large": which kernels vitseg_forward takes for this call."""
-    rc = lib().vitseg_forward_route(C.byref(CConfig.from_config(cfg)), batch, precision)
+def forward_route(cfg: ViTSegConfig, batch: int, precision: int, image_size=None) -> str:
+    """"small" (the small-batch route of csrc/small.hpp) or "large": which kernels vitseg_forward takes for this call.  The
+    route depends on the activations only, so an input of another size asks with cfg at that size."""
+    c = CConfig.from_config(cfg)
+    if not _native(cfg, image_size):
+        c.image_size = int(image_size)
+    rc = lib().vitseg_forward_route(C.byref(c), batch, precision)
     if rc < 0:
         check(rc)
     return "small" if rc == 1 else "large"
 
 
-def workspace_offset(cfg: ViTSegConfig, batch: int, precision: int, buffer: int):
+def workspace_offset(cfg: ViTSegConfig, batch: int, precision: int, buffer: int, image_size=None):
     off, n = C.c_size_t(), C.c_size_t()
-    check(lib().vitseg_workspace_offset(C.byref(CConfig.from_config(cfg)), batch, precision, buffer,
-                                        C.byref(off), C.byref(n)))
+    if _native(cfg, image_size):
+        check(lib().vitseg_workspace_offset(C.byref(CConfig.from_config(cfg)), batch, precision, buffer,
+                                            C.byref(off), C.byref(n)))
+    else:
+        check(at_symbol("vitseg_workspace_offset_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
+                                                      buffer, C.byref(off), C.byref(n)))
     return off.value, n.value
 
 
-def train_workspace(cfg: ViTSegConfig, batch: int, precision: int) -> int:
+def train_workspace(cfg: ViTSegConfig, batch: int, precision: int, image_size=None) -> int:
     n = C.c_size_t()
-    check(lib().vitseg_train_workspace(C.byref(CConfig.from_config(cfg)), batch, precision, C.byref(n)))
+    if _native(cfg, image_size):
+        check(lib().vitseg_train_workspace(C.byref(CConfig.from_config(cfg)), batch, precision, C.byref(n)))
+    else:
+        check(at_symbol("vitseg_train_workspace_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
+                                                     C.byref(n)))
     return n.value
 
 

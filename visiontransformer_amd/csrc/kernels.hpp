@@ -164,6 +164,10 @@ int launch_im2col_patch_bf16(const float* img, void* T, int B, int Cin, int S, i
 int launch_im2col_patch(const float* img, float* T, int B, int Cin, int S, int P, hipStream_t s);
 int launch_conv_dgrad_weight(const float* W0, float* Wd, int D, hipStream_t s);
 int launch_embed_bwd(const float* dX, float* dpos, float* dcls, int B, int Np, int D, hipStream_t s);
+// position table [1 + g0^2, D] -> [1 + g1^2, D] (bicubic, HF interpolate_pos_encoding) and its adjoint (pos_interp.hip);
+// scratch of the adjoint: g1 * g0 * D floats
+int launch_pos_interp(const float* src, float* dst, int g0, int g1, int D, hipStream_t s);
+int launch_pos_interp_bwd(const float* dout, float* din, float* scratch, int g0, int g1, int D, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step,
                 float grad_scale, hipStream_t s, float weight_decay = 0.f);
 

@@ -45,6 +45,17 @@ inline int check_config(const vitseg_config* c, Shape* s) {
     return VITSEG_OK;
 }
 
+// An input of side image_size_in through the arena of cfg (Hugging Face's interpolate_pos_encoding): *s0 = the arena's
+// shape (its layout, its position table), *cin = cfg at the input's size, *s = the activations' shape.
+inline int derive_input(const vitseg_config* cfg, int image_size_in, vitseg_config* cin, Shape* s, Shape* s0) {
+    if (int rc = check_config(cfg, s0)) return rc;
+    VITSEG_CHECK_ARG(image_size_in >= s0->P && image_size_in % s0->P == 0, VITSEG_ESHAPE,
+                     "image_size_in %d is not a positive multiple of patch_size %d", image_size_in, s0->P);
+    *cin = *cfg;
+    cin->image_size = image_size_in;
+    return check_config(cin, s);
+}
+
 inline size_t tensor_numel(const Shape& s, int t) {
     const size_t D = s.D, I = s.I;
     switch (t) {

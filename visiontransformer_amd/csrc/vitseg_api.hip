@@ -72,12 +72,14 @@ using namespace plan;
 
 // ---- workspace plan -------------------------------------------------------------
 struct Plan {
-    size_t zero, x, h, qkv, u, f, z, thin, total;  // byte offsets
+    size_t zero, x, h, qkv, u, f, z, thin, pos, total;  // byte offsets (pos: the resampled position table, 0 = none)
     size_t thin_floats;                // capacity of the split-K scratch
     size_t Mt, Mp;                     // total token rows, patch rows
 };
 
-Plan make_plan(const Shape& s, int B, int precision) {
+// s: the activations' shape (the input's grid); pos_interp: the input's grid differs from the arena's, so the position
+// table resampled to it gets a region of its own (after every other, so that the offsets above do not move)
+Plan make_plan(const Shape& s, int B, int precision, bool pos_interp = false) {
     Plan p{};
     p.Mp = (size_t)B * s.Np;
     p.Mt = p.Mp + B;
@@ -110,6 +112,7 @@ Plan make_plan(const Shape& s, int B, int precision) {
             if (n > p.thin_floats) p.thin_floats = n;
     }
     p.thin = take(p.thin_floats * 4);
+    if (pos_interp) p.pos = take((size_t)s.N * s.D * 4);
     p.total = off;
     return p;
 }
@@ -122,7 +125,7 @@ Plan make_plan(const Shape& s, int B, int precision) {
 // kernels, the attention products too (q, k, P, v rounded in registers, fp32 softmax); the residual stream, q | k | v as stored,
 // the patch embedding and the head stay fp32.
 int forward_small(const vitseg_config* cfg, const Shape& s, const Layout& lay, const Plan& p, const float* params, const void* params_lp,
-                  int precision, const float* x, int batch, float* logits, uint8_t* mask, char* ws, hipStream_t st) {
+                  const float* pos, int precision, const float* x, int batch, float* logits, uint8_t* mask, char* ws, hipStream_t st) {
     auto W = [&](int t, int layer = 0) { return params + tensor_offset(lay, t, layer); };
     const int h16 = precision == VITSEG_BF16 ? 1 : precision == VITSEG_F16 ? 2 : 0;
     float* X = (float*)(ws + p.x);
@@ -149,7 +152,7 @@ int forward_small(const vitseg_config* cfg, const Shape& s, const Layout& lay, c
         SRows r{};
         r.h_fmt = h_fmt;
         r.X = X; r.partial = part; r.split_stride = dstride; r.splits = splits; r.bias = bias;
-        r.pos = W(VITSEG_T_POS); r.cls = W(VITSEG_T_CLS); r.lnw = lnw; r.lnb = lnb; r.H = H;
+        r.pos = pos; r.cls = W(VITSEG_T_CLS); r.lnw = lnw; r.lnb = lnb; r.H = H;
         r.rows = Mt; r.Mp = Mp; r.Np = s.Np; r.D = D; r.ln_rows = ln_rows; r.embed = embed ? 1 : 0;
         r.eps = cfg->layer_norm_eps;
         ProfScope ps(VITSEG_K_LAYERNORM, (double)Mt * D * 4 * (2 + splits) + (double)ln_rows * D * 4, st);
@@ -160,14 +163,14 @@ int forward_small(const vitseg_config* cfg, const Shape& s, const Layout& lay, c
     const bool dma_patch = (s.P == 8 || s.P == 16 || s.P == 32) && s.Kp % 32 == 0;
     if (!dma_patch) {
         GemmArgs g{};
-        g.A = x; g.W = W(VITSEG_T_PATCH_W); g.bias = W(VITSEG_T_PATCH_B); g.R = W(VITSEG_T_POS); g.C = X;
+        g.A = x; g.W = W(VITSEG_T_PATCH_W); g.bias = W(VITSEG_T_PATCH_B); g.R = pos; g.C = X;
         g.M = Mp; g.N = D; g.K = s.Kp; g.lda = 0; g.ldc = D;
         g.S = s.S; g.P = s.P; g.g = s.g; g.Np = s.Np; g.Cin = s.Cin; g.D = D;
         {
             ProfScope ps(VITSEG_K_GEMM_PATCH, 2.0 * g.M * g.N * g.K, st);
             if ((rc = launch_gemm_f32(g, A_PATCH, EPI_POS, st, 0))) return rc;
         }
-        if ((rc = launch_cls_rows(W(VITSEG_T_CLS), W(VITSEG_T_POS), X, batch, s.Np, D, st))) return rc;
+        if ((rc = launch_cls_rows(W(VITSEG_T_CLS), pos, X, batch, s.Np, D, st))) return rc;
         ProfScope ps(VITSEG_K_LAYERNORM, (double)Mt * D * 8, st);
         if ((rc = launch_layernorm(X, W(VITSEG_T_LN1_W, 0), W(VITSEG_T_LN1_B, 0), H, Mt, D, cfg->layer_norm_eps, h16, st))) return rc;
     } else {
@@ -314,20 +317,31 @@ int vitseg_forward_route(const vitseg_config* cfg, int batch, int precision) {
 }
 
 int vitseg_query_workspace(const vitseg_config* cfg, int batch, int precision, size_t* bytes) {
-    Shape s;
-    if (int rc = check_config(cfg, &s)) return rc;
+    return vitseg_query_workspace_at(cfg, cfg ? cfg->image_size : 0, batch, precision, bytes);
+}
+
+int vitseg_query_workspace_at(const vitseg_config* cfg, int image_size_in, int batch, int precision, size_t* bytes) {
+    Shape s, s0;
+    vitseg_config cin;
+    if (int rc = derive_input(cfg, image_size_in, &cin, &s, &s0)) return rc;
     VITSEG_CHECK_ARG(batch >= 1 && bytes, VITSEG_EINVAL, "batch %d / null out pointer", batch);
     VITSEG_CHECK_ARG(precision >= VITSEG_F32 && precision <= VITSEG_F32X3, VITSEG_EINVAL, "precision %d", precision);
-    *bytes = make_plan(s, batch, precision).total;
+    *bytes = make_plan(s, batch, precision, s.g != s0.g).total;
     return VITSEG_OK;
 }
 
 int vitseg_workspace_offset(const vitseg_config* cfg, int batch, int precision, int buffer, size_t* offset_bytes,
                             size_t* bytes) {
-    Shape s;
-    if (int rc = check_config(cfg, &s)) return rc;
+    return vitseg_workspace_offset_at(cfg, cfg ? cfg->image_size : 0, batch, precision, buffer, offset_bytes, bytes);
+}
+
+int vitseg_workspace_offset_at(const vitseg_config* cfg, int image_size_in, int batch, int precision, int buffer,
+                               size_t* offset_bytes, size_t* bytes) {
+    Shape s, s0;
+    vitseg_config cin;
+    if (int rc = derive_input(cfg, image_size_in, &cin, &s, &s0)) return rc;
     VITSEG_CHECK_ARG(batch >= 1, VITSEG_EINVAL, "batch %d", batch);
-    const Plan p = make_plan(s, batch, precision);
+    const Plan p = make_plan(s, batch, precision, s.g != s0.g);
     size_t o = 0, n = 0;
     switch (buffer) {
         case VITSEG_BUF_TOKENS: o = p.x; n = p.Mt * s.D * 4; break;
@@ -342,8 +356,18 @@ int vitseg_workspace_offset(const vitseg_config* cfg, int batch, int precision, 
 int vitseg_forward(const vitseg_config* cfg, const float* params, const void* params_bf16, const float* x, int batch,
                    int precision, float* logits, uint8_t* mask, void* workspace, size_t workspace_bytes,
                    void* stream_) {
-    Shape s;
-    if (int rc = check_config(cfg, &s)) return rc;
+    return vitseg_forward_at(cfg, cfg ? cfg->image_size : 0, params, params_bf16, x, batch, precision, logits, mask, workspace,
+                             workspace_bytes, stream_);
+}
+
+// s: the input's shape (activations, outputs); s0 / lay: the arena's.  With another grid the position table is resampled
+// into the workspace first and the embedding launches read it there instead of the arena's (the one pointer they take).
+int vitseg_forward_at(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16, const float* x,
+                      int batch, int precision, float* logits, uint8_t* mask, void* workspace, size_t workspace_bytes,
+                      void* stream_) {
+    Shape s, s0;
+    vitseg_config cin;
+    if (int rc = derive_input(cfg, image_size_in, &cin, &s, &s0)) return rc;
     VITSEG_CHECK_ARG(params && x && workspace && batch >= 1, VITSEG_EINVAL, "null pointer or batch < 1");
     VITSEG_CHECK_ARG(logits || mask, VITSEG_EINVAL, "both outputs are null");
     VITSEG_CHECK_ARG(precision >= VITSEG_F32 && precision <= VITSEG_F32X3, VITSEG_EINVAL, "precision %d", precision);
@@ -354,11 +378,11 @@ int vitseg_forward(const vitseg_config* cfg, const float* params, const void* pa
     // fp32 storage, GEMMs on the fp16 pipe with split operands; 2 = the weights come pre-split (params_bf16 slot)
     const int x3 = precision == VITSEG_F32X3 ? (params_bf16 ? 2 : 1) : 0;
     const bool lp = precision == VITSEG_BF16 || precision == VITSEG_F16, f16 = precision == VITSEG_F16;
-    const Plan p = make_plan(s, batch, precision);
+    const Plan p = make_plan(s, batch, precision, s.g != s0.g);
     VITSEG_CHECK_ARG(workspace_bytes >= p.total, VITSEG_EWORKSPACE, "workspace %zu < required %zu", workspace_bytes,
                      p.total);
     hipStream_t st = (hipStream_t)stream_;
-    const Layout lay = make_layout(s);
+    const Layout lay = make_layout(s0);
     auto W = [&](int t, int layer = 0) { return params + tensor_offset(lay, t, layer); };
     // weight operand of a GEMM: fp32 arena or its bf16 shadow (same element offsets)
     auto WG = [&](int t, int layer = 0) -> const void* {
@@ -367,7 +391,14 @@ int vitseg_forward(const vitseg_config* cfg, const float* params, const void* pa
         return lp ? (const void*)((const unsigned short*)params_bf16 + off) : (const void*)(params + off);
     };
     char* ws = (char*)workspace;
-    if (small_applies(cfg, batch, precision)) return forward_small(cfg, s, lay, p, params, params_bf16, precision, x, batch, logits, mask, ws, st);
+    const float* pos = W(VITSEG_T_POS);
+    if (s.g != s0.g) {
+        float* table = (float*)(ws + p.pos);
+        if (int rc = launch_pos_interp(pos, table, s0.g, s.g, s.D, st)) return rc;
+        pos = table;
+    }
+    if (small_applies(&cin, batch, precision))
+        return forward_small(cfg, s, lay, p, params, params_bf16, pos, precision, x, batch, logits, mask, ws, st);
     float* X = (float*)(ws + p.x);
     void* H = (void*)(ws + p.h);      // fp32 or bf16 by precision
     void* QKV = (void*)(ws + p.qkv);
@@ -381,7 +412,7 @@ int vitseg_forward(const vitseg_config* cfg, const float* params, const void* pa
     {
         GemmArgs g{};
         g.A = x; g.W = x3 == 2 ? WG(VITSEG_T_PATCH_W) : (const void*)W(VITSEG_T_PATCH_W);  // fp32 (or pre-split) weights
-        g.bias = W(VITSEG_T_PATCH_B); g.R = W(VITSEG_T_POS); g.C = X;
+        g.bias = W(VITSEG_T_PATCH_B); g.R = pos; g.C = X;
         g.M = Mp; g.N = D; g.K = s.Kp; g.lda = 0; g.ldc = D;
         g.S = s.S; g.P = s.P; g.g = s.g; g.Np = s.Np; g.Cin = s.Cin; g.D = D;
         {
@@ -390,7 +421,7 @@ int vitseg_forward(const vitseg_config* cfg, const float* params, const void* pa
             // products on the fp16 pipe) does this GEMM in 0.16 ms instead of 0.36 ms
             if ((rc = launch_gemm_f32(g, A_PATCH, EPI_POS, st, lp ? 1 : x3))) return rc;
         }
-        if ((rc = launch_cls_rows(W(VITSEG_T_CLS), W(VITSEG_T_POS), X, batch, s.Np, D, st))) return rc;
+        if ((rc = launch_cls_rows(W(VITSEG_T_CLS), pos, X, batch, s.Np, D, st))) return rc;
     }
     // ---- encoder layers (a4..a8) ----
     const double ln_bytes = 2.0 * Mt * D * 4;
@@ -853,6 +884,14 @@ int vitseg_op_attention_h16_small(const float* qkv, void* ctx16, int batch, int 
 
 int vitseg_op_attention_f32(const float* qkv, float* ctx, int batch, int num_patches, int num_heads, void* stream) {
     return launch_attention_f32(qkv, ctx, nullptr, batch, num_patches, num_heads, DropArgs{}, (hipStream_t)stream);
+}
+
+int vitseg_pos_interp(const float* pos_in, float* pos_out, int g0, int g1, int D, void* stream) {
+    return launch_pos_interp(pos_in, pos_out, g0, g1, D, (hipStream_t)stream);
+}
+
+int vitseg_pos_interp_bwd(const float* dpos_out, float* dpos_in, float* scratch, int g0, int g1, int D, void* stream) {
+    return launch_pos_interp_bwd(dpos_out, dpos_in, scratch, g0, g1, D, (hipStream_t)stream);
 }
 
 int vitseg_op_upsample_argmax(const float* lowres, float* logits, uint8_t* mask, int batch, int C, int g, int S,

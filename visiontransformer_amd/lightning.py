@@ -18,13 +18,19 @@ from .model import ViTSegmentationModel
 
 
 class LightningViTModel(nn.Module):
-    def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, **kw):
+    def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, *,
+                 interpolate_pos_encoding: bool = False, **kw):
+        """`interpolate_pos_encoding`: inputs of other (square, multiple-of-P) sizes than `image_size` run with the
+        position table resampled to their grid (ViTSegmentationModel.forward); targets are resized to the input's size."""
         super().__init__()
         self.model = ViTSegmentationModel(num_classes, patch_size, hidden_size, num_hidden_layers,
                                           num_attention_heads, **kw)
+        self.interpolate_pos_encoding = bool(interpolate_pos_encoding)
         self.logged = {}
 
     def forward(self, x):
+        if self.interpolate_pos_encoding:
+            return self.model(x, interpolate_pos_encoding=True)
         return self.model(x)
 
     def _resize_target(self, y, size, dtype=torch.long):
@@ -41,8 +47,12 @@ class LightningViTModel(nn.Module):
     def _loss(self, batch, grad_scale=None):
         x, y = batch
         S = self.model.cfg.image_size  # the reference hard-codes (224, 224) = its image_size (classes.py:278)
+        if self.interpolate_pos_encoding:
+            S = int(x.shape[-1])       # ... which is also its input size: with other input sizes, the input's
         # uint8 class indices: what the fused CE kernels read (a quarter of the int64 bytes); C <= 32 in training
         y = self._resize_target(y.to(x.device, non_blocking=True), size=(S, S), dtype=torch.uint8)
+        if self.interpolate_pos_encoding:
+            return self.model.ce_loss(x, y, grad_scale=grad_scale, interpolate_pos_encoding=True)
         return self.model.ce_loss(x, y, grad_scale=grad_scale)
 
     # `logged` holds DEVICE scalars: reading one (float(...)) is the only host sync, and only the caller decides when

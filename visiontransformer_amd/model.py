@@ -31,15 +31,16 @@ class _LogitsFn(torch.autograd.Function):
     """logits = forward(x) with libvitseg's backward: d loss / d logits -> d loss / d arena."""
 
     @staticmethod
-    def forward(ctx, arena, model, x):
-        ctx.model, ctx.x = model, x
+    def forward(ctx, arena, model, x, interp=False):
+        ctx.model, ctx.x, ctx.interp = model, x, interp
         ctx.drop = model._next_dropout()
-        return model._forward_train(x, want_logits=True, drop=ctx.drop)
+        return model._forward_train(x, want_logits=True, drop=ctx.drop, interp=interp)
 
     @staticmethod
     def backward(ctx, dlogits):
-        grads, _ = ctx.model._backward(ctx.x, grad_logits=dlogits.to(torch.float32).contiguous(), drop=ctx.drop)
-        return ctx.model._deliver_grad(grads), None, None
+        grads, _ = ctx.model._backward(ctx.x, grad_logits=dlogits.to(torch.float32).contiguous(), drop=ctx.drop,
+                                       interp=ctx.interp)
+        return ctx.model._deliver_grad(grads), None, None, None
 
 
 class _CELossFn(torch.autograd.Function):
@@ -50,10 +51,11 @@ class _CELossFn(torch.autograd.Function):
     steal (the model keeps a reference to its persistent buffer)."""
 
     @staticmethod
-    def forward(ctx, arena, model, x, target, grad_scale):
+    def forward(ctx, arena, model, x, target, grad_scale, interp=False):
         drop = model._next_dropout()
-        model._forward_train(x, want_logits=False, drop=drop)
-        grads, loss = model._backward(x, target=target, drop=drop, loss_scale=1.0 if grad_scale is None else grad_scale)
+        model._forward_train(x, want_logits=False, drop=drop, interp=interp)
+        grads, loss = model._backward(x, target=target, drop=drop, loss_scale=1.0 if grad_scale is None else grad_scale,
+                                      interp=interp)
         ctx.grads, ctx.model = grads, model
         ctx.prescaled = grad_scale is not None
         return loss
@@ -63,7 +65,7 @@ class _CELossFn(torch.autograd.Function):
         grads, ctx.grads = ctx.grads, None
         if not ctx.prescaled:
             grads.mul_(dloss)   # in place: the buffer is ours until it is delivered
-        return ctx.model._deliver_grad(grads), None, None, None, None
+        return ctx.model._deliver_grad(grads), None, None, None, None, None
 
 
 class ViTSegmentationModel(nn.Module):
@@ -163,14 +165,22 @@ class ViTSegmentationModel(nn.Module):
         return r
 
     # ------------------------------------------------------------------ launch plumbing
-    def _check_input(self, x: torch.Tensor):
+    def _check_input(self, x: torch.Tensor, interp: bool = False):
+        """`interp` (interpolate_pos_encoding): any square input whose side is a multiple of the patch size; the
+        position table is resampled to its grid (HF ViTEmbeddings.interpolate_pos_encoding)."""
         cfg = self.cfg
         if x.dim() != 4:
             raise ValueError(f"expected a [B, C, H, W] tensor, got shape {tuple(x.shape)}")
         if x.shape[1] != cfg.num_channels:  # modeling_vit.py:63-68
             raise ValueError("Make sure that the channel dimension of the pixel values match with the one set in the "
                              f"configuration. Expected {cfg.num_channels} but got {x.shape[1]}.")
-        if x.shape[2] != cfg.image_size or x.shape[3] != cfg.image_size:  # modeling_vit.py:152-156
+        if interp:
+            H, W, P = x.shape[2], x.shape[3], cfg.patch_size
+            if H != W:   # the reference's h = w = sqrt(num_patches) (classes.py:253-255) cannot reshape other grids
+                raise ValueError(f"interpolate_pos_encoding needs a square input, got {H}*{W}.")
+            if H < P or H % P:
+                raise ValueError(f"Input image size ({H}*{W}) is not a positive multiple of the patch size {P}.")
+        elif x.shape[2] != cfg.image_size or x.shape[3] != cfg.image_size:  # modeling_vit.py:152-156
             raise ValueError(f"Input image size ({x.shape[2]}*{x.shape[3]}) doesn't match model "
                              f"({cfg.image_size}*{cfg.image_size}).")
         if not x.is_cuda or x.device != self.arena.device:
@@ -178,16 +188,20 @@ class ViTSegmentationModel(nn.Module):
                                f"same HIP device (input on {x.device}, parameters on {self.arena.device}). "
                                "There is no CPU fallback.")
 
-    def forward_route(self, batch: int) -> str:
+    def forward_route(self, batch: int, image_size: Optional[int] = None) -> str:
         """"small" / "large": the kernel family an inference forward of this batch size runs on (results are bit-identical for
-        every batch size inside one route)."""
-        return _lib.forward_route(self.cfg, batch, self.precision)
+        every batch size inside one route); `image_size`: the input's side (interpolate_pos_encoding), default the model's."""
+        return _lib.forward_route(self.cfg, batch, self.precision, image_size)
 
-    def workspace(self, batch: int) -> torch.Tensor:
-        key = (batch, self.precision)
+    def _size_in(self, x: torch.Tensor, interp: bool) -> int:
+        return int(x.shape[-1]) if interp else self.cfg.image_size
+
+    def workspace(self, batch: int, image_size: Optional[int] = None) -> torch.Tensor:
+        S = self.cfg.image_size if image_size is None else int(image_size)
+        key = (batch, self.precision, S)
         ws = self._ws.get(key)
         if ws is None:
-            nbytes = _lib.query_workspace(self.cfg, batch, self.precision)
+            nbytes = _lib.query_workspace(self.cfg, batch, self.precision, S)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.arena.device)
             self._ws = {key: ws}  # keep one: a new batch size replaces the old workspace
         return ws
@@ -210,29 +224,36 @@ class ViTSegmentationModel(nn.Module):
             self._bf16_version = ver
         return self._arena_bf16
 
-    def _run(self, x: torch.Tensor, want_logits: bool, want_mask: bool, ws: Optional[torch.Tensor] = None):
-        self._check_input(x)
+    def _run(self, x: torch.Tensor, want_logits: bool, want_mask: bool, ws: Optional[torch.Tensor] = None,
+             interp: bool = False):
+        self._check_input(x, interp)
         x = x.to(torch.float32).contiguous()  # modeling_vit.py:369-371 casts to the weight dtype
-        B, S, Cc = x.shape[0], self.cfg.image_size, self.cfg.num_classes
+        B, S, Cc = x.shape[0], self._size_in(x, interp), self.cfg.num_classes
         logits = torch.empty((B, Cc, S, S), dtype=torch.float32, device=x.device) if want_logits else None
         mask = torch.empty((B, S, S), dtype=torch.uint8, device=x.device) if want_mask else None
         if ws is None:
-            ws = self.workspace(B)
+            ws = self.workspace(B, S)
         lp = self._bf16_arena()
+        cfg = C.byref(_lib.CConfig.from_config(self.cfg))
         with torch.cuda.device(x.device):
             stream = torch.cuda.current_stream().cuda_stream
-            rc = _lib.lib().vitseg_forward(C.byref(_lib.CConfig.from_config(self.cfg)), self.arena.data_ptr(),
-                                           _ptr(lp), x.data_ptr(), B, self.precision, _ptr(logits), _ptr(mask),
-                                           ws.data_ptr(), ws.numel(), stream)
+            if S == self.cfg.image_size:
+                rc = _lib.lib().vitseg_forward(cfg, self.arena.data_ptr(), _ptr(lp), x.data_ptr(), B, self.precision,
+                                               _ptr(logits), _ptr(mask), ws.data_ptr(), ws.numel(), stream)
+            else:
+                rc = _lib.at_symbol("vitseg_forward_at")(cfg, S, self.arena.data_ptr(), _ptr(lp), x.data_ptr(), B,
+                                                         self.precision, _ptr(logits), _ptr(mask), ws.data_ptr(),
+                                                         ws.numel(), stream)
         _lib.check(rc)
         return logits, mask
 
     # ------------------------------------------------------------------ training plumbing
-    def _train_workspace(self, batch: int) -> torch.Tensor:
-        key = ("train", batch)
+    def _train_workspace(self, batch: int, image_size: Optional[int] = None) -> torch.Tensor:
+        S = self.cfg.image_size if image_size is None else int(image_size)
+        key = ("train", batch, S)
         ws = self._ws.get(key)
         if ws is None:
-            ws = torch.empty(_lib.train_workspace(self.cfg, batch, self.precision), dtype=torch.uint8,
+            ws = torch.empty(_lib.train_workspace(self.cfg, batch, self.precision, S), dtype=torch.uint8,
                              device=self.arena.device)
             self._ws = {key: ws}
         return ws
@@ -245,18 +266,22 @@ class ViTSegmentationModel(nn.Module):
         rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
         return (self.dropout, (self.dropout_seed * 0x9E3779B97F4A7C15 + self._dropout_step * 0x100000001B3 + rank) & (2 ** 64 - 1))
 
-    def _forward_train(self, x: torch.Tensor, want_logits: bool, drop=(0.0, 0)):
-        self._check_input(x)
+    def _forward_train(self, x: torch.Tensor, want_logits: bool, drop=(0.0, 0), interp: bool = False):
+        self._check_input(x, interp)
         x = x.to(torch.float32).contiguous()
-        B, S = x.shape[0], self.cfg.image_size
-        ws = self._train_workspace(B)
+        B, S = x.shape[0], self._size_in(x, interp)
+        ws = self._train_workspace(B, S)
         logits = torch.empty((B, self.cfg.num_classes, S, S), dtype=torch.float32, device=x.device) \
             if want_logits else None
+        args = (self.arena.data_ptr(), _ptr(self._bf16_arena()), x.data_ptr(), B, self.precision, drop[0], drop[1],
+                _ptr(logits), ws.data_ptr(), ws.numel())
+        cfg = C.byref(_lib.CConfig.from_config(self.cfg))
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().vitseg_forward_train(
-                C.byref(_lib.CConfig.from_config(self.cfg)), self.arena.data_ptr(), _ptr(self._bf16_arena()),
-                x.data_ptr(), B, self.precision, drop[0], drop[1], _ptr(logits), ws.data_ptr(), ws.numel(),
-                torch.cuda.current_stream().cuda_stream))
+            stream = torch.cuda.current_stream().cuda_stream
+            if S == self.cfg.image_size:
+                _lib.check(_lib.lib().vitseg_forward_train(cfg, *args, stream))
+            else:
+                _lib.check(_lib.at_symbol("vitseg_forward_train_at")(cfg, S, *args, stream))
         return logits
 
     def no_sync(self):
@@ -333,21 +358,25 @@ class ViTSegmentationModel(nn.Module):
         return None
 
     def _backward(self, x: torch.Tensor, target: Optional[torch.Tensor] = None,
-                  grad_logits: Optional[torch.Tensor] = None, drop=(0.0, 0), loss_scale: float = 1.0):
+                  grad_logits: Optional[torch.Tensor] = None, drop=(0.0, 0), loss_scale: float = 1.0,
+                  interp: bool = False):
         x = x.to(torch.float32).contiguous()
-        B = x.shape[0]
-        ws = self._train_workspace(B)
+        B, S = x.shape[0], self._size_in(x, interp)
+        ws = self._train_workspace(B, S)
         grads = self._take_grad_buffer()
         loss = torch.zeros((), dtype=torch.float32, device=x.device) if target is not None else None
         overlap = self._overlap_active()
         with torch.cuda.device(x.device):
             reducer, events, handles, comm = self._bucket_state() if overlap else (None, None, None, None)
-            _lib.check(_lib.lib().vitseg_backward(
-                C.byref(_lib.CConfig.from_config(self.cfg)), self.arena.data_ptr(), _ptr(self._bf16_arena()),
-                x.data_ptr(), B, self.precision, drop[0], drop[1],
-                _ptr(target), int(target is not None and target.dtype == torch.uint8), _ptr(grad_logits),
-                grads.data_ptr(), _ptr(loss), float(loss_scale), handles, ws.data_ptr(), ws.numel(),
-                torch.cuda.current_stream().cuda_stream))
+            args = (self.arena.data_ptr(), _ptr(self._bf16_arena()), x.data_ptr(), B, self.precision, drop[0], drop[1],
+                    _ptr(target), int(target is not None and target.dtype == torch.uint8), _ptr(grad_logits),
+                    grads.data_ptr(), _ptr(loss), float(loss_scale), handles, ws.data_ptr(), ws.numel(),
+                    torch.cuda.current_stream().cuda_stream)
+            cfg = C.byref(_lib.CConfig.from_config(self.cfg))
+            if S == self.cfg.image_size:
+                _lib.check(_lib.lib().vitseg_backward(cfg, *args))
+            else:
+                _lib.check(_lib.at_symbol("vitseg_backward_at")(cfg, S, *args))
             if overlap:
                 # the whole backward is enqueued by now; each ring starts when its bucket's event fires and the
                 # compute stream only rejoins after the last one (what DDP's finalize does)
@@ -360,31 +389,40 @@ class ViTSegmentationModel(nn.Module):
         return torch.is_grad_enabled() and self.arena.requires_grad
 
     # ------------------------------------------------------------------ reference surface
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, interpolate_pos_encoding: bool = False) -> torch.Tensor:
         """logits [B, C, H, W] (model/CE/classes.py:246-262).  Differentiable w.r.t. the parameters when
         autograd is on (the backward runs in libvitseg, see vitseg_backward).  In train() mode dropout
-        (`self.dropout`, reference 0.1) is applied at the four HF sites with a counter-based generator."""
+        (`self.dropout`, reference 0.1) is applied at the four HF sites with a counter-based generator.
+        `interpolate_pos_encoding` (HF ViTModel.forward's keyword): any square input whose side is a multiple of the
+        patch size; the position table, which keeps the model's geometry, is resampled bicubically to the input's
+        patch grid on every call, and its gradient flows back to the table (vitseg_forward_at / vitseg_backward_at)."""
+        interp = bool(interpolate_pos_encoding)
         if self._needs_grad():
-            return _LogitsFn.apply(self.arena, self, x)
-        logits, _ = self._run(x, True, False)
+            return _LogitsFn.apply(self.arena, self, x, interp)
+        logits, _ = self._run(x, True, False, interp=interp)
         return logits
 
     @torch.no_grad()
-    def predict_mask(self, x: torch.Tensor, return_logits: bool = False):
+    def predict_mask(self, x: torch.Tensor, return_logits: bool = False, interpolate_pos_encoding: bool = False):
         """uint8 [B, H, W] = argmax_c sigmoid(logits) with first-index ties, i.e. the reference scripts'
-        `logits.sigmoid()` + `argmax` (model/CE/testViTModel.py:122-126), fused into the decoder tail."""
-        logits, mask = self._run(x, return_logits, True)
+        `logits.sigmoid()` + `argmax` (model/CE/testViTModel.py:122-126), fused into the decoder tail.
+        `interpolate_pos_encoding`: as in `forward`."""
+        logits, mask = self._run(x, return_logits, True, interp=bool(interpolate_pos_encoding))
         return (mask, logits) if return_logits else mask
 
     @torch.no_grad()
-    def predict_mask_graphed(self, x: torch.Tensor, return_logits: bool = False):
+    def predict_mask_graphed(self, x: torch.Tensor, return_logits: bool = False, interpolate_pos_encoding: bool = False):
         """`predict_mask` replayed from a captured hipGraph (one per batch size and output set): the ~110 kernel
         launches of a forward become one graph launch.  Measured (tools/latency_probe.py, ViT-B/16): no gain at batch
         1-8 -- 1.4 ms (bf16) to 5.9 ms (fp32) per forward at 224x224 is GPU time of under-filled GEMM launches, not host
         launch time -- so nothing uses it by default; it is there for smaller models / faster hosts, and bit-identical
         to the eager path.  Inputs are copied into the graph's static buffer; the returned tensors are the graph's
         static outputs and are overwritten by the next call with the same batch size (clone them to keep them).
-        Re-captured automatically when the parameters change."""
+        Re-captured automatically when the parameters change.  Native size only: another input size (interpolated
+        position embeddings) raises ValueError -- use `predict_mask(..., interpolate_pos_encoding=True)`."""
+        if interpolate_pos_encoding and tuple(x.shape[2:]) != (self.cfg.image_size, self.cfg.image_size):
+            raise ValueError(f"predict_mask_graphed runs at the model's image size {self.cfg.image_size} only, got "
+                             f"{tuple(x.shape[2:])}: use predict_mask(..., interpolate_pos_encoding=True)")
         self._check_input(x)
         key = (int(x.shape[0]), bool(return_logits))
         ver = (self.arena._version, self.arena.data_ptr())
@@ -438,32 +476,38 @@ class ViTSegmentationModel(nn.Module):
         m = self.predict_mask(tiles)
         return m.reshape(B, ty, tx, S, S).permute(0, 1, 3, 2, 4).reshape(B, H, W).contiguous()
 
-    def ce_loss(self, x: torch.Tensor, target: torch.Tensor, grad_scale: Optional[float] = None) -> torch.Tensor:
+    def ce_loss(self, x: torch.Tensor, target: torch.Tensor, grad_scale: Optional[float] = None,
+                interpolate_pos_encoding: bool = False) -> torch.Tensor:
         """`nn.CrossEntropyLoss()(self(x), target)` (model/CE/classes.py:268,280) as a device scalar, without
         materialising the [B, C, S, S] logits: forward to the low-res map, then the fused upsample+CE kernel.
         `target`: class indices [B, S, S], torch.long (reference) or torch.uint8, on the model's device.  Labels must lie
         in [0, C): `ignore_index` is not supported, and any other label (255, -100, C) makes the loss NaN.
         `grad_scale` (optional): the gradient `loss.backward()` deposits is grad_scale * d loss / d params, folded into
         the CE gradient inside the kernel (e.g. 1 / accumulate_grad_batches); call `.backward()` on the returned loss
-        itself then -- an upstream factor is ignored in this mode."""
-        S, B = self.cfg.image_size, x.shape[0]
+        itself then -- an upstream factor is ignored in this mode.  `interpolate_pos_encoding`: as in `forward`; the
+        target then has the input's size."""
+        interp = bool(interpolate_pos_encoding)
+        if interp:
+            self._check_input(x, True)
+        S, B = self._size_in(x, interp), x.shape[0]
         if tuple(target.shape) != (B, S, S) or target.dtype not in (torch.int64, torch.uint8):
             raise ValueError(f"target must be int64/uint8 [B, {S}, {S}], got {target.dtype} {tuple(target.shape)}")
         if self._needs_grad():
-            return _CELossFn.apply(self.arena, self, x, target.to(self.arena.device).contiguous(), grad_scale)
+            return _CELossFn.apply(self.arena, self, x, target.to(self.arena.device).contiguous(), grad_scale, interp)
         with torch.no_grad():
-            _, _ = self._run(x, False, True)  # fills the low-res logits (mask output is a by-product)
-            low = self.debug_buffer(B, _lib.BUF_LOWRES)
+            _, _ = self._run(x, False, True, interp=interp)  # fills the low-res logits (mask output is a by-product)
+            low = self.debug_buffer(B, _lib.BUF_LOWRES, S)
             target = target.to(self.arena.device).contiguous()
             scratch = torch.empty(_lib.lib().vitseg_ce_scratch_bytes(B, S), dtype=torch.uint8, device=low.device)
             loss = torch.empty((), dtype=torch.float32, device=low.device)
             _lib.check(_lib.lib().vitseg_ce_loss(low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8),
                                                  None, scratch.data_ptr(), loss.data_ptr(), B, self.cfg.num_classes,
-                                                 self.cfg.grid, S, torch.cuda.current_stream().cuda_stream))
+                                                 S // self.cfg.patch_size, S, torch.cuda.current_stream().cuda_stream))
         return loss
 
     @torch.no_grad()
-    def debug_buffer(self, batch: int, which: int) -> torch.Tensor:
-        """fp32 view of a workspace buffer defined after forward (parity tests)."""
-        off, n = _lib.workspace_offset(self.cfg, batch, self.precision, which)
-        return self.workspace(batch)[off:off + n].view(torch.float32)
+    def debug_buffer(self, batch: int, which: int, image_size: Optional[int] = None) -> torch.Tensor:
+        """fp32 view of a workspace buffer defined after forward (parity tests); `image_size`: the input's side of that
+        forward (interpolate_pos_encoding), default the model's."""
+        off, n = _lib.workspace_offset(self.cfg, batch, self.precision, which, image_size)
+        return self.workspace(batch, image_size)[off:off + n].view(torch.float32)

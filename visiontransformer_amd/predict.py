@@ -27,14 +27,17 @@ CONFIGURATIONS = {
 
 
 def load_model(model_id_or_config, num_classes: int, checkpoint: Optional[str] = None, *, image_size: int = 224,
-               precision: str = "fp32", device="cuda:0") -> LightningViTModel:
+               precision: str = "fp32", device="cuda:0", serve_size: Optional[int] = None) -> LightningViTModel:
     """Builds `LightningViTModel` for a reference configuration ID (or a (P, D, L, A) tuple) and loads a
-    Lightning checkpoint `{'state_dict': ...}` if given (testViTModel.py:109-119)."""
+    Lightning checkpoint `{'state_dict': ...}` if given (testViTModel.py:109-119).  `image_size` is the checkpoint's
+    (its position table); `serve_size` (default: the same) the side `predict` resizes images to -- when the two differ
+    the forward resamples the position table to the served grid (interpolate_pos_encoding)."""
     P, D, L, A = CONFIGURATIONS[model_id_or_config] if isinstance(model_id_or_config, int) else model_id_or_config
     model = LightningViTModel(num_classes, P, D, L, A, image_size=image_size, precision=precision, device=device)
     if checkpoint is not None:
         ck = torch.load(checkpoint, map_location="cpu")
         model.load_state_dict(ck["state_dict"] if "state_dict" in ck else ck)
+    model.serve_size = int(serve_size) if serve_size is not None else None
     return model.eval()
 
 
@@ -65,12 +68,16 @@ def preprocess(image, size: int, device="cuda:0") -> torch.Tensor:
 
 
 def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, index_to_color=None,
-            return_logits: bool = False):
+            return_logits: bool = False, serve_size: Optional[int] = None):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
-    `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S]."""
+    `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
+    one `load_model` was given, else the model's image size; another size than the model's runs with the position table
+    resampled to it (interpolate_pos_encoding)."""
     seg = model.model if isinstance(model, LightningViTModel) else model
-    x = preprocess(image, seg.cfg.image_size, seg.arena.device)
-    out = seg.predict_mask(x, return_logits=return_logits)
+    S = serve_size if serve_size is not None else getattr(model, "serve_size", None)
+    S = seg.cfg.image_size if S is None else int(S)
+    x = preprocess(image, S, seg.arena.device)
+    out = seg.predict_mask(x, return_logits=return_logits, interpolate_pos_encoding=S != seg.cfg.image_size)
     mask = (out[0] if return_logits else out)[0].cpu().numpy()
     res = [mask]
     if index_to_color is not None:

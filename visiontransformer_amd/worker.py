@@ -16,6 +16,9 @@ fed; a ViT-B/16 forward at batch 1 and at batch 8 cost nearly the same), then ea
 
     python -m visiontransformer_amd.worker --port 8001 --backend http://127.0.0.1:8000 \\
            --model 0:17:/ckpt/version_0.ckpt          # vision_model_id:num_classes[:checkpoint]
+
+`--model id:C:ckpt:config:224:512` serves a checkpoint trained at 224x224 at 512x512: images are resized to the sixth
+field and the forward resamples the position table to that grid (interpolate_pos_encoding).
 """
 from __future__ import annotations
 
@@ -110,22 +113,24 @@ class ModelSlot:
 
 
 def gpu_slot(model_id_or_config, num_classes: int, checkpoint: Optional[str] = None, *, image_size: int = 224,
-             precision: str = "fp32", device: str = "cuda:0") -> ModelSlot:
+             precision: str = "fp32", device: str = "cuda:0", serve_size: Optional[int] = None) -> ModelSlot:
     """ModelSlot running on libvitseg: device pre-processing of every image (sizes may differ per job), one batched
-    forward + fused sigmoid/argmax."""
+    forward + fused sigmoid/argmax.  `image_size`: the checkpoint's; `serve_size` (default the same): the side images are
+    resized to, with the position table resampled to its grid when the two differ."""
     import torch
     from .predict import load_model
     from .preprocess import Preprocessor
     model = load_model(model_id_or_config, num_classes, checkpoint, image_size=image_size, precision=precision,
-                       device=device)
-    seg, pre = model.model, Preprocessor(image_size, device)
+                       device=device, serve_size=serve_size)
+    S = image_size if serve_size is None else int(serve_size)
+    seg, pre = model.model, Preprocessor(S, device)
 
     def predict_batch(images):
-        x = torch.empty((len(images), 3, image_size, image_size), dtype=torch.float32, device=device)
+        x = torch.empty((len(images), 3, S, S), dtype=torch.float32, device=device)
         for i, a in enumerate(images):
             pre.images(torch.from_numpy(np.ascontiguousarray(a)), out=x[i:i + 1])
         with torch.no_grad():
-            m = seg.predict_mask(x)
+            m = seg.predict_mask(x, interpolate_pos_encoding=S != image_size)
         return list(m.cpu().numpy())
 
     slot = ModelSlot(predict_batch, num_classes)
@@ -256,6 +261,17 @@ class Worker:
         return ThreadingHTTPServer((host, port), self.handler())
 
 
+def parse_model_spec(spec: str) -> dict:
+    """`--model` value vision_model_id:num_classes[:checkpoint[:config_id[:image_size[:serve_size]]]] -> its fields
+    (image_size: the checkpoint's, default 224; serve_size: the side images are served at, default image_size)."""
+    parts = spec.split(":")
+    return dict(model_id=int(parts[0]), num_classes=int(parts[1]),
+                checkpoint=parts[2] if len(parts) > 2 and parts[2] else None,
+                config_id=int(parts[3]) if len(parts) > 3 and parts[3] else 0,
+                image_size=int(parts[4]) if len(parts) > 4 and parts[4] else 224,
+                serve_size=int(parts[5]) if len(parts) > 5 and parts[5] else None)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--host", default="127.0.0.1")
@@ -263,19 +279,16 @@ def main(argv=None):
     ap.add_argument("--backend", default=os.environ.get("BACKEND_URL", "http://127.0.0.1:8000"))
     ap.add_argument("--token", default=os.environ.get("ORCH_SHARED_TOKEN", "your_shared_secret_token"))
     ap.add_argument("--model", action="append", required=True,
-                    help="vision_model_id:num_classes[:checkpoint[:config_id[:image_size]]] (repeatable)")
+                    help="vision_model_id:num_classes[:checkpoint[:config_id[:image_size[:serve_size]]]] (repeatable)")
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--max-batch", type=int, default=16)
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     slots = {}
     for spec in a.model:
-        parts = spec.split(":")
-        mid, C = int(parts[0]), int(parts[1])
-        ck = parts[2] if len(parts) > 2 and parts[2] else None
-        cfg_id = int(parts[3]) if len(parts) > 3 else 0
-        size = int(parts[4]) if len(parts) > 4 else 224
-        slots[mid] = gpu_slot(cfg_id, C, ck, image_size=size, precision=a.precision)
+        m = parse_model_spec(spec)
+        slots[m["model_id"]] = gpu_slot(m["config_id"], m["num_classes"], m["checkpoint"], image_size=m["image_size"],
+                                        serve_size=m["serve_size"], precision=a.precision)
     srv = Worker(slots, a.backend, a.token, max_batch=a.max_batch).serve(a.host, a.port)
     log.info("listening on %s:%d/enqueue/ -> %s", a.host, a.port, a.backend)
     srv.serve_forever()
