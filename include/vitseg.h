@@ -54,7 +54,9 @@ typedef struct vitseg_config {
     int32_t num_layers;        /* L */
     int32_t num_heads;         /* A;  D / A must be 64 in this build */
     int32_t image_size;        /* S  (reference: 224) */
-    int32_t intermediate_size; /* I  (reference: 3072) */
+    int32_t intermediate_size; /* I  (reference: 3072; multiple of 4; a multiple of 64 for VITSEG_BF16 /
+                                * VITSEG_F16, whose GEMMs step K in 64-value slices: other values give VITSEG_ESHAPE
+                                * from vitseg_query_workspace, vitseg_train_workspace and every entry point) */
     int32_t num_channels;      /* 3 */
     float layer_norm_eps;      /* 1e-12, configuration_vit.py:58 */
 } vitseg_config;
@@ -291,7 +293,9 @@ int vitseg_ce_loss(const float* lowres, const void* target, int target_is_u8, fl
  * *loss) OR the gradient of an arbitrary loss w.r.t. the logits (fp32 [B, C, S, S]) and fills `grads`, an
  * arena-shaped fp32 buffer (same offsets as the parameters).  loss_scale multiplies the gradient of the fused CE loss
  * at its source (1 / accumulate_grad_batches in a gradient-accumulation loop, what Lightning applies to every micro-batch
- * loss); the value written to *loss is not scaled. */
+ * loss); the value written to *loss is not scaled.
+ * Training also needs num_classes <= 32 and hidden_size <= 1024 (the head and LayerNorm backward kernels); outside
+ * that, vitseg_train_workspace, vitseg_forward_train and vitseg_backward return VITSEG_ESHAPE before any launch. */
 int vitseg_train_workspace(const vitseg_config* cfg, int batch, int precision, size_t* bytes);
 int vitseg_forward_train(const vitseg_config* cfg, const float* params, const void* params_bf16, const float* x,
                          int batch, int precision, float dropout_p, uint64_t dropout_seed, float* logits,

@@ -7,7 +7,7 @@ import torch
 from guard import check, guarded, snapshot, unchanged
 from oracle import bf16_model as BM
 from oracle import vitseg_oracle as O
-from util import CASES, Golden
+from util import BF16_GRAD_COS, BF16_GRAD_REL, CASES, Golden, grad_check as _grad_check
 from visiontransformer_amd import _lib, synth
 from visiontransformer_amd.config import ViTSegConfig
 from visiontransformer_amd.lightning import LightningViTModel
@@ -15,12 +15,10 @@ from visiontransformer_amd.model import ViTSegmentationModel
 
 pytestmark = pytest.mark.gpu
 
-# bf16 gradient gates.  Shallow models (<= 2 layers): per-tensor relative L2 error / cosine against the fp32 or fp64
-# gradient of the same step, bf16 operands (2^-9) through 1-2 layers give <= 5.1e-2 / 0.9987.  At depth no constant is
-# used: the distance of the HIP gradients from the exact ones is compared, tensor by tensor, with the distance of the
+# bf16 gradient gates: BF16_GRAD_REL / BF16_GRAD_COS (tests/util.py) for shallow models (<= 2 layers).  At depth no constant
+# is used: the distance of the HIP gradients from the exact ones is compared, tensor by tensor, with the distance of the
 # ROUNDING MODEL of the same step (oracle/bf16_model.py: fp64 arithmetic, rounded to bf16 where the HIP path stores or
 # multiplies a bf16) from the exact ones -- see _check_against_rounding_model.
-BF16_GRAD_REL, BF16_GRAD_COS = 0.10, 0.997            # <= 2 layers
 MODEL_RATIO, MODEL_SLACK = 1.3, 0.02                  # HIP error <= MODEL_RATIO * model error + MODEL_SLACK, per tensor
 DEV = "cuda:0"
 
@@ -517,66 +515,6 @@ def _vitb_512_case(B, L=1, seed=71):
     x = torch.from_numpy(synth.make_images(cfg, B, seed=9))
     y = torch.from_numpy(synth.make_targets(cfg, B, seed=9, size=512))
     return cfg, sd, x, y
-
-
-def _relu_flip_tokens(stages, cfg, thr=2e-6, limit=16):
-    """Reference-layout token indices (CLS = 0) whose gradient one sign flip of a seg_head.0 ReLU can move: the head
-    applies ReLU to ~10^6 pre-activations; one that lies within fp32 rounding of zero in the fp64 oracle may take the other
-    branch on the GPU, which changes the gradient that flows into the 3x3 token neighbourhood of that unit.  Returns the
-    union of those neighbourhoods (a handful of units at most -- asserted)."""
-    z = stages["head_pre"].detach()
-    near = (z.abs() < thr).nonzero()
-    assert near.shape[0] <= limit, f"{near.shape[0]} head pre-activations within {thr} of zero"
-    g = cfg.grid
-    toks = set()
-    for _, _, y, x in near.tolist():
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                if 0 <= y + dy < g and 0 <= x + dx < g:
-                    toks.add(1 + (y + dy) * g + (x + dx))
-    return sorted(toks), int(near.shape[0])
-
-
-def _grad_check(cfg, arena_grad, leaf, precision, stages=None):
-    from visiontransformer_amd.params import arena_views
-    gv = arena_views(cfg, arena_grad)
-    rel_gate, cos_gate = BF16_GRAD_REL, BF16_GRAD_COS
-    worst, worst_cos, bad, worst_name = 0.0, 1.0, [], ""
-    num, den = 0.0, 0.0
-    exempt_rows, n_near = _relu_flip_tokens(stages, cfg) if stages is not None else ([], 0)
-    for k, r in leaf.items():
-        if r.grad is None or "pooler" in k:
-            continue
-        A, Bg = gv[k].cpu().double(), r.grad.double()
-        if precision == "fp32" and exempt_rows and k.endswith("position_embeddings"):
-            # the only tensor indexed by token: leave out exactly the token rows next to a ReLU unit whose fp64
-            # pre-activation is within fp32 rounding of zero (see _relu_flip_tokens); everything else is compared
-            keep = torch.ones(A.shape[1], dtype=torch.bool)
-            keep[exempt_rows] = False
-            A, Bg = A[:, keep], Bg[:, keep]
-        a, b = A.flatten(), Bg.flatten()
-        if b.norm() < 1e-7:
-            if a.norm() >= 1e-4:
-                bad.append((k, "zero-gradient tensor", float(a.norm())))
-            continue
-        rel = float((a - b).norm() / b.norm())
-        num, den = num + float((a - b).pow(2).sum()), den + float(b.pow(2).sum())
-        if rel > worst:
-            worst, worst_name = rel, k
-        if precision == "fp32":
-            if rel >= 2e-4:
-                bad.append((k, rel, float((a - b).abs().max() / b.abs().max())))
-        else:       # bf16 operands (2^-9 relative) through the layer
-            cos = float((a @ b) / (a.norm() * b.norm()))
-            worst_cos = min(worst_cos, cos)
-            if not (cos > cos_gate and rel < rel_gate):
-                bad.append((k, rel, cos))
-    whole = (num / max(den, 1e-300)) ** 0.5
-    print(f"gradient check ({precision}): worst relative L2 {worst:.3e} ({worst_name}), worst cosine {worst_cos:.5f}, "
-          f"whole gradient {whole:.3e}, "
-          f"{n_near} head units within fp32 rounding of zero ({len(exempt_rows)} position-embedding rows set aside)")
-    assert not bad, bad
-    return worst, whole
 
 
 def _check_against_rounding_model(tag, hip, exact, model):

@@ -187,8 +187,31 @@ def test_attention(B, Np, A):
     assert err < 2e-5, err  # fp32 exp2/softmax on O(1) values
 
 
-@pytest.mark.parametrize("B,C,g,S", [(2, 2, 14, 224), (1, 17, 14, 224), (1, 2, 32, 512), (1, 3, 28, 224), (1, 1, 14, 112)])
+UPSAMPLE_SHAPES = [(2, 2, 14, 224), (1, 17, 14, 224), (1, 2, 32, 512), (1, 3, 28, 224), (1, 1, 14, 112)]
+# the widest class counts: C = 150 at S = 512 stages more than 48 KiB of source rows (-> the global kernel by shape),
+# C = 255 at S = 224 about 42 KiB (the staged kernel near its limit)
+UPSAMPLE_MANY = [(1, 150, 32, 512), (2, 255, 14, 224)]
+
+
+@pytest.mark.parametrize("B,C,g,S", UPSAMPLE_SHAPES)
 def test_upsample_sigmoid_argmax_bit_exact(B, C, g, S):
+    _upsample_bit_exact(B, C, g, S)
+
+
+@pytest.mark.parametrize("B,C,g,S", UPSAMPLE_MANY)
+def test_upsample_many_classes_bit_exact(B, C, g, S):
+    _upsample_bit_exact(B, C, g, S)
+
+
+@pytest.mark.parametrize("B,C,g,S", UPSAMPLE_SHAPES + UPSAMPLE_MANY)
+def test_upsample_global_switch_bit_exact(B, C, g, S):
+    """Switch upsample_global: upsample_kernel<false> (source rows from global memory, no LDS staging, no two-class mask
+    kernel) at every shape, held to the same bits as ATen's order."""
+    with _lib.option("upsample_global", 1):
+        _upsample_bit_exact(B, C, g, S)
+
+
+def _upsample_bit_exact(B, C, g, S):
     z = _rand(B, C, g, g, seed=g + C, scale=2.0)
     if C >= 3:
         z[:, 1] += 18.0  # saturate two classes: sigmoid -> 1.0f for both, first index must win

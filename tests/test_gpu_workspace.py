@@ -70,17 +70,23 @@ def _forward(cfg, precision, x, arena, shadow, fill):
     return logits.clone(), mask.clone()
 
 
-# (C, P, D, L, A, S, I): the smallest grids (S = 2 P), 17 classes, patch 8
+# (C, P, D, L, A, S, I): the smallest grids (S = 2 P), 17 classes, patch 8; a 1 x 1 grid (g1_p16), the generic patch
+# gather (p12), 255 classes (c255) and I = 100 (the large route by I; fp32 formats only: the 16-bit ones need I % 64 == 0)
 INFER_CFGS = {
     "c2_p16_s32": (2, 16, 64, 1, 1, 32, 128),
     "c17_p8_s16": (17, 8, 128, 2, 2, 16, 256),
     "c3_p16_s48": (3, 16, 128, 1, 2, 48, 256),
+    "g1_p16": (3, 16, 128, 1, 2, 16, 256),
+    "p12": (3, 12, 128, 1, 2, 96, 256),
+    "c255": (255, 16, 64, 1, 1, 224, 256),
+    "i100": (2, 16, 128, 1, 2, 64, 100),
 }
+OLD_CFGS = ("c2_p16_s32", "c17_p8_s16", "c3_p16_s48")   # (these keep their fp32x3 / small ids, which skip)
+FORWARD_RUNS = [(n, p, r) for n in sorted(INFER_CFGS) for p in ("fp32", "bf16", "fp16", "fp32x3") for r in ("small", "large")
+                if (n in OLD_CFGS or (p, r) != ("fp32x3", "small")) and (n != "i100" or (p in ("fp32", "fp32x3") and r == "large"))]
 
 
-@pytest.mark.parametrize("route", ["small", "large"])
-@pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16", "fp32x3"])
-@pytest.mark.parametrize("name", sorted(INFER_CFGS))
+@pytest.mark.parametrize("name,precision,route", FORWARD_RUNS)
 def test_forward_guarded_and_poisoned(name, precision, route):
     if precision == "fp32x3" and route == "small":
         pytest.skip("fp32x3 has no small-batch route")
@@ -139,7 +145,12 @@ TRAIN_CFGS = {
     "c3_p16_s32": (3, 16, 64, 1, 1, 32, 128, 2),        # the smallest grid
     "c2_p32_s64_narrow": (2, 32, 64, 1, 1, 64, 128, 1),  # patch 32 with a narrow MLP: the patch-embedding slabs
     "c17_p8_s16": (17, 8, 128, 2, 2, 16, 256, 2),
+    "g1_p16": (3, 16, 128, 1, 2, 16, 256, 2),            # a 1 x 1 token grid
+    "p12": (3, 12, 128, 1, 2, 96, 256, 2),               # the generic patch gather / im2col
+    "i100": (2, 16, 128, 1, 2, 64, 100, 2),              # the large route by I (fp32 only: bf16 needs I % 64 == 0)
 }
+TRAIN_RUNS = [(n, p, r) for n in sorted(TRAIN_CFGS) for p, r in (("fp32", "small"), ("fp32", "large"), ("bf16", None))
+              if n != "i100" or (p, r) == ("fp32", "large")]
 
 
 def _train_case(cfg, precision, B, dropout):
@@ -175,8 +186,7 @@ def _train_case(cfg, precision, B, dropout):
 # The training step's route is the fp32 forward's (small_applies(cfg, batch, VITSEG_F32) in vitseg_forward_train and
 # vitseg_backward, the answer vitseg_forward_route gives for VITSEG_F32); the bf16 training step has one route.
 @pytest.mark.parametrize("dropout", [0.0, 0.1])
-@pytest.mark.parametrize("precision,route", [("fp32", "small"), ("fp32", "large"), ("bf16", None)])
-@pytest.mark.parametrize("name", sorted(TRAIN_CFGS))
+@pytest.mark.parametrize("name,precision,route", TRAIN_RUNS)
 def test_train_step_guarded_and_poisoned(name, precision, route, dropout):
     c = TRAIN_CFGS[name]
     cfg = ViTSegConfig(*c[:5], image_size=c[5], intermediate_size=c[6])

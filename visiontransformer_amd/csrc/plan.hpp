@@ -45,6 +45,25 @@ inline int check_config(const vitseg_config* c, Shape* s) {
     return VITSEG_OK;
 }
 
+// What the 16-bit precisions (VITSEG_BF16 / VITSEG_F16) need beyond check_config: their GEMMs step K in whole 64-value
+// slices (gemm.hip launch_gemm_bf16 / gemm_bf16_train), and fc2 reduces over K = intermediate_size.  Called by every
+// workspace query and entry point before anything is launched, so that a config is refused at query time rather than
+// part-way through a launch sequence.
+inline int check_precision(const Shape& s, int precision) {
+    if (precision == VITSEG_BF16 || precision == VITSEG_F16)
+        VITSEG_CHECK_ARG(s.I % 64 == 0, VITSEG_ESHAPE,
+                         "intermediate_size %d: the 16-bit precisions need a multiple of 64", s.I);
+    return VITSEG_OK;
+}
+
+// What training needs beyond check_precision: the CE / head backward kernels hold at most 32 classes, and the LayerNorm
+// backward kernels a row of at most 1024 values (backward.hip).
+inline int check_train(const Shape& s, int precision) {
+    VITSEG_CHECK_ARG(s.C <= 32, VITSEG_ESHAPE, "training supports at most 32 classes (got %d)", s.C);
+    VITSEG_CHECK_ARG(s.D <= 1024, VITSEG_ESHAPE, "training supports hidden_size <= 1024 (got %d)", s.D);
+    return check_precision(s, precision);
+}
+
 // An input of side image_size_in through the arena of cfg (Hugging Face's interpolate_pos_encoding): *s0 = the arena's
 // shape (its layout, its position table), *cin = cfg at the input's size, *s = the activations' shape.
 inline int derive_input(const vitseg_config* cfg, int image_size_in, vitseg_config* cin, Shape* s, Shape* s0) {

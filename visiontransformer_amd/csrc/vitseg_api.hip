@@ -250,6 +250,9 @@ bool small_applies(const vitseg_config* cfg, int batch, int precision) {
     // batch 16 of 197 tokens and at batch 4 of 785 (profiles/r05_h16_route_probe.txt)
     const long lim16 = opt(OPT_SMALL_MAX_ROWS) > 0 ? opt(OPT_SMALL_MAX_ROWS) : small_max_rows_16(s.N);   // (the option: probes of the limit)
     if (precision != VITSEG_F32 && !(s.I % 64 == 0 && attn_small_infer(s.Np) && rows < lim16)) return false;
+    // ... and K chunks of the split linears (o_proj: K = D, fc2: K = I) that are whole 64-value steps: gemm_f32s counts a 16-bit
+    // K in pairs and needs chunks of 32 pairs (D = 448 splits into 2 chunks of 224 values, D = 320 into 2 of 160)
+    if (precision != VITSEG_F32 && ((s.D / small_splits(s.D, s.D)) % 64 || (s.I / small_splits(s.D, s.I)) % 64)) return false;
     return true;
 }
 }  // namespace vitseg
@@ -326,6 +329,7 @@ int vitseg_query_workspace_at(const vitseg_config* cfg, int image_size_in, int b
     if (int rc = derive_input(cfg, image_size_in, &cin, &s, &s0)) return rc;
     VITSEG_CHECK_ARG(batch >= 1 && bytes, VITSEG_EINVAL, "batch %d / null out pointer", batch);
     VITSEG_CHECK_ARG(precision >= VITSEG_F32 && precision <= VITSEG_F32X3, VITSEG_EINVAL, "precision %d", precision);
+    if (int rc = check_precision(s, precision)) return rc;
     *bytes = make_plan(s, batch, precision, s.g != s0.g).total;
     return VITSEG_OK;
 }
@@ -371,6 +375,7 @@ int vitseg_forward_at(const vitseg_config* cfg, int image_size_in, const float* 
     VITSEG_CHECK_ARG(params && x && workspace && batch >= 1, VITSEG_EINVAL, "null pointer or batch < 1");
     VITSEG_CHECK_ARG(logits || mask, VITSEG_EINVAL, "both outputs are null");
     VITSEG_CHECK_ARG(precision >= VITSEG_F32 && precision <= VITSEG_F32X3, VITSEG_EINVAL, "precision %d", precision);
+    if (int rc = check_precision(s, precision)) return rc;
     VITSEG_CHECK_ARG(precision == VITSEG_F32 || precision == VITSEG_F32X3 || params_bf16, VITSEG_EINVAL,
                      "16-bit forward needs the 16-bit arena");
     VITSEG_CHECK_ARG(((uintptr_t)params | (uintptr_t)x | (uintptr_t)workspace | (uintptr_t)logits) % 16 == 0,
