@@ -3,7 +3,7 @@
 The ROUNDING MODEL of libvitseg's bf16 mixed-precision training step, in fp64: the arithmetic of
 `vitseg_oracle.py` (= the reference's model/CE training step, /root/reference/model/CE/classes.py:276-285 over
 transformers/models/vit/modeling_vit.py:164-286) with every value rounded to bf16 exactly where the HIP path
-(visiontransformer_amd/csrc/vitseg_train.hip forward_train_bf16 / backward_bf16) stores or multiplies a bf16:
+(visiontransformer_amd/csrc/forward.hip walk_large / vitseg_train.hip backward_bf16) stores or multiplies a bf16:
 
   forward   GEMM operands (LayerNorm outputs, the 16-bit shadow of the weights, q|k|v, the attention context,
             gelu(u)) are bf16; accumulation, bias, residual stream, LayerNorm statistics, softmax are wider (fp32 on

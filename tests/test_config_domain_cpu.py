@@ -3,6 +3,7 @@ accepts must be refused by `vitseg_query_workspace` / `vitseg_train_workspace` e
 training limit says so (include/vitseg.h), and accepted otherwise.  A query that says OK for a config
 the launches cannot run hands the caller a partial launch sequence later (16-bit GEMMs step K in 64-value slices: before
 the query checked it, I = 224 passed the bf16 query and failed at layer 0's fc2)."""
+import ctypes as C
 import random
 
 import pytest
@@ -106,3 +107,22 @@ def test_limit_edges():
     with pytest.raises(ValueError, match="hidden_size <= 1024"):
         _lib.train_workspace(cfg(A=17, I=4096), 1, _lib.BF16)
     assert _lib.query_workspace(cfg(C=255, A=32, I=8192), 1, _lib.BF16) > 0   # inference keeps the whole domain
+
+
+@pytest.mark.parametrize("precision", [_lib.F32, _lib.BF16])
+def test_backward_refuses_bad_loss_arguments_before_any_launch(precision):
+    """`vitseg_backward` needs exactly one of `target` (fused CE) and `grad_logits`, and `loss` with `target`.  Both
+    precisions refuse a violation with VITSEG_EINVAL before anything reaches the device, so fake non-null pointers and a
+    large enough workspace size exercise the checks here."""
+    cfg = ViTSegConfig(2, 16, 128, 1, 2, image_size=64, intermediate_size=256)
+    B = 1
+    ws_bytes = _lib.train_workspace(cfg, B, precision)
+    c = _lib.CConfig.from_config(cfg)
+    fake = C.c_void_p(1 << 20)
+    L = _lib.lib()
+    for target, grad_logits, loss in ((None, None, None), (fake, None, None)):
+        rc = L.vitseg_backward(C.byref(c), fake, fake, fake, B, precision, 0.0, 0, target, 0, grad_logits, fake, loss, 1.0,
+                               None, fake, ws_bytes, None)
+        assert rc == _lib.EINVAL, (rc, L.vitseg_last_error())
+        msg = L.vitseg_last_error().decode()
+        assert ("exactly one of target" in msg) if target is None else ("loss output pointer" in msg), msg

@@ -555,7 +555,7 @@ def _check_against_rounding_model(tag, hip, exact, model):
 def test_training_step_vitb_width_512(precision):
     """ViT-B width (D 768, 12 heads, I 3072), 512x512, batch 8 (M = 8200 token rows), one layer: the shapes at which
     the bf16 path takes the 256x256 / 256x128 tiles and the CLS rows of the QKV / dgrad GEMMs go through the split-K
-    side launch (vitseg_train.hip forward_train_bf16 / backward_bf16), against autograd on the oracle
+    side launch (forward.hip walk_large / vitseg_train.hip backward_bf16), against autograd on the oracle
     (model/CE/classes.py:276-285 restated by O.training_step)."""
     B = 8
     cfg, sd, x, y = _vitb_512_case(B)

@@ -123,11 +123,23 @@ __host__ __device__ __forceinline__ bool drop_keep(unsigned key, unsigned minor,
     return ((minor & 1u) ? (h >> 16) : (h & 0xffffu)) >= thresh;
 }
 struct DropArgs {
-    unsigned thresh;  // round(p * 65536); 0 = dropout off
+    unsigned thresh;  // round(p * 65536); 0 = dropout off (DropArgs{}): the kernels then read none of the other fields
     unsigned seed;
     unsigned stream;
     float scale;      // 1 / (1 - p)
 };
+// dropout with probability p (0 <= p < 1) on `stream`; p = 0: DropArgs{}
+inline DropArgs drop_args(float p, unsigned seed, unsigned stream) {
+    DropArgs d{};
+    if (p > 0.f) {
+        d.thresh = (unsigned)((double)p * 65536.0 + 0.5);
+        if (d.thresh == 0) d.thresh = 1;  // p below 2^-17 still drops something rather than switching dropout off
+        d.seed = seed;
+        d.stream = stream;
+        d.scale = 1.0f / (1.0f - p);
+    }
+    return d;
+}
 
 // Attention-probability keep bits as precomputed words (attention_dropmask.hip), patch queries x patch keys of one
 // (image, head) pair bh, Np a multiple of 128, nb = Np / 32:

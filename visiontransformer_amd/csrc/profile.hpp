@@ -1,6 +1,6 @@
 // Measurement hooks shared by the inference (vitseg_api.hip) and training (vitseg_train.hip) drivers: while enabled,
 // a ProfScope brackets the launches issued during its lifetime with a pair of hipEvents on the launch stream and
-// records the algorithmic work of those launches (see include/vitseg.h, vitseg_profile_*).
+// records the algorithmic work of those launches (see include/vitseg.h, vitseg_profile_*).  A negative kind records nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,7 +43,7 @@ struct ProfScope {
     hipStream_t st;
     bool active;
     ProfRec r;
-    ProfScope(int kind, double work, hipStream_t s) : st(s), active(profiler().on) {
+    ProfScope(int kind, double work, hipStream_t s) : st(s), active(kind >= 0 && profiler().on) {
         if (!active) return;
         Profiler& g = profiler();
         r.kind = kind;

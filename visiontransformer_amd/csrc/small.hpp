@@ -3,7 +3,7 @@
 // model/CE/datasetTestViTmodel.py:97-109,174-186) and the worker's single-image call (197 rows;
 // model/CE/testViTModel.py:92-126).  At these sizes the GEMMs of the large-batch path are a fraction of one round (or a
 // few ragged rounds) of its 256x128 / 128x128 tiles; the kernels declared here cut the same arithmetic differently
-// (gemm_f32s.hip, rows_small.hip, attention_small.hip) and vitseg_api.hip:forward_small strings them together.
+// (gemm_f32s.hip, rows_small.hip, attention_small.hip) and forward.hip:walk_small strings them together.
 // Where the boundary sits is a measurement (profiles/r05_ref_grid_threshold.txt): the route wins up to the largest
 // published configuration (12 548 rows: 0.74 of the fp32 peak against 0.72) and loses to the persistent kernel at the
 // headline's 32 800 rows (0.85).
@@ -113,7 +113,7 @@ int launch_headfin(const float* partial, size_t split_stride, const float* b0, c
 // lse (optional): [B, A, Np + 1] log2-domain log-sum-exp per query, saved for the backward; dr: dropout of the probabilities
 // ctx_fmt: ctx as 0 fp32, 1 bf16, 2 fp16 values (the 16-bit route: o_proj's operand)
 int launch_attention_small(const float* qkv, float* ctx, int B, int Np, int A, hipStream_t s, float* lse = nullptr,
-                           DropArgs dr = DropArgs{0, 0, 0, 1.f}, int ctx_fmt = 0);
+                           DropArgs dr = DropArgs{}, int ctx_fmt = 0);
 // its backward (attention_bwd_small.hip): dqkv = (dq | dk | dv) from dctx, the saved qkv / ctx / lse; ONE launch, the
 // blocks of the first half produce dk / dv (32 keys each, the four waves split the queries), those of the second dq
 // (32 queries each, the waves split the keys); delta = rowsum(dctx o ctx) is formed inside
@@ -125,7 +125,7 @@ int launch_attention_bwd_small(const float* qkv, const float* ctx, const float* 
 // br_dbias = that branch's bias gradient.  scratch: layernorm_bwd_scratch_floats(rows, D).
 int launch_layernorm_bwd_small(const float* x, const float* w, const float* g, size_t g_stride, int g_splits,
                                const float* dres_in, float* dres_out, float* dw, float* db, float* scratch, int rows, int D,
-                               float eps, hipStream_t s, float* br_out = nullptr, DropArgs br_drop = DropArgs{0, 0, 0, 1.f},
+                               float eps, hipStream_t s, float* br_out = nullptr, DropArgs br_drop = DropArgs{},
                                float* br_dbias = nullptr);
 // the sequence lengths attn_small_kernel takes in the forward of the route (by the SHAPE only: a row's bits must not depend on the
 // batch): every length but the whole-64-key-tile ones that fill 128-query blocks (512x512 at P = 16: 1025 tokens), which take

@@ -1,5 +1,5 @@
 // C ABI of libvitseg.so (include/vitseg.h): parameter-arena layout, workspace planning and
-// the forward orchestration of the ViT segmentation hot path
+// the inference entry points of the ViT segmentation hot path (their launches: forward.hip)
 // (ViTSegmentationModel.forward, /root/reference/model/CE/classes.py:246-262).
 #include <ctype.h>
 #include <stdarg.h>
@@ -13,8 +13,7 @@
 
 #include "kernels.hpp"
 #include "profile.hpp"
-#include "plan.hpp"
-#include "small.hpp"
+#include "forward.hpp"
 
 namespace vitseg {
 
@@ -106,126 +105,13 @@ Plan make_plan(const Shape& s, int B, int precision, bool pos_interp = false) {
         if (need > p.thin_floats) p.thin_floats = need;
     }
     if (small_rows) {   // K-chunk slabs of the small-batch route (small.hpp)
-        const size_t need[4] = {(size_t)small_splits(s.D, s.D) * p.Mt * s.D, (size_t)small_splits(s.D, s.I) * p.Mt * s.D,
-                                (size_t)small_splits(s.D, s.Kp) * p.Mt * s.D, (size_t)9 * p.Mp * MID};
-        for (size_t n : need)
-            if (n > p.thin_floats) p.thin_floats = n;
+        const size_t need = small_slab_floats(s, p.Mt, p.Mp, SMALL_INFER);
+        if (need > p.thin_floats) p.thin_floats = need;
     }
     p.thin = take(p.thin_floats * 4);
     if (pos_interp) p.pos = take((size_t)s.N * s.D * 4);
     p.total = off;
     return p;
-}
-
-// ---- the small-batch fp32 forward (small.hpp): fewer than SMALL_MAX_ROWS token rows ------------------------------
-// 7 launches per layer: QKV GEMM (+bias) | attention | o_proj chunks | chunk sum + bias + residual + LayerNorm |
-// fc1 GEMM (+bias, GELU) | fc2 chunks | chunk sum + bias + residual + the next LayerNorm.
-// precision VITSEG_BF16 / VITSEG_F16: the four linears of every block multiply 16-bit operands (weights from the 16-bit arena,
-// LayerNorm output / attention context / MLP hidden written in that format by their producers) on the wide MFMA of the same
-// kernels, the attention products too (q, k, P, v rounded in registers, fp32 softmax); the residual stream, q | k | v as stored,
-// the patch embedding and the head stay fp32.
-int forward_small(const vitseg_config* cfg, const Shape& s, const Layout& lay, const Plan& p, const float* params, const void* params_lp,
-                  const float* pos, int precision, const float* x, int batch, float* logits, uint8_t* mask, char* ws, hipStream_t st) {
-    auto W = [&](int t, int layer = 0) { return params + tensor_offset(lay, t, layer); };
-    const int h16 = precision == VITSEG_BF16 ? 1 : precision == VITSEG_F16 ? 2 : 0;
-    float* X = (float*)(ws + p.x);
-    float* H = (float*)(ws + p.h);
-    float* QKV = (float*)(ws + p.qkv);
-    float* U = (float*)(ws + p.u);
-    float* Z = (float*)(ws + p.z);
-    float* part = (float*)(ws + p.thin);
-    const int Mt = (int)p.Mt, Mp = (int)p.Mp, D = s.D;
-    const size_t dstride = (size_t)Mt * D;   // slab stride of the D-wide chunk sums
-    int rc;
-    auto linear = [&](const float* A, int M, int K, int lda, int wt, int bt, int layer, float* C, int N, int epi, int kind) {
-        SGemm g{};
-        g.A = A; g.W = W(wt, layer); g.bias = W(bt, layer); g.C = C;
-        if (h16) g.W = (const float*)((const unsigned short*)params_lp + tensor_offset(lay, wt, layer));   // (A is 16-bit too: its producer wrote it so)
-        g.h16 = h16;
-        g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = K; g.ldc = N;
-        g.splits = epi == SE_PARTIAL ? small_splits(N, K) : 1;
-        g.split_stride = dstride;
-        ProfScope ps(kind, 2.0 * M * N * K, st);
-        return launch_gemm_f32s(g, epi, SA_PLAIN, st);
-    };
-    auto rows = [&](int splits, const float* bias, const float* lnw, const float* lnb, int ln_rows, bool embed, int h_fmt) {
-        SRows r{};
-        r.h_fmt = h_fmt;
-        r.X = X; r.partial = part; r.split_stride = dstride; r.splits = splits; r.bias = bias;
-        r.pos = pos; r.cls = W(VITSEG_T_CLS); r.lnw = lnw; r.lnb = lnb; r.H = H;
-        r.rows = Mt; r.Mp = Mp; r.Np = s.Np; r.D = D; r.ln_rows = ln_rows; r.embed = embed ? 1 : 0;
-        r.eps = cfg->layer_norm_eps;
-        ProfScope ps(VITSEG_K_LAYERNORM, (double)Mt * D * 4 * (2 + splits) + (double)ln_rows * D * 4, st);
-        return launch_resln(r, st);
-    };
-    // ---- embeddings (a2 + a3): patch projection chunks, then bias + position embedding + CLS rows + LayerNorm 1 of layer 0
-    // (patch sizes the gathering DMA does not cover -- P = 4: 48 values per patch -- take the large-batch route's launches)
-    const bool dma_patch = (s.P == 8 || s.P == 16 || s.P == 32) && s.Kp % 32 == 0;
-    if (!dma_patch) {
-        GemmArgs g{};
-        g.A = x; g.W = W(VITSEG_T_PATCH_W); g.bias = W(VITSEG_T_PATCH_B); g.R = pos; g.C = X;
-        g.M = Mp; g.N = D; g.K = s.Kp; g.lda = 0; g.ldc = D;
-        g.S = s.S; g.P = s.P; g.g = s.g; g.Np = s.Np; g.Cin = s.Cin; g.D = D;
-        {
-            ProfScope ps(VITSEG_K_GEMM_PATCH, 2.0 * g.M * g.N * g.K, st);
-            if ((rc = launch_gemm_f32(g, A_PATCH, EPI_POS, st, 0))) return rc;
-        }
-        if ((rc = launch_cls_rows(W(VITSEG_T_CLS), pos, X, batch, s.Np, D, st))) return rc;
-        ProfScope ps(VITSEG_K_LAYERNORM, (double)Mt * D * 8, st);
-        if ((rc = launch_layernorm(X, W(VITSEG_T_LN1_W, 0), W(VITSEG_T_LN1_B, 0), H, Mt, D, cfg->layer_norm_eps, h16, st))) return rc;
-    } else {
-        SGemm g{};
-        g.A = x; g.W = W(VITSEG_T_PATCH_W); g.C = part;
-        g.M = Mp; g.N = D; g.K = s.Kp; g.lda = 0; g.ldw = s.Kp; g.ldc = D;
-        g.splits = small_splits(D, s.Kp); g.split_stride = dstride;
-        g.g = s.g; g.Np = s.Np; g.S = s.S; g.P = s.P; g.Cin = s.Cin;
-        {
-            ProfScope ps(VITSEG_K_GEMM_PATCH, 2.0 * g.M * g.N * g.K, st);
-            if ((rc = launch_gemm_f32s(g, SE_PARTIAL, SA_PATCH, st))) return rc;
-        }
-        if ((rc = rows(g.splits, W(VITSEG_T_PATCH_B), W(VITSEG_T_LN1_W, 0), W(VITSEG_T_LN1_B, 0), Mt, true, h16))) return rc;
-    }
-    for (int l = 0; l < s.L; ++l) {
-        if ((rc = linear(H, Mt, D, D, VITSEG_T_WQKV, VITSEG_T_BQKV, l, QKV, 3 * D, SE_BIAS, VITSEG_K_GEMM_BIAS))) return rc;
-        {
-            ProfScope ps(VITSEG_K_ATTENTION, 4.0 * batch * s.A * (double)s.N * s.N * 64, st);
-            // by the SHAPE only (a row's bits must not depend on the batch): patch counts that are whole 64-key tiles and long
-            // enough to fill 128-query blocks (512x512: 1024) take attention_f32's tail-free loop, every other length the
-            // key-split kernel (tools/attn_small_probe.py, profiles/r05_attn_small_probe.txt: 197 and 785 tokens 1.1-2.7x
-            // faster at every batch; 1025 tokens faster only at batch 1; 3137 tokens 1.4x faster at batch 1, 1.06x at 2,
-            // 0.92x at 4: the rows of such a forward end at batch 5)
-            // (the 16-bit form of the route exists for the key-split kernel's lengths only: small_applies)
-            rc = attn_small_infer(s.Np) ? launch_attention_small(QKV, H, batch, s.Np, s.A, st, nullptr, DropArgs{0, 0, 0, 1.f}, h16)
-                                        : launch_attention_f32(QKV, H, nullptr, batch, s.Np, s.A, DropArgs{}, st);
-            if (rc) return rc;
-        }
-        if ((rc = linear(H, Mt, D, D, VITSEG_T_WO, VITSEG_T_BO, l, part, D, SE_PARTIAL, VITSEG_K_GEMM_RESADD))) return rc;
-        if ((rc = rows(small_splits(D, D), W(VITSEG_T_BO, l), W(VITSEG_T_LN2_W, l), W(VITSEG_T_LN2_B, l), Mt, false, h16))) return rc;
-        if ((rc = linear(H, Mt, D, D, VITSEG_T_W1, VITSEG_T_B1, l, U, s.I, SE_GELU, VITSEG_K_GEMM_GELU))) return rc;
-        if ((rc = linear(U, Mt, s.I, s.I, VITSEG_T_W2, VITSEG_T_B2, l, part, D, SE_PARTIAL, VITSEG_K_GEMM_RESADD))) return rc;
-        const bool last = l + 1 == s.L;   // the final LayerNorm covers the patch rows only (CLS is dropped, classes.py:250)
-        if ((rc = rows(small_splits(D, s.I), W(VITSEG_T_B2, l), last ? W(VITSEG_T_LNF_W) : W(VITSEG_T_LN1_W, l + 1),
-                       last ? W(VITSEG_T_LNF_B) : W(VITSEG_T_LN1_B, l + 1), last ? Mp : Mt, false, last ? 0 : h16)))   // (the head reads fp32)
-            return rc;
-    }
-    // ---- seg_head (a10 + a11): the 3x3 conv as nine shifted GEMMs (one tap per chunk), then ReLU + the 1x1 conv
-    {
-        SGemm g{};
-        g.A = H; g.W = W(VITSEG_T_HEAD0_W); g.C = part;
-        g.M = Mp; g.N = MID; g.K = D; g.lda = D; g.ldw = 9 * D; g.ldc = MID;
-        g.splits = 9; g.split_stride = (size_t)Mp * MID;
-        g.g = s.g; g.Np = s.Np;
-        {
-            ProfScope ps(VITSEG_K_GEMM_CONV3, 2.0 * g.M * g.N * 9 * g.K, st);
-            if ((rc = launch_gemm_f32s(g, SE_PARTIAL, SA_CONV3, st))) return rc;
-        }
-        ProfScope ps(VITSEG_K_HEAD1X1, (double)Mp * MID * 4 * 9 + (double)batch * s.C * s.Np * 4, st);
-        if ((rc = launch_headfin(part, g.split_stride, W(VITSEG_T_HEAD0_B), W(VITSEG_T_HEAD2_W), W(VITSEG_T_HEAD2_B), Z, batch, s.Np, s.C, st)))
-            return rc;
-    }
-    const double px = (double)batch * s.S * s.S;
-    ProfScope ps(VITSEG_K_UPSAMPLE, (logits ? px * s.C * 4 : 0.0) + (mask ? px : 0.0) + (double)batch * s.C * s.Np * 4, st);
-    return launch_upsample(Z, logits, mask, batch, s.C, s.g, s.S, st);
 }
 
 }  // namespace
@@ -235,26 +121,6 @@ Profiler& profiler() {
     return p;
 }
 
-long small_max_rows() {
-    const long v = opt(OPT_SMALL_MAX_ROWS);
-    return v > 0 ? v : SMALL_MAX_ROWS;
-}
-
-bool small_applies(const vitseg_config* cfg, int batch, int precision) {
-    Shape s;
-    if (precision == VITSEG_F32X3 || opt(OPT_NO_SMALL) || check_config(cfg, &s)) return false;
-    const long rows = (long)batch * s.N;
-    if (!(rows < small_max_rows() && s.D % 64 == 0 && s.I % 32 == 0 && s.I > s.D && s.S % 4 == 0)) return false;
-    // 16-bit operands (inference): whole 64-value K steps per chunk, the sequence lengths of the key-split attention kernel (it
-    // writes the 16-bit context), and fewer rows than fp32 -- the large-batch 16-bit kernels (256 x 256 tiles) catch up at
-    // batch 16 of 197 tokens and at batch 4 of 785 (profiles/r05_h16_route_probe.txt)
-    const long lim16 = opt(OPT_SMALL_MAX_ROWS) > 0 ? opt(OPT_SMALL_MAX_ROWS) : small_max_rows_16(s.N);   // (the option: probes of the limit)
-    if (precision != VITSEG_F32 && !(s.I % 64 == 0 && attn_small_infer(s.Np) && rows < lim16)) return false;
-    // ... and K chunks of the split linears (o_proj: K = D, fc2: K = I) that are whole 64-value steps: gemm_f32s counts a 16-bit
-    // K in pairs and needs chunks of 32 pairs (D = 448 splits into 2 chunks of 224 values, D = 320 into 2 of 160)
-    if (precision != VITSEG_F32 && ((s.D / small_splits(s.D, s.D)) % 64 || (s.I / small_splits(s.D, s.I)) % 64)) return false;
-    return true;
-}
 }  // namespace vitseg
 
 using namespace vitseg;
@@ -380,136 +246,37 @@ int vitseg_forward_at(const vitseg_config* cfg, int image_size_in, const float* 
                      "16-bit forward needs the 16-bit arena");
     VITSEG_CHECK_ARG(((uintptr_t)params | (uintptr_t)x | (uintptr_t)workspace | (uintptr_t)logits) % 16 == 0,
                      VITSEG_EINVAL, "pointers must be 16-byte aligned");
-    // fp32 storage, GEMMs on the fp16 pipe with split operands; 2 = the weights come pre-split (params_bf16 slot)
-    const int x3 = precision == VITSEG_F32X3 ? (params_bf16 ? 2 : 1) : 0;
-    const bool lp = precision == VITSEG_BF16 || precision == VITSEG_F16, f16 = precision == VITSEG_F16;
     const Plan p = make_plan(s, batch, precision, s.g != s0.g);
     VITSEG_CHECK_ARG(workspace_bytes >= p.total, VITSEG_EWORKSPACE, "workspace %zu < required %zu", workspace_bytes,
                      p.total);
     hipStream_t st = (hipStream_t)stream_;
     const Layout lay = make_layout(s0);
-    auto W = [&](int t, int layer = 0) { return params + tensor_offset(lay, t, layer); };
-    // weight operand of a GEMM: fp32 arena or its bf16 shadow (same element offsets)
-    auto WG = [&](int t, int layer = 0) -> const void* {
-        const size_t off = tensor_offset(lay, t, layer);
-        if (x3 == 2) return (const void*)((const float*)params_bf16 + off);  // split arena: same float offsets
-        return lp ? (const void*)((const unsigned short*)params_bf16 + off) : (const void*)(params + off);
-    };
     char* ws = (char*)workspace;
-    const float* pos = W(VITSEG_T_POS);
+    const float* pos = params + tensor_offset(lay, VITSEG_T_POS, 0);
     if (s.g != s0.g) {
         float* table = (float*)(ws + p.pos);
         if (int rc = launch_pos_interp(pos, table, s0.g, s.g, s.D, st)) return rc;
         pos = table;
     }
-    if (small_applies(&cin, batch, precision))
-        return forward_small(cfg, s, lay, p, params, params_bf16, pos, precision, x, batch, logits, mask, ws, st);
+    // one set of activations for every layer: the residual stream X, the LayerNorm output / attention context H (fp32 or
+    // 16-bit by precision), q | k | v, the MLP hidden
     float* X = (float*)(ws + p.x);
-    void* H = (void*)(ws + p.h);      // fp32 or bf16 by precision
-    void* QKV = (void*)(ws + p.qkv);
-    void* U = (void*)(ws + p.u);
-    float* F = (float*)(ws + p.f);
-    float* Z = (float*)(ws + p.z);
-    const int Mt = (int)p.Mt, Mp = (int)p.Mp, D = s.D;
-    int rc;
-
-    // ---- embeddings (a2 + a3): patch GEMM gathers straight from the NCHW image ----
-    {
-        GemmArgs g{};
-        g.A = x; g.W = x3 == 2 ? WG(VITSEG_T_PATCH_W) : (const void*)W(VITSEG_T_PATCH_W);  // fp32 (or pre-split) weights
-        g.bias = W(VITSEG_T_PATCH_B); g.R = pos; g.C = X;
-        g.M = Mp; g.N = D; g.K = s.Kp; g.lda = 0; g.ldc = D;
-        g.S = s.S; g.P = s.P; g.g = s.g; g.Np = s.Np; g.Cin = s.Cin; g.D = D;
-        {
-            ProfScope ps(VITSEG_K_GEMM_PATCH, 2.0 * g.M * g.N * g.K, st);
-            // 16-bit modes: the image and the patch weights are fp32 either way; the split-operand kernel (fp32-grade
-            // products on the fp16 pipe) does this GEMM in 0.16 ms instead of 0.36 ms
-            if ((rc = launch_gemm_f32(g, A_PATCH, EPI_POS, st, lp ? 1 : x3))) return rc;
-        }
-        if ((rc = launch_cls_rows(W(VITSEG_T_CLS), pos, X, batch, s.Np, D, st))) return rc;
-    }
-    // ---- encoder layers (a4..a8) ----
-    const double ln_bytes = 2.0 * Mt * D * 4;
-    // when the patch rows are a whole number of row tiles, the trailing CLS rows of the linear layers go
-    // through the split-K side launch (bitwise batch-invariant: a CLS row takes that path at every batch size)
-    const int thin_rows = (p.Mp % 256 == 0 && batch <= THIN_MAX_ROWS) ? batch : 0;
-    auto gemm = [&](GemmArgs g, int epi, int kind) {
-        ProfScope ps(kind, 2.0 * g.M * g.N * g.K, st);
-        g.thin_rows = thin_rows;
-        g.thin_scratch = (float*)(ws + p.thin);
-        g.thin_capacity = p.thin_floats;
-        return lp ? launch_gemm_bf16(g, A_PLAIN, epi, st, f16) : launch_gemm_f32(g, A_PLAIN, epi, st, x3);
-    };
-    auto lnorm = [&](const float* w, const float* b, int rows) {
-        ProfScope ps(VITSEG_K_LAYERNORM, (double)rows * D * (lp ? 6 : 8), st);
-        return launch_layernorm(X, w, b, H, rows, D, cfg->layer_norm_eps, lp ? (f16 ? 2 : 1) : 0, st);
-    };
-    (void)ln_bytes;
-    for (int l = 0; l < s.L; ++l) {
-        if ((rc = lnorm(W(VITSEG_T_LN1_W, l), W(VITSEG_T_LN1_B, l), Mt))) return rc;
-        GemmArgs g{};
-        g.A = H; g.W = WG(VITSEG_T_WQKV, l); g.bias = W(VITSEG_T_BQKV, l); g.C = QKV;
-        g.M = Mt; g.N = 3 * D; g.K = D; g.lda = D; g.ldc = 3 * D;
-        if ((rc = gemm(g, EPI_BIAS, VITSEG_K_GEMM_BIAS))) return rc;
-        {
-            ProfScope ps(VITSEG_K_ATTENTION, 4.0 * batch * s.A * (double)s.N * s.N * 64, st);
-            rc = lp ? launch_attention_bf16(QKV, H, nullptr, batch, s.Np, s.A, DropArgs{}, st, f16)
-                    : launch_attention_f32((const float*)QKV, (float*)H, nullptr, batch, s.Np, s.A, DropArgs{}, st, x3 != 0);
-            if (rc) return rc;
-        }
-        g = GemmArgs{};
-        g.A = H; g.W = WG(VITSEG_T_WO, l); g.bias = W(VITSEG_T_BO, l); g.R = X; g.C = X;
-        g.M = Mt; g.N = D; g.K = D; g.lda = D; g.ldc = D;
-        if ((rc = gemm(g, EPI_RESADD, VITSEG_K_GEMM_RESADD))) return rc;
-        if ((rc = lnorm(W(VITSEG_T_LN2_W, l), W(VITSEG_T_LN2_B, l), Mt))) return rc;
-        g = GemmArgs{};
-        g.A = H; g.W = WG(VITSEG_T_W1, l); g.bias = W(VITSEG_T_B1, l); g.C = U;
-        g.M = Mt; g.N = s.I; g.K = D; g.lda = D; g.ldc = s.I;
-        if ((rc = gemm(g, EPI_GELU, VITSEG_K_GEMM_GELU))) return rc;
-        g = GemmArgs{};
-        g.A = U; g.W = WG(VITSEG_T_W2, l); g.bias = W(VITSEG_T_B2, l); g.R = X; g.C = X;
-        g.M = Mt; g.N = D; g.K = s.I; g.lda = s.I; g.ldc = D;
-        if ((rc = gemm(g, EPI_RESADD, VITSEG_K_GEMM_RESADD))) return rc;
-    }
-    // ---- final LayerNorm on the patch rows only (CLS is dropped, classes.py:250) ----
-    if ((rc = lnorm(W(VITSEG_T_LNF_W), W(VITSEG_T_LNF_B), Mp))) return rc;
-    // ---- seg_head (a10 + a11): 3x3 conv as implicit GEMM over the token-major map ----
-    {
-        GemmArgs g{};
-        g.A = H; g.W = WG(VITSEG_T_HEAD0_W); g.bias = W(VITSEG_T_HEAD0_B); g.C = F;
-        g.M = Mp; g.N = MID; g.K = 9 * D; g.lda = 0; g.ldc = MID;
-        g.g = s.g; g.Np = s.Np; g.D = D;
-        g.zeros = ws + p.zero;
-        if (lp) {
-            hipError_t e = hipMemsetAsync(ws + p.zero, 0, 256, st);
-            if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(zero page)");
-        }
-        {
-            ProfScope ps(VITSEG_K_GEMM_CONV3, 2.0 * g.M * g.N * g.K, st);
-            if (!lp && !x3 && D % 32 == 0 && opt(OPT_CONV_DMA) && (size_t)(Mp + 128) * D * 4 < 0x7fffffffull) {
-                // (switch conv_dma, off by default) fp32: the same fmaf chain per output (k = (ky, kx, d): bit-identical to the
-                // implicit GEMM) with the operands through the LDS-DMA ring of gemm_f32s -- taps outside the image are out-of-range
-                // offsets that read as zeros.  Measured at the headline size (profiles/r05_notes.md): 0.94 -> 0.85 ms per forward,
-                // but 1 794 MB of L2 misses per launch against 978 MB: nine taps x two 128-column tiles re-read the map through
-                // the Infinity Cache.  Not the default: more traffic for 0.2 % of the step.
-                SGemm c{};
-                c.A = (const float*)H; c.W = W(VITSEG_T_HEAD0_W); c.bias = W(VITSEG_T_HEAD0_B); c.C = (float*)F;
-                c.M = Mp; c.N = MID; c.K = D; c.lda = D; c.ldw = 9 * D; c.ldc = MID; c.splits = 1;
-                c.g = s.g; c.Np = s.Np;
-                rc = launch_gemm_f32s(c, SE_RELU, SA_CONV3_ALL, st);
-            } else {
-                rc = lp ? launch_gemm_bf16(g, A_CONV3, EPI_RELU, st, f16) : launch_gemm_f32(g, A_CONV3, EPI_RELU, st, x3);
-            }
-            if (rc) return rc;
-        }
-        ProfScope ps(VITSEG_K_HEAD1X1, (double)Mp * MID * 4 + (double)batch * s.C * s.Np * 4, st);
-        if ((rc = launch_head1x1(F, W(VITSEG_T_HEAD2_W), W(VITSEG_T_HEAD2_B), Z, batch, s.Np, s.C, st))) return rc;
-    }
-    // ---- bilinear upsample (+ sigmoid -> argmax) (a12 + a14) ----
-    const double px = (double)batch * s.S * s.S;
-    ProfScope ps(VITSEG_K_UPSAMPLE, (logits ? px * s.C * 4 : 0.0) + (mask ? px : 0.0) + (double)batch * s.C * s.Np * 4,
-                 st);
-    return launch_upsample(Z, logits, mask, batch, s.C, s.g, s.S, st);
+    void* H = ws + p.h;
+    const LayerIO io{X, H, ws + p.qkv, H, nullptr, X, H, nullptr, ws + p.u, X, nullptr};
+    Fwd f{};
+    f.s = s; f.lay = &lay; f.params = params; f.params_lp = params_bf16; f.pos = pos; f.x = x; f.batch = batch;
+    f.eps = cfg->layer_norm_eps; f.st = st;
+    f.h16 = precision == VITSEG_BF16 ? 1 : precision == VITSEG_F16 ? 2 : 0;
+    // fp32 storage, GEMMs on the fp16 pipe with split operands; 2 = the weights come pre-split (params_bf16 slot)
+    f.x3 = precision == VITSEG_F32X3 ? (params_bf16 ? 2 : 1) : 0;
+    f.layer = [&](int) { return io; };
+    f.hf = H; f.F = (float*)(ws + p.f); f.Z = (float*)(ws + p.z); f.zeros = ws + p.zero;
+    f.scratch = (float*)(ws + p.thin); f.scratch_floats = p.thin_floats;
+    f.logits = logits; f.mask = mask;
+    f.thin_rows = true; f.whole_split = true; f.attn_small = attn_small_infer; f.conv_dma = true;
+    f.prof = FwdProf{VITSEG_K_GEMM_PATCH, VITSEG_K_LAYERNORM, VITSEG_K_GEMM_BIAS, VITSEG_K_ATTENTION, VITSEG_K_GEMM_RESADD,
+                     VITSEG_K_GEMM_GELU, VITSEG_K_GEMM_RESADD, VITSEG_K_GEMM_CONV3, VITSEG_K_HEAD1X1, VITSEG_K_UPSAMPLE, false};
+    return small_applies(&cin, batch, precision) ? walk_small(f) : walk_large(f);
 }
 
 size_t vitseg_ce_scratch_bytes(int batch, int S) { return ce_partial_count(batch, S) * sizeof(double); }
@@ -576,13 +343,7 @@ int vitseg_op_linear_f32_ex(const float* A, const float* Wt, const float* bias, 
     GemmArgs g{};
     g.A = A; g.W = Wt; g.bias = bias; g.R = R; g.C = C; g.aux = aux;
     g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
-    if (dropout_p > 0.f && epilogue == EPI_RESADD) {
-        g.drop.thresh = (unsigned)((double)dropout_p * 65536.0 + 0.5);
-        if (g.drop.thresh == 0) g.drop.thresh = 1;
-        g.drop.seed = dropout_seed;
-        g.drop.stream = dropout_stream;
-        g.drop.scale = 1.0f / (1.0f - dropout_p);
-    }
+    if (epilogue == EPI_RESADD) g.drop = drop_args(dropout_p, dropout_seed, dropout_stream);
     return launch_gemm_f32(g, A_PLAIN, epilogue, (hipStream_t)stream);
 }
 
@@ -636,13 +397,7 @@ int vitseg_op_linear_h16_ex(const void* A, const void* Wt, const float* bias, co
         g.thin_scratch = scratch;
         g.thin_capacity = scratch_floats;
     }
-    if (dropout_p > 0.f) {
-        g.drop.thresh = (unsigned)((double)dropout_p * 65536.0 + 0.5);
-        if (g.drop.thresh == 0) g.drop.thresh = 1;
-        g.drop.seed = dropout_seed;
-        g.drop.stream = dropout_stream;
-        g.drop.scale = 1.0f / (1.0f - dropout_p);
-    }
+    g.drop = drop_args(dropout_p, dropout_seed, dropout_stream);
     VITSEG_CHECK_ARG(!colsum_out || (colsum_scratch && epilogue == EPI_DGELU && !f16), VITSEG_EINVAL,
                      "linear_h16_ex: column sums come with the bf16 dGELU epilogue and need scratch");
     g.colsum_out = colsum_out;
@@ -689,14 +444,7 @@ int vitseg_op_attention_bwd_f32_small(const float* qkv, const float* dctx, float
                                       uint32_t dropout_stream, void* stream) {
     VITSEG_CHECK_ARG(qkv && dctx && ctx_out && lse_out && dqkv, VITSEG_EINVAL, "attention_bwd_small: null pointer");
     VITSEG_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, VITSEG_EINVAL, "attention_bwd_small: dropout_p %f", dropout_p);
-    DropArgs d{0, 0, 0, 1.f};
-    if (dropout_p > 0.f) {
-        d.thresh = (unsigned)((double)dropout_p * 65536.0 + 0.5);
-        if (d.thresh == 0) d.thresh = 1;
-        d.seed = dropout_seed;
-        d.stream = dropout_stream;
-        d.scale = (float)(1.0 / (1.0 - (double)dropout_p));
-    }
+    const DropArgs d = drop_args(dropout_p, dropout_seed, dropout_stream);
     if (int rc = launch_attention_small(qkv, ctx_out, batch, num_patches, num_heads, (hipStream_t)stream, lse_out, d)) return rc;
     return launch_attention_bwd_small(qkv, ctx_out, dctx, lse_out, dqkv, batch, num_patches, num_heads, d, (hipStream_t)stream);
 }
@@ -717,14 +465,7 @@ int vitseg_op_attention_bwd_bf16(const void* qkv, const void* dctx, void* ctx_ou
                                  void* stream) {
     VITSEG_CHECK_ARG(qkv && dctx && ctx_out && lse_out && scratch && dqkv, VITSEG_EINVAL, "attention_bwd: null pointer");
     VITSEG_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, VITSEG_EINVAL, "attention_bwd: dropout_p %f", dropout_p);
-    DropArgs d{};
-    if (dropout_p > 0.f) {
-        d.thresh = (unsigned)((double)dropout_p * 65536.0 + 0.5);
-        if (d.thresh == 0) d.thresh = 1;
-        d.seed = dropout_seed;
-        d.stream = dropout_stream;
-        d.scale = 1.0f / (1.0f - dropout_p);
-    }
+    const DropArgs d = drop_args(dropout_p, dropout_seed, dropout_stream);
     const unsigned* mw = nullptr;
     if (dropmask_words) {
         VITSEG_CHECK_ARG(d.thresh && num_patches % 128 == 0, VITSEG_EINVAL,
@@ -751,14 +492,7 @@ int vitseg_op_layernorm_bwd_f32_small(const float* x, const float* w, const floa
                                       int D, float eps, float* br_out, float* br_dbias, float dropout_p, uint32_t dropout_seed,
                                       uint32_t dropout_stream, void* stream) {
     VITSEG_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, VITSEG_EINVAL, "layernorm_bwd_small: dropout_p %f", dropout_p);
-    DropArgs d{0, 0, 0, 1.f};
-    if (dropout_p > 0.f) {
-        d.thresh = (unsigned)((double)dropout_p * 65536.0 + 0.5);
-        if (d.thresh == 0) d.thresh = 1;
-        d.seed = dropout_seed;
-        d.stream = dropout_stream;
-        d.scale = 1.0f / (1.0f - dropout_p);
-    }
+    const DropArgs d = drop_args(dropout_p, dropout_seed, dropout_stream);
     return launch_layernorm_bwd_small(x, w, g, g_stride, g_splits, dres_in, dres_out, dw, db, scratch, rows, D, eps,
                                       (hipStream_t)stream, br_out, d, br_dbias);
 }
@@ -884,7 +618,7 @@ int vitseg_op_attention_f32_small(const float* qkv, float* ctx, int batch, int n
 int vitseg_op_attention_h16_small(const float* qkv, void* ctx16, int batch, int num_patches, int num_heads, int f16, void* stream) {
     VITSEG_CHECK_ARG(qkv && ctx16, VITSEG_EINVAL, "attention_h16_small: null pointer");
     return launch_attention_small(qkv, (float*)ctx16, batch, num_patches, num_heads, (hipStream_t)stream, nullptr,
-                                  DropArgs{0, 0, 0, 1.f}, f16 ? 2 : 1);
+                                  DropArgs{}, f16 ? 2 : 1);
 }
 
 int vitseg_op_attention_f32(const float* qkv, float* ctx, int batch, int num_patches, int num_heads, void* stream) {
