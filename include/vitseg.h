@@ -380,12 +380,14 @@ int vitseg_paed_binary_loss(const float* logits, const float* mask, const float*
 int vitseg_eval_counts(const uint8_t* pred, const uint8_t* gt, int n, int S, int gt_h, int gt_w, const int32_t* yidx,
                        const int32_t* xidx, int64_t* counts, void* stream);
 
-/* one Adam step over a flat fp32 buffer (torch.optim.Adam semantics, weight_decay 0, amsgrad off);
+/* one Adam step over a flat fp32 buffer (torch.optim.Adam semantics, weight_decay 0, amsgrad off: torch's L2 weight decay,
+ * g += weight_decay * p, is not implemented, and FusedAdam refuses a nonzero weight_decay);
  * step is 1-based; gradients are multiplied by grad_scale first (1/world for summed all-reduce). */
 int vitseg_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n_floats, float lr,
                      float beta1, float beta2, float eps, int step, float grad_scale, void* stream);
-/* the same with torch.optim.AdamW's decoupled weight decay (params *= 1 - lr * weight_decay in front of the update): what
- * PAEDTrainer.configure_optimizers builds (model/PAED/classes.py:536-548, AdamW(lr=1e-4), weight_decay 1e-2 by default) */
+/* the same with torch.optim.AdamW's decoupled weight decay (params *= 1 - lr * weight_decay in front of the update, not
+ * torch.optim.Adam's L2 form): what PAEDTrainer.configure_optimizers builds (model/PAED/classes.py:536-548,
+ * AdamW(lr=1e-4), weight_decay 1e-2 by default) */
 int vitseg_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n_floats, float lr,
                       float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
 

@@ -634,8 +634,9 @@ def test_training_step_vitb16_full_depth_512(p):
 
 
 def test_training_step_reproducible_at_the_training_size():
-    """BASELINE configs[2] size (ViT-B/16, 512 x 512, batch 64, bf16 mixed precision, dropout 0.1), where the fp64 oracle is
-    out of reach: a size-independent property instead -- the step has no atomics and every reduction a fixed order, so the
+    """BASELINE configs[2] size (ViT-B/16, 512 x 512, batch 64, bf16 mixed precision, dropout 0.1).  With dropout 0 the step is
+    compared with its decomposition into B = 2 steps in test_gpu_production_size.py; the dropout masks depend on an image's
+    index in the batch, so here a size-independent property -- the step has no atomics and every reduction a fixed order, so the
     same step (same parameters, batch, dropout seed and step counter) gives the same loss and the same gradient of all
     88.8 M parameters BIT FOR BIT; and a different dropout step changes them (the masks are really applied)."""
     B = 64

@@ -360,8 +360,9 @@ def _cls_split_k_body(precision):
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_batch_invariance_at_the_headline_size(precision):
-    """BASELINE configs[1] geometry (ViT-B/16, 512 x 512, batch 32), where the oracle would take minutes: a size-independent
-    property instead -- the logits and the mask of an image do not depend on what else is in the batch.  Images 5 .. of
+    """BASELINE configs[1] geometry (ViT-B/16, 512 x 512, batch 32), where the fp64 oracle of all 32 images would take minutes
+    (a sample of them is compared with it in test_gpu_production_size.py): a size-independent property here -- the logits
+    and the mask of an image do not depend on what else is in the batch.  Images 5 .. of
     a batch of 32 against the same images as a batch of their own: bit for bit in fp32 (persistent GEMMs, attention and
     the CLS side path all keep a row's summation order), to fp32-rounding level in bf16."""
     cfg = ViTSegConfig(2, 16, 768, 12, 12, image_size=512)
@@ -396,7 +397,8 @@ def test_batch_invariance_at_the_headline_size(precision):
 
 def test_seventeen_classes_at_the_headline_size():
     """The reference's real class count (17, model/PAED/classes.py:418) at the headline geometry (512 x 512, batch 32): the
-    decoder tail then writes 17.8 MB of logits per image.  Size-independent properties: (1) an image's logits and mask do not
+    decoder tail then writes 17.8 MB of logits per image (images 0 and 31 are compared with the fp64 oracle in
+    test_gpu_production_size.py).  Size-independent properties: (1) an image's logits and mask do not
     depend on the rest of the batch (bit for bit); (2) the full-resolution logits ARE the ATen-order bilinear upsample of the
     low-resolution map (torch.equal against the oracle's restatement); (3) the mask is the first-max argmax of ATen's fp32
     sigmoid of those logits on EVERY pixel."""

@@ -59,7 +59,10 @@ def _ce_bounds(up, lse, C, npx):
 
 @pytest.mark.parametrize("B,C,g,S,kind", [
     (2, 2, 14, 224, "randn"), (1, 17, 14, 224, "randn"), (2, 32, 32, 512, "randn"), (1, 1, 16, 64, "randn"),
-    (2, 5, 7, 28, "randn"), (2, 5, 7, 28, "big"), (2, 17, 14, 224, "big"), (2, 4, 7, 28, "ties")])
+    (2, 5, 7, 28, "randn"), (2, 5, 7, 28, "big"), (2, 17, 14, 224, "big"), (2, 4, 7, 28, "ties"),
+    # the training sizes: B * S * S / 256 = 65 536 and 32 768 partial sums, where ce_finish_kernel's four-chain loop runs
+    # (it needs more than 4 096; the largest case above makes 2 048)
+    (64, 2, 32, 512, "randn"), (32, 17, 32, 512, "randn")])
 def test_ce_loss_against_fp64(B, C, g, S, kind):
     gen = torch.Generator().manual_seed(B * 1000 + C * 10 + g)
     z = torch.randn(B, C, g, g, generator=gen).float() * 3.0

@@ -96,6 +96,27 @@ def test_forward_rejects_what_the_reference_rejects_and_never_falls_back_to_cpu(
         m(torch.zeros(1, 3, 224, 224))
 
 
+def test_fused_adam_refuses_weight_decay_it_does_not_implement():
+    """FusedAdam stands for torch.optim.Adam, whose weight_decay is L2 (g += wd * p); the kernel only has AdamW's decoupled
+    form, so a nonzero weight_decay is refused (constructor and added groups) and FusedAdamW is named.  FusedAdamW keeps the
+    decoupled decay, and the CE module still builds Adam(lr=1e-5) (model/CE/classes.py:296-297)."""
+    from visiontransformer_amd.lightning import LightningViTModel
+    from visiontransformer_amd.optim import FusedAdam, FusedAdamW
+    p = torch.nn.Parameter(torch.zeros(8))
+    with pytest.raises(ValueError, match="FusedAdamW"):
+        FusedAdam([p], lr=1e-3, weight_decay=1e-2)
+    opt = FusedAdam([p], lr=1e-3)
+    with pytest.raises(ValueError, match="FusedAdamW"):
+        opt.add_param_group({"params": [torch.nn.Parameter(torch.zeros(4))], "weight_decay": 0.1})
+    assert len(opt.param_groups) == 1
+    w = FusedAdamW([p], lr=1e-3, weight_decay=1e-2)
+    assert w.param_groups[0]["weight_decay"] == 1e-2 and isinstance(w, FusedAdam)
+    assert FusedAdamW([p]).param_groups[0]["weight_decay"] == 1e-2        # torch.optim.AdamW's default
+    lm = LightningViTModel(2, 16, 192, 1, 3)
+    o = lm.configure_optimizers()
+    assert type(o) is FusedAdam and o.param_groups[0]["lr"] == 1e-5 and o.param_groups[0]["weight_decay"] == 0.0
+
+
 def test_synth_is_deterministic():
     cfg = vit_tiny16()
     a = synth.make_images(cfg, 2, seed=0)

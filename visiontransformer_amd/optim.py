@@ -1,7 +1,9 @@
-"""Fused Adam over the flat parameter arena (one kernel launch per step).
+"""Fused Adam / AdamW over the flat parameter arena (one kernel launch per step).
 
-Same update as `torch.optim.Adam(params, lr)` with default betas/eps, weight_decay 0, amsgrad off --
-what `LightningViTModel.configure_optimizers` builds in the reference (model/CE/classes.py:296-297).
+`FusedAdam(params, lr)` is `torch.optim.Adam(params, lr)` with default betas/eps, weight_decay 0, amsgrad off --
+what `LightningViTModel.configure_optimizers` builds in the reference (model/CE/classes.py:296-297).  It refuses a
+nonzero weight_decay: torch.optim.Adam adds L2 decay to the gradient (g += wd * p), which the kernel does not do.
+`FusedAdamW` is `torch.optim.AdamW` (decoupled decay: p *= 1 - lr * wd in front of the update).
 """
 from __future__ import annotations
 
@@ -11,9 +13,22 @@ from . import _lib
 
 
 class FusedAdam(torch.optim.Optimizer):
+    _decoupled = False   # FusedAdamW: weight_decay is AdamW's decoupled decay
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        """`weight_decay` is DECOUPLED (torch.optim.AdamW's: p *= 1 - lr * weight_decay in front of the update); 0 = Adam."""
+        """`weight_decay` must be 0 (ValueError otherwise): torch.optim.Adam's L2 form is not implemented; use FusedAdamW
+        for decoupled decay."""
+        self._check_decay(weight_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _check_decay(self, weight_decay):
+        if weight_decay != 0 and not self._decoupled:
+            raise ValueError(f"FusedAdam(weight_decay={weight_decay}): torch.optim.Adam's L2 weight decay is not "
+                             f"implemented; use FusedAdamW for AdamW's decoupled decay")
+
+    def add_param_group(self, param_group):
+        self._check_decay(param_group.get("weight_decay", self.defaults["weight_decay"]))
+        super().add_param_group(param_group)
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0):
@@ -43,8 +58,10 @@ class FusedAdam(torch.optim.Optimizer):
 
 
 class FusedAdamW(FusedAdam):
-    """`torch.optim.AdamW(params, lr)` (default weight_decay 1e-2) over the flat arena in one launch per step: what
-    `PAEDTrainer.configure_optimizers` builds in the reference (model/PAED/classes.py:536-548)."""
+    """`torch.optim.AdamW(params, lr)` (default weight_decay 1e-2, decoupled: p *= 1 - lr * weight_decay in front of the
+    update) over the flat arena in one launch per step: what `PAEDTrainer.configure_optimizers` builds in the reference
+    (model/PAED/classes.py:536-548)."""
+    _decoupled = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
