@@ -13,9 +13,14 @@ its own shard of the global image stream (weak scaling, images are independent u
 data-path collective -- SURVEY.md section 8e); value = all ranks' images / max-over-ranks time.
 
 Rank 0 prints ONE JSON line with `roofline` (dominant kernel: hipEvent time measured inside the
-timed steps on the launch stream, algorithmic FLOPs per launch) and `cpu_baseline` (the oracle,
-a CPU port of the reference path, on a bounded sample on this box's host cores).  `--dump-outputs DIR` also writes
+timed steps on the launch stream, algorithmic FLOPs per launch).  `--dump-outputs DIR` also writes
 what the last timed step returned (logits, mask) as .npy files, for comparing two builds on the same inputs.
+
+A plain run sets up, warms up, times the steps and prints that line; nothing else.  `--full` adds, after the timed
+steps, whatever takes runs of its own: `cpu_baseline` (the oracle, a CPU port of the reference path, on a bounded
+sample on the host's cores) with its `parity` check, the other operand formats, the side configurations
+(training step, ViT-L/16, request path, the reference's grid), the N > 1 training path, the kernel groups of
+`--mode train`.  `--no-cpu-baseline` / `--no-side-configs` trim a `--full` run.
 """
 from __future__ import annotations
 
@@ -269,7 +274,7 @@ def bench_tiled(args, rank, world, dev, barrier):
 
 
 def side_l16_tiled_f16(dev, steps=5):
-    """BASELINE configs[4] at its per-GPU share inside the default line (rank 0, N = 1, outside the timed region):
+    """BASELINE configs[4] at its per-GPU share inside the default --full line (rank 0, N = 1, outside the timed region):
     ViT-L/16, 16 images of 1024x1024 as 64 tiles of 512x512, fp16, uint8 mask output.  Random-init weights from the
     constructor (a throughput figure; the full-depth parity of this model is tests/test_gpu_forward.py)."""
     B = 16
@@ -346,7 +351,7 @@ def bench_aux(args, rank, world, dev, barrier):
                          "frac": round(algo / (dev_ms * 1e-3) / 8e12, 4), "traffic": None,
                          "kernel": "resize_h_kernel + resize_v_tensor_kernel" if args.mode == "prep" else "eval_counts_kernel",
                          "device_ms_per_step": round(dev_ms, 4), "algorithmic_bytes_per_step": algo}}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             if args.mode == "prep":   # what the reference's DataLoader workers run per image: Pillow resize + /255
                 from PIL import Image
                 n, t1 = 0, time.perf_counter()
@@ -437,14 +442,14 @@ def bench_ref_grid(args, rank, world, dev, barrier):
                  "frac_of_peak": round(B * cfg.forward_flops_per_image() / t / 1e12 / peak, 4),
                  "launches_per_forward": model.graph_nodes(B, True), "graph_bit_identical": same,
                  "route": model.forward_route(B)}
-            if rank == 0 and not args.no_cpu_baseline and B == batches[0] and cpu_budget > 0:
+            if rank == 0 and args.full and not args.no_cpu_baseline and B == batches[0] and cpu_budget > 0:
                 t0 = time.perf_counter()
                 base, parity, _ = cpu_baseline(cfg, sd_np, images_np, logits, mask, seconds_budget=min(cpu_budget, 12.0),
                                                n_images=B)
                 cpu_budget -= time.perf_counter() - t0
                 e["cpu_baseline"], e["parity"] = base, parity
             entry[f"batch{B}"] = e
-        if cid == 0 and not args.no_side_configs:
+        if cid == 0 and args.full and not args.no_side_configs:
             # the reference's TRAINING regime (model/CE/trainCurrentViTmodel.py:57: batch 4, 224x224; classes.py:264-297): one
             # step = forward + CE + backward + Adam(lr=1e-5), dropout 0.1 -- informational (these launches are the large-batch
             # kernels; the small-batch route of section 3b is inference-only so far)
@@ -541,7 +546,7 @@ def bench_train(args, cfg, model, x, rank, world, dev, barrier):
     arena) + Adam(lr=1e-5): BASELINE configs[2]/[3] (--precision bf16 = mixed precision, --batch 64)."""
     B = args.batch
     y = torch.from_numpy(synth.make_targets(cfg, B, seed=0, first_image=rank * B, size=cfg.image_size)).to(dev)
-    PROF_STEPS = 3
+    PROF_STEPS = 3 if args.full else 0   # the kernel groups take steps of their own: --full only
     elapsed, prof, loss = run_train_steps(model, x, y, world, args.steps, args.warmup, PROF_STEPS, barrier)
     barrier()
     if world > 1:
@@ -552,12 +557,8 @@ def bench_train(args, cfg, model, x, rank, world, dev, barrier):
     if rank == 0:
         value = world * B * args.steps / elapsed
         flops_img = 3.0 * cfg.forward_flops_per_image()
-        dom = max(prof, key=lambda k: prof[k]["ms"])
-        d = prof[dom]
-        dom_tflops = d["work"] / (d["ms"] * 1e-3) / 1e12
-        names = KERNEL_NAMES.get("train_" + ("f32" if args.precision == "f32" else "bf16"), {})
         peak = PEAK_TFLOPS[args.precision]
-        print(json.dumps({
+        out = {
             "metric": "images/sec (512×512) ViT-B/16 seg, 1/2/4/8 MI355X + mask argmax match",
             "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -567,22 +568,28 @@ def bench_train(args, cfg, model, x, rank, world, dev, barrier):
                        "global_batch": B * world,
                        "parallelism": f"data-parallel x{world}, bucketed gradient all-reduce ({collective_name(world)}) "
                                       f"overlapped with the backward"},
-            # dominant kernel group of the step (largest summed device time): algorithmic FLOPs / hipEvent time on the
-            # launch stream; per-kernel times of the same command: profiles/rNN_bench_train_*_kernel_stats.csv
-            "roofline": {"bound": "mfma", "achieved": round(dom_tflops, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(dom_tflops / peak, 4), "traffic": None, "kernel": names.get(dom, dom),
-                         "launches": d["launches"], "avg_launch_ms": round(d["ms"] / max(d["launches"], 1), 4),
-                         "flops_per_launch": d["work"] / max(d["launches"], 1)},
-            "kernel_groups": kernel_groups(prof, PROF_STEPS, peak),
             "whole_model": {"flops_per_image": flops_img,
                             "achieved_tflops_per_gpu": round(value / world * flops_img / 1e12, 2),
                             "frac_of_peak": round(value / world * flops_img / 1e12 / peak, 4)},
-            "final_loss": float(loss.detach())}), flush=True)
+            "final_loss": float(loss.detach())}
+        if PROF_STEPS:
+            # dominant kernel group of the step (largest summed device time): algorithmic FLOPs / hipEvent time on the
+            # launch stream; per-kernel times of the same command: profiles/rNN_bench_train_*_kernel_stats.csv
+            dom = max(prof, key=lambda k: prof[k]["ms"])
+            d = prof[dom]
+            dom_tflops = d["work"] / (d["ms"] * 1e-3) / 1e12
+            names = KERNEL_NAMES.get("train_" + ("f32" if args.precision == "f32" else "bf16"), {})
+            out["roofline"] = {"bound": "mfma", "achieved": round(dom_tflops, 2), "peak": peak, "unit": "TFLOP/s",
+                               "frac": round(dom_tflops / peak, 4), "traffic": None, "kernel": names.get(dom, dom),
+                               "launches": d["launches"], "avg_launch_ms": round(d["ms"] / max(d["launches"], 1), 4),
+                               "flops_per_launch": d["work"] / max(d["launches"], 1)}
+            out["kernel_groups"] = kernel_groups(prof, PROF_STEPS, peak)
+        print(json.dumps(out), flush=True)
     barrier()
 
 
 def side_train_bf16(cfg, sd_np, x32, dev, steps=5):
-    """BASELINE configs[2] inside the default line (rank 0, N = 1, outside the timed region): ViT-B/16 training step,
+    """BASELINE configs[2] inside the default --full line (rank 0, N = 1, outside the timed region): ViT-B/16 training step,
     batch 64 x 512x512, bf16 operands / fp32 master weights + Adam, the reference's dropout 0.1."""
     B = 64
     model = ViTSegmentationModel(cfg.num_classes, cfg.patch_size, cfg.hidden_size, cfg.num_hidden_layers,
@@ -641,7 +648,7 @@ def side_train_dist(cfg, sd_np, rank, world, dev, barrier, batch=64, steps=4):
 
 
 def side_ref_grid(dev, reps=10):
-    """The reference's own published regime inside the default line (rank 0, N = 1, outside the timed region; the full table with
+    """The reference's own published regime inside the default --full line (rank 0, N = 1, outside the timed region; the full table with
     the hipGraph column, the oracle check and the CPU baseline per configuration is `--workload ref_grid`): every configuration of
     predict.CONFIGURATIONS at batch 4 x 224x224, 17 classes, fp32 forward -> logits + mask; ViT-B/16 also at batch 1 (the worker's
     call) and its training step at the reference's batch (model/CE/trainCurrentViTmodel.py:57)."""
@@ -836,10 +843,15 @@ def main():
     ap.add_argument("--workload", default="b16_512", choices=["b16_512", "l16_1024_tiled", "l16_1024_native", "ref_grid"],
                     help="b16_512 = BASELINE configs[1] (default, the headline metric); l16_1024_tiled = configs[4]; "
                          "l16_1024_native = the same images as one 4097-token sequence each")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: CPU baseline and oracle "
+                         "parity, the other operand formats, the side configurations, the N > 1 training path, the "
+                         "kernel groups of --mode train (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline (in the default line also without the runs beside it)")
     ap.add_argument("--no-side-configs", action="store_true",
-                    help="skip the configs[2] / configs[4] side runs the default fp32 line appends (train_bf16_path, "
-                         "l16_1024_tiled_f16_path)")
+                    help="--full without the configs[2] / configs[4] side runs of the default fp32 line (train_bf16_path, "
+                         "l16_1024_tiled_f16_path, ...)")
     ap.add_argument("--dropout", type=float, default=0.1, help="train mode: dropout probability (reference 0.1)")
     ap.add_argument("--dist-train-batch", type=int, default=64,
                     help="N > 1: images per rank of the data-parallel training step appended to the line (train_bf16_path)")
@@ -936,7 +948,7 @@ def main():
         dist.all_gather(parts, mine)
         split_check = {"ranks_seen": dist.get_world_size(), "images_per_rank": B,
                        "mask_checksum_per_rank": [int(p[0]) for p in parts], "mask_pixels_per_rank": [int(p[1]) for p in parts]}
-        if args.precision == "f32" and not args.no_side_configs:   # the path the north_star shards with a collective
+        if args.precision == "f32" and args.full and not args.no_side_configs:   # the path the north_star shards with a collective
             logits_keep = logits
             dist_train = side_train_dist(cfg, sd_np, rank, world, dev, barrier, batch=args.dist_train_batch)
             logits = logits_keep
@@ -985,7 +997,7 @@ def main():
             out["inference_split"] = split_check
         if dist_train is not None:
             out["train_bf16_path"] = dist_train
-        extras = not args.no_cpu_baseline and world == 1   # CPU baseline / side paths: N = 1 only (spec), rank 0
+        extras = args.full and not args.no_cpu_baseline and world == 1   # CPU baseline / side paths: N = 1 only (spec), rank 0
         if args.precision == "f32" and extras:
             # informational (outside the timed region, rank 0 only): the same step on the other operand formats.
             # f32x3 = fp32 storage, GEMM operands split into half pairs, 3 fp16 MFMAs per product (fp32-grade results);

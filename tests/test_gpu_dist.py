@@ -18,7 +18,7 @@ def test_bench_two_ranks_on_one_gpu_exercises_split_and_gradient_exchange():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "4", "--dist-train-batch", "2", "--no-cpu-baseline"],
+                        "--batch", "4", "--dist-train-batch", "2", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

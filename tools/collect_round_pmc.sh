@@ -5,4 +5,4 @@
 set -e
 bash tools/collect_pmc.sh bench_f32 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --precision f32
 bash tools/collect_pmc.sh bench_bf16 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --precision bf16
-bash tools/collect_pmc.sh train_bf16 python3 bench.py --mode train --precision bf16 --batch 64 --steps 1 --warmup 1
+bash tools/collect_pmc.sh train_bf16 python3 bench.py --mode train --precision bf16 --batch 64 --steps 1 --warmup 1 --full
