@@ -380,6 +380,27 @@ int vitseg_paed_binary_loss(const float* logits, const float* mask, const float*
 int vitseg_eval_counts(const uint8_t* pred, const uint8_t* gt, int n, int S, int gt_h, int gt_w, const int32_t* yidx,
                        const int32_t* xidx, int64_t* counts, void* stream);
 
+/* ---- connected regions and their boxes (replaces get_bounding_boxes = scipy.ndimage.label + np.argwhere per label, called
+ *      for every class present but 0: testViTModel.py:34-42,171-185, datasetTestViTmodel.py:27,315-318,
+ *      model/PAED/ViTscriptTest.py:27,318-321) ----
+ * A region is a maximal set of equal pixels of one image that is connected: connectivity 4 (the cross, scipy's default
+ * structure) or 8 (the full 3x3).  Pixels equal to `background` (0..255; -1 = none) form no region.
+ * mask uint8 [n, H, W] (any H, W >= 1, H * W < 2^31);
+ * counts int32 [n]: regions per image (the true total, also when > max_regions);
+ * regions int32 [n, max_regions, 8]: class, y_min, x_min, y_max, x_max, area, first, 0 -- box inclusive, first = raster
+ *   index y * W + x of the region's first pixel; the first max_regions of each image in (class, first) order, which is
+ *   the order of the reference's loop (np.unique classes, then scipy's label numbering); rows past the count are zero;
+ *   16-byte aligned; may be NULL when max_regions == 0;
+ * labels (optional) int32 [n, H, W]: region index in its image's list (full index, also past max_regions), -1 = background
+ *   (scipy's label k of mask == c is offset_c + k - 1).
+ * scratch: vitseg_regions_scratch_bytes(n, H, W) device bytes (about 24 bytes per pixel; every word read is written
+ * within the call).  Results are integers from order-independent operations: the same bits on every call.
+ * VITSEG_EINVAL: null pointer, connectivity not 4 / 8, background outside -1..255; VITSEG_ESHAPE: non-positive sizes,
+ * H * W >= 2^31 or n > 65535; VITSEG_EWORKSPACE: scratch smaller than vitseg_regions_scratch_bytes (0 for a bad shape). */
+size_t vitseg_regions_scratch_bytes(int n, int H, int W);
+int vitseg_regions(const uint8_t* mask, int n, int H, int W, int connectivity, int background, int32_t* counts,
+                   int32_t* regions, int max_regions, int32_t* labels, void* scratch, size_t scratch_bytes, void* stream);
+
 /* one Adam step over a flat fp32 buffer (torch.optim.Adam semantics, weight_decay 0, amsgrad off: torch's L2 weight decay,
  * g += weight_decay * p, is not implemented, and FusedAdam refuses a nonzero weight_decay);
  * step is 1-based; gradients are multiplied by grad_scale first (1/world for summed all-reduce). */

@@ -3,6 +3,7 @@
 
     python model/CE/testViTModel.py IMAGE [--model-id 0] [--num-classes 17] [--checkpoint x.ckpt]
                                           [--image-size 224] [--precision fp32|bf16] [--out mask.png]
+                                          [--boxes boxes.json]
 
 Without --checkpoint the weights are random (the reference's checkpoints are private)."""
 import argparse
@@ -22,9 +23,17 @@ def main():
     ap.add_argument("--image-size", type=int, default=224)
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--out")
+    ap.add_argument("--boxes", help="write the predicted regions' boxes, {class: [[y_min, x_min, y_max, x_max], ...]} for "
+                                    "every class present but 0 (the reference's boxes panel), to this JSON file")
     a = ap.parse_args()
     model = load_model(a.model_id, a.num_classes, a.checkpoint, image_size=a.image_size, precision=a.precision)
-    mask = predict(a.image, model)
+    if a.boxes:
+        import json
+        mask, boxes = predict(a.image, model, return_boxes=True)
+        with open(a.boxes, "w") as f:
+            json.dump({str(c): [list(b) for b in bs] for c, bs in boxes.items()}, f)
+    else:
+        mask = predict(a.image, model)
     print("classes present:", np.unique(mask).tolist(), "mask shape:", mask.shape)
     if a.out:
         from PIL import Image

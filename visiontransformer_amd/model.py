@@ -411,6 +411,18 @@ class ViTSegmentationModel(nn.Module):
         return (mask, logits) if return_logits else mask
 
     @torch.no_grad()
+    def predict_regions(self, x: torch.Tensor, *, background: int = 0, connectivity: int = 4, return_mask: bool = False,
+                        interpolate_pos_encoding: bool = False):
+        """The regions of each image's predicted mask: a list of int32 [k, 7] numpy arrays, rows (class, y_min, x_min,
+        y_max, x_max, area, first) in (class, first) order (regions.region_boxes) -- the reference's "Predicted Regions
+        with Boxes" (model/CE/testViTModel.py:34-42,171-185).  The forward, the mask and the labelling are enqueued on one
+        stream; the host waits once, for the region counts.  `return_mask`: also the uint8 [B, H, W] device mask."""
+        from . import regions as _regions
+        mask = self.predict_mask(x, interpolate_pos_encoding=interpolate_pos_encoding)
+        recs = _regions.region_boxes(mask, background=background, connectivity=connectivity)
+        return (recs, mask) if return_mask else recs
+
+    @torch.no_grad()
     def predict_mask_graphed(self, x: torch.Tensor, return_logits: bool = False, interpolate_pos_encoding: bool = False):
         """`predict_mask` replayed from a captured hipGraph (one per batch size and output set): the ~110 kernel
         launches of a forward become one graph launch.  Measured (tools/latency_probe.py, ViT-B/16): no gain at batch

@@ -68,20 +68,29 @@ def preprocess(image, size: int, device="cuda:0") -> torch.Tensor:
 
 
 def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, index_to_color=None,
-            return_logits: bool = False, serve_size: Optional[int] = None):
+            return_logits: bool = False, serve_size: Optional[int] = None, return_boxes: bool = False):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
-    resampled to it (interpolate_pos_encoding)."""
+    resampled to it (interpolate_pos_encoding).  `return_boxes`: also, last, the reference's "Predicted Regions with
+    Boxes" as {class: [(y_min, x_min, y_max, x_max), ...]} for every class present but 0 (testViTModel.py:171-185; the
+    4-connected regions of regions.region_boxes, computed on the device)."""
     seg = model.model if isinstance(model, LightningViTModel) else model
     S = serve_size if serve_size is not None else getattr(model, "serve_size", None)
     S = seg.cfg.image_size if S is None else int(S)
     x = preprocess(image, S, seg.arena.device)
     out = seg.predict_mask(x, return_logits=return_logits, interpolate_pos_encoding=S != seg.cfg.image_size)
-    mask = (out[0] if return_logits else out)[0].cpu().numpy()
+    mask_dev = (out[0] if return_logits else out)[0]
+    boxes = None
+    if return_boxes:
+        from .regions import boxes_by_class, region_boxes
+        boxes = boxes_by_class(region_boxes(mask_dev))
+    mask = mask_dev.cpu().numpy()
     res = [mask]
     if index_to_color is not None:
         res.append(np.asarray(index_to_color, dtype=np.uint8)[mask])
     if return_logits:
         res.append(out[1][0].cpu().numpy())
+    if return_boxes:
+        res.append(boxes)
     return res[0] if len(res) == 1 else tuple(res)
