@@ -401,6 +401,25 @@ size_t vitseg_regions_scratch_bytes(int n, int H, int W);
 int vitseg_regions(const uint8_t* mask, int n, int H, int W, int connectivity, int background, int32_t* counts,
                    int32_t* regions, int max_regions, int32_t* labels, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- exact Euclidean distance transforms and the signed-distance targets of binary masks (replaces
+ *      segmentation.compute_sdf = scipy.ndimage.distance_transform_edt of ~mask and of mask, each divided by its maximum,
+ *      model/PAED/segmentation.py:6-34, called per item by StructuralDamageDataset, model/PAED/classes.py:51-85) ----
+ * mask uint8 [n, H, W]: a non-zero byte is a mask pixel (astype(bool)).  Per image, d2 = the exact squared distance to the
+ * nearest feature pixel: the mask pixels for sdf_ext, the other pixels for sdf_int (feature pixels get 0).  An image with no
+ * feature pixel for a field gets scipy's result, the distance to the virtual point (-1, 0): d2 = (y + 1)^2 + x^2.
+ * sdf_ext, sdf_int float [n, H, W] (either may be NULL: that field is skipped):
+ *   normalize = 0: (float) sqrt((double) d2), i.e. distance_transform_edt(~m) and (m) cast to float32;
+ *   normalize = 1: that distance / (float) sqrt((double) max d2 of the image and field), IEEE float division, and 0
+ *   everywhere when the maximum is 0 -- compute_sdf's result.
+ * scratch: vitseg_sdf_scratch_bytes(n, H, W) device bytes (2 words per image; every word read is written within the call).
+ * All arithmetic before the final conversion is integer: the same bits on every call, and per image the same bits in any
+ * batch.  VITSEG_EINVAL: null mask or scratch, normalize not 0 / 1; VITSEG_ESHAPE: H or W outside 1..16384, n outside
+ * 1..65535; VITSEG_EWORKSPACE: scratch smaller than vitseg_sdf_scratch_bytes (0 for a bad shape).  Nothing is launched
+ * when a check fails. */
+size_t vitseg_sdf_scratch_bytes(int n, int H, int W);
+int vitseg_sdf(const uint8_t* mask, int n, int H, int W, int normalize, float* sdf_ext, float* sdf_int, void* scratch,
+               size_t scratch_bytes, void* stream);
+
 /* one Adam step over a flat fp32 buffer (torch.optim.Adam semantics, weight_decay 0, amsgrad off: torch's L2 weight decay,
  * g += weight_decay * p, is not implemented, and FusedAdam refuses a nonzero weight_decay);
  * step is 1-based; gradients are multiplied by grad_scale first (1/world for summed all-reduce). */

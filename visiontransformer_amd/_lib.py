@@ -46,7 +46,9 @@ AT_EXPORTS = [
 ]
 # connected regions of class masks and their boxes (regions.py): bound on first use, the same way
 REGION_EXPORTS = ["vitseg_regions_scratch_bytes", "vitseg_regions"]
-EXPORTS += AT_EXPORTS + REGION_EXPORTS   # every symbol include/vitseg.h declares
+# exact distance transforms and the signed-distance targets of binary masks (sdf.py): bound on first use, the same way
+SDF_EXPORTS = ["vitseg_sdf_scratch_bytes", "vitseg_sdf"]
+EXPORTS += AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS   # every symbol include/vitseg.h declares
 VERSION = 110   # include/vitseg.h VITSEG_VERSION this binding was written against
 KERNEL_KINDS = ["gemm_bias", "gemm_gelu", "gemm_resadd", "gemm_patch", "gemm_conv3", "attention", "layernorm",
                 "head1x1", "upsample", "train_gemm_fwd", "train_dgrad", "train_wgrad", "train_attn_fwd", "train_attn_bwd"]
@@ -157,7 +159,7 @@ def lib() -> C.CDLL:
         l.vitseg_profile_enable.argtypes = [i32]
         l.vitseg_profile_collect.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
         for name in EXPORTS:
-            if name not in AT_EXPORTS and name not in REGION_EXPORTS:
+            if name not in AT_EXPORTS and name not in REGION_EXPORTS and name not in SDF_EXPORTS:
                 getattr(l, name)  # raises AttributeError if the build is stale
         for name, args in _at_argtypes(vp, sz, i32, pcfg, psz).items():
             fn = getattr(l, name, None)
@@ -167,6 +169,10 @@ def lib() -> C.CDLL:
             l.vitseg_regions_scratch_bytes.argtypes = [i32, i32, i32]
             l.vitseg_regions_scratch_bytes.restype = sz
             l.vitseg_regions.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, sz, vp]
+        if getattr(l, "vitseg_sdf", None) is not None:
+            l.vitseg_sdf_scratch_bytes.argtypes = [i32, i32, i32]
+            l.vitseg_sdf_scratch_bytes.restype = sz
+            l.vitseg_sdf.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -202,6 +208,15 @@ def region_symbol(name: str):
     fn = getattr(lib(), name, None)
     if fn is None:
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before connected regions): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def sdf_symbol(name: str):
+    """One of SDF_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before distance transforms): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
 

@@ -139,3 +139,16 @@ class Preprocessor:
                 mask.data_ptr(), n, H, W, self._nearest(H, oh, mode).data_ptr(), self._nearest(W, ow, mode).data_ptr(),
                 oh, ow, _ptr(lut), int(dtype == torch.long), out.data_ptr(), torch.cuda.current_stream().cuda_stream))
         return out
+
+    def paed_binary_targets(self, mask_u8, size: int = 224) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """What the binary PAED dataset's item holds besides the image (model/PAED/classes.py:60-73), from decoded 'L' masks
+        uint8 [H, W] or [n, H, W] of any size: `Resize((size, size), NEAREST)` (Pillow-exact), `> 127`, then compute_sdf
+        (vitseg_sdf).  Returns (mask float32 [n, 1, size, size] of 0 / 1, sdf_ext, sdf_int float32 [n, size, size]) on the
+        device: the batch PAEDTrainer.training_step takes."""
+        from .sdf import _launch
+        if isinstance(mask_u8, np.ndarray):
+            mask_u8 = torch.from_numpy(np.ascontiguousarray(mask_u8))
+        binarise = {v: 1 for v in range(128, 256)}
+        m = self.masks(mask_u8, (size, size), NEAREST_PIL, value_to_class=binarise, dtype=torch.uint8)
+        sdf_ext, sdf_int = _launch(m, True)
+        return m[:, None].float(), sdf_ext, sdf_int

@@ -53,21 +53,36 @@ def ce_batches(cfg, n_images: int, batch_size: int, data: Optional[str] = None, 
     return [(xs[i:i + batch_size], ys[i:i + batch_size]) for i in range(0, xs.shape[0], batch_size)]
 
 
-def paed_binary_batches(cfg, n_images: int, batch_size: int, data: Optional[str] = None, seed: int = 0, sdf_size: int = 224):
+def paed_binary_batches(cfg, n_images: int, batch_size: int, data: Optional[str] = None, seed: int = 0, sdf_size: int = 224,
+                        sdf: str = "standin"):
     """[(images, masks [b,1,h,w] float 0/1, sdf_ext [b,h,w], sdf_int [b,h,w])]: the binary PAED dataset's items
-    (model/PAED/classes.py:60-88: mask resized to 224 NEAREST and binarised, SDFs computed from it on the host)."""
+    (model/PAED/classes.py:60-88: mask resized to 224 NEAREST and binarised, SDFs computed from it).  A `data` blob holds
+    "images" and either "masks", "sdf_ext", "sdf_int" or the decoded 'L' masks "raw_masks" (uint8 [n, H, W]), whose targets
+    Preprocessor.paed_binary_targets computes on the device.  Synthetic masks get smooth stand-in SDFs (`sdf="standin"`)
+    or their exact ones from sdf.compute_sdf (`sdf="exact"`)."""
+    if sdf not in ("standin", "exact"):
+        raise ValueError(f'sdf must be "standin" or "exact", got {sdf!r}')
     if data:
         blob = torch.load(data)
-        xs, ms, se, si = blob["images"].float(), blob["masks"].float(), blob["sdf_ext"].float(), blob["sdf_int"].float()
+        xs = blob["images"].float()
+        if "sdf_ext" not in blob and "raw_masks" in blob:
+            from .preprocess import Preprocessor
+            dev = f"cuda:{torch.cuda.current_device()}"
+            ms, se, si = Preprocessor(cfg.image_size, device=dev).paed_binary_targets(blob["raw_masks"], size=sdf_size)
+        else:
+            ms, se, si = blob["masks"].float(), blob["sdf_ext"].float(), blob["sdf_int"].float()
     else:
         xs = torch.from_numpy(synth.make_images(cfg, n_images, seed=seed))
         g = torch.Generator().manual_seed(seed + 17)
-        # blobs: threshold a smooth random field; the "SDFs" are smooth non-negative maps of the same size (synthetic
-        # stand-ins: the real ones come from scipy distance transforms in the dataset class, host-side I/O)
+        # blobs: threshold a smooth random field; the stand-in "SDFs" are smooth non-negative maps of the same size
         field = torch.nn.functional.avg_pool2d(torch.rand(n_images, 1, sdf_size + 30, sdf_size + 30, generator=g), 31, 1)
         ms = (field > field.mean()).float()
-        se = (field[:, 0] - field.amin()).clamp_min(0) * 40 * (1 - ms[:, 0])
-        si = (field.amax() - field[:, 0]).clamp_min(0) * 40 * ms[:, 0]
+        if sdf == "exact":
+            from .sdf import compute_sdf
+            se, si = compute_sdf(ms[:, 0].to(torch.uint8), device=f"cuda:{torch.cuda.current_device()}")
+        else:
+            se = (field[:, 0] - field.amin()).clamp_min(0) * 40 * (1 - ms[:, 0])
+            si = (field.amax() - field[:, 0]).clamp_min(0) * 40 * ms[:, 0]
     out = []
     for i in range(0, xs.shape[0], batch_size):
         out.append((xs[i:i + batch_size], ms[i:i + batch_size], se[i:i + batch_size], si[i:i + batch_size]))
