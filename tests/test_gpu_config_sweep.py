@@ -280,7 +280,7 @@ def switch_cases():
     return {"vitb": _Case(VITB, 12), "a5": _Case(CASES["a5"]["c"], 5)}
 
 
-# gn sets the column-group width of the tile visit order of the round-1 tile kernels (gemm.hip launch_one: the patch and head
+# gn sets the column-group width of the tile visit order of the round-1 tile kernels (gemm_tile.hip launch_one: the patch and head
 # GEMMs of the fp32 large route, every 16-bit linear at a5); f32p_noinl runs gemm_f32p's epilogues at each tile's end instead
 # of inline.  Neither changes what any output element sums or in which order: bitwise equal to the default.
 @pytest.mark.parametrize("case,precision,opt,value", [

@@ -422,7 +422,7 @@ def test_seventeen_classes_at_the_headline_size():
 def test_large_batch_head_conv_through_the_dma_kernel_is_bit_identical():
     """The 3x3 head conv of a large-batch fp32 forward can run on gemm_f32s (switch conv_dma; SA_CONV3_ALL: operands through the
     LDS-DMA ring, taps outside the image as out-of-range offsets) with the implicit GEMM's own fmaf chain per output: the same
-    bits as gemm.hip's kernel, here at 17 x 512x512 = 17 408 patch rows (above the small-batch route's limit), 2 layers."""
+    bits as gemm_tile.hip's kernel, here at 17 x 512x512 = 17 408 patch rows (above the small-batch route's limit), 2 layers."""
     cfg = ViTSegConfig(2, 16, 768, 2, 12, image_size=512)
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(cfg, seed=5).items()}
     x = torch.from_numpy(synth.make_images(cfg, 17, seed=4)).to(DEV)

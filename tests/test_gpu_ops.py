@@ -52,7 +52,7 @@ def test_layernorm(rows, D):
 @pytest.mark.parametrize("M,N,K,epi", [
     (128, 128, 32, 0), (257, 192, 64, 0), (788, 576, 192, 0), (300, 768, 768, 1), (1025, 768, 3072, 2),
     (130, 3072, 768, 1), (64, 256, 6912, 3), (33, 100, 48, 0), (2050, 2304, 768, 0),
-    # ragged against gemm.hip's 128x128 tiles and 32-deep K steps: M = 1, less than one tile, rows / columns either side
+    # ragged against gemm_tile.hip's 128x128 tiles and 32-deep K steps: M = 1, less than one tile, rows / columns either side
     # of a tile edge (N and ldc are multiples of 4), K not a multiple of 32
     (1, 64, 32, 0), (1, 768, 768, 2), (127, 132, 36, 1), (129, 124, 100, 0), (255, 260, 132, 2), (257, 388, 68, 3)])
 def test_linear_epilogues(M, N, K, epi):
@@ -99,7 +99,7 @@ def test_linear_epilogues(M, N, K, epi):
 ])
 def test_linear_f32_persistent_kernel(M, N, K, epi, extra, monkeypatch):
     """csrc/gemm_f32p.hip (persistent 256x128 kernel of the fp32 linears) against a float64 product, and BITWISE against
-    gemm.hip's tile kernel (same k order per dot product): modeling_vit.py:207-254."""
+    gemm_tile.hip's kernel (same k order per dot product): modeling_vit.py:207-254."""
     L = _lib.lib()
     A, W = _rand(M, K, seed=M), _rand(N, K, seed=N + 1, scale=0.05)
     bias = None if "nobias" in extra else _rand(N, seed=7, scale=0.1)
@@ -437,7 +437,7 @@ def test_attention_f32x3_is_fp32_grade(B, Np, A):
 
 
 # ---------------------------------------------------------------- every shape-selected tile variant of the 16-bit GEMM
-# csrc/gemm.hip picks the tile by shape: 256x256 for wide outputs (M >= 8192, N >= 2048: QKV, fc1 and the dgrad into
+# csrc/gemm_dispatch.hip picks the tile by shape: 256x256 for wide outputs (M >= 8192, N >= 2048: QKV, fc1 and the dgrad into
 # them at the BASELINE batches), 256x128 for long K (M >= 4096, K >= 2048: fc2 and the dgrads with a long reduction),
 # 128x128 otherwise, CLS rows optionally through the split-K side launch.  Each variant x epilogue the inference and
 # training paths use is compared with the fp64 product here (BASELINE configs[2] runs all of them).
@@ -478,7 +478,7 @@ def _drop_rows_np(M, N, p, seed, stream):
 def test_linear_h16_tile_variants(M, N, K, epi, extra, fmt, request):
     if fmt == "fp16" and (epi == 5 or "aux" in extra or "drop" in extra):
         pytest.skip("training epilogues exist for bf16 only (fp16 is an inference format)")
-    if "thin" in extra:   # a ragged row tile that fits the persistent kernel's last round would ride along instead (gemm.hip)
+    if "thin" in extra:   # a ragged row tile that fits the persistent kernel's last round would ride along instead (gemm_dispatch.hip)
         old = _lib.get_option("no_ragged_p8")
         request.addfinalizer(lambda: _lib.set_option("no_ragged_p8", old))
         _lib.set_option("no_ragged_p8", 1)

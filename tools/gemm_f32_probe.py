@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of the fp32 linear kernels on the model's shapes, interleaved rounds in ONE process (random operands): the
-persistent 256x128 kernel (csrc/gemm_f32p.hip) against gemm.hip's 128x128 tile kernel (VITSEG_NO_F32P=1); outputs must
+persistent 256x128 kernel (csrc/gemm_f32p.hip) against gemm_tile.hip's 128x128 tile kernel (VITSEG_NO_F32P=1); outputs must
 be bit-identical.    python3 tools/gemm_f32_probe.py [--batch 32] [--rounds 3] [--gn N]"""
 import argparse
 import os

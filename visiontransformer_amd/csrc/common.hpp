@@ -22,7 +22,7 @@ int hip_fail(hipError_t e, const char* what);
 // the launch path.  Initial values come from the environment variable of the same name ("VITSEG_" + upper case) ONCE, when
 // the library is loaded; vitseg_set_option() (include/vitseg.h) changes them afterwards.
 enum Opt {
-    OPT_NO_F32P = 0,       // fp32 linears on gemm.hip's tile kernel instead of gemm_f32p.hip
+    OPT_NO_F32P = 0,       // fp32 linears on gemm_tile.hip's kernel instead of gemm_f32p.hip
     OPT_NO_P8,             // 16-bit linears / weight gradients on the round-1 kernels instead of gemm_p8.hip
     OPT_NO_H16P,           // bias-epilogue 16-bit linears on gemm_p8.hip instead of gemm_h16p.hip
     OPT_NO_RAGGED_P8,      // a ragged last row tile never rides in the persistent kernel's last round
@@ -33,10 +33,10 @@ enum Opt {
     OPT_F32P_NOINL,        // gemm_f32p: every epilogue at its tile's end
     OPT_GN,                // column-group width of the tile order (0: by shape)
     OPT_NO_MASK2,          // two-class mask-only upsample through the general kernel instead of upsample_mask2_kernel
-    OPT_NO_SMALL,          // fp32 forwards of fewer than 2048 token rows on the large-batch kernels instead of the small-batch route (small.hpp)
+    OPT_NO_SMALL,          // fp32 forwards of fewer than SMALL_MAX_ROWS token rows on the large-batch kernels instead of the small-batch route (small.hpp)
     OPT_SMALL_VARIANT,     // gemm_f32s tile variant 1..5 for every launch (0: small_plan picks)
     OPT_SMALL_MAX_ROWS,    // fp32 forwards below this many token rows take the small-batch route (0: the built-in SMALL_MAX_ROWS)
-    OPT_CONV_DMA,          // the large-batch fp32 3x3 head conv on the LDS-DMA kernel (gemm_f32s SA_CONV3_ALL: same bits, -10 % time, 1.8x the L2-miss bytes) instead of gemm.hip's implicit GEMM
+    OPT_CONV_DMA,          // the large-batch fp32 3x3 head conv on the LDS-DMA kernel (gemm_f32s SA_CONV3_ALL: same bits, -10 % time, 1.8x the L2-miss bytes) instead of gemm_tile.hip's implicit GEMM
     OPT_COUNT
 };
 long opt(int id);

@@ -110,7 +110,7 @@ int upsample(const Fwd& f) {
 
 }  // namespace
 
-// ---- the large-batch route: gemm.hip's tile kernels (fp32 / fp32x3 / 16-bit operands), LayerNorm launches of their own ----
+// ---- the large-batch route: the GEMM router (gemm_dispatch.hip) and its tile kernels (fp32 / fp32x3 / 16-bit operands), LayerNorm launches of their own ----
 int walk_large(const Fwd& f) {
     const Shape& s = f.s;
     const int Mp = f.batch * s.Np, Mt = Mp + f.batch, D = s.D, I = s.I;

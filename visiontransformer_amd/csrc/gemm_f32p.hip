@@ -2,7 +2,7 @@
 // v_mfma_f32_32x32x2_f32) -- the q/k/v/o projections and the MLP of modeling_vit.py:207-254 on the parity path
 // (BASELINE configs[1], VITSEG_F32).  Roofline: fp32 matrix pipe, 157.3 TFLOP/s; algorithmic work 2 M N K per launch.
 //
-// Why a second fp32 kernel (gemm.hip's 128x128 one stays for the gathering loaders, the T-forms and small shapes):
+// Why a second fp32 kernel (gemm_tile.hip's 128x128 one stays for the gathering loaders, the T-forms and small shapes):
 // that kernel keeps the pipe 0.74-0.77 busy (profiles/r02_pmc_bench_f32.json).  It runs two independent 4-wave blocks
 // per CU that stay in lockstep (identical tiles), so both are in their prologue / epilogue / staging waits at the same
 // time, its operand prefetch is one K step deep (an HBM-fed operand such as fc2's 403 MB activation is late), and the
@@ -19,7 +19,7 @@
 //   * the accumulators hold C TRANSPOSED (MFMA A operand = W rows): a lane owns 4 consecutive columns of a row, parks
 //     them with one ds_write_b128 in a wave-private 4 KiB slab (outside the ring) and the slab is re-read row-wise, so
 //     global traffic is whole 128-byte lines.
-// The K order of every dot product is the one of gemm.hip's kernel (k = 32 kt + 8 j + 4 h + e), so results are
+// The K order of every dot product is the one of gemm_tile.hip's kernel (k = 32 kt + 8 j + 4 h + e), so results are
 // bit-identical to it -- and independent of the batch size.
 #include <stdlib.h>
 
@@ -523,7 +523,7 @@ int launch_f32p_one(const GemmArgs& a, hipStream_t s) {
 // true when the persistent kernel takes this fp32 GEMM: plain A, whole 128-column tiles, whole 32-float K steps,
 // enough tiles to fill the chip, operands addressable through one 2 GiB buffer descriptor
 bool gemm_f32p_applies(const GemmArgs& a, int epi) {
-    if (opt(OPT_NO_F32P)) return false;   // A/B against gemm.hip's kernel (tools/gemm_probe.py)
+    if (opt(OPT_NO_F32P)) return false;   // A/B against gemm_tile.hip's kernel (tools/gemm_probe.py)
     const int ldw = a.ldw ? a.ldw : a.K;
     const size_t a_bytes = ((size_t)a.M + FM) * a.lda * 4, w_bytes = (size_t)a.N * ldw * 4;
     const int tiles = ((a.M + FM - 1) / FM) * (a.N / FN);

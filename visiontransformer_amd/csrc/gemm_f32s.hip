@@ -673,7 +673,7 @@ int launch_gemm_f32s(SGemm a, int epi, int amode, hipStream_t s) {
     VITSEG_CHECK_ARG(amode != SA_PATCH || ((a.P == 8 || a.P == 16 || a.P == 32) && a.S % 4 == 0), VITSEG_ESHAPE, "gemm_f32s: patch size %d", a.P);
     VITSEG_CHECK_ARG((size_t)(amode == SA_TT ? a.K : a.M + 128) * a.lda * 4 < 0x7fffffffull && (size_t)(amode == SA_PLAIN_WT || amode == SA_TT ? a.K : a.N) * a.ldw * 4 < 0x7fffffffull, VITSEG_ESHAPE,
                      "gemm_f32s: operand beyond one buffer descriptor");
-    a.kh = epi == SE_PARTIAL || amode == SA_CONV3_ALL ? 1 : small_pieces(a.K);   // (the whole conv is ONE chain, as gemm.hip computes it)
+    a.kh = epi == SE_PARTIAL || amode == SA_CONV3_ALL ? 1 : small_pieces(a.K);   // (the whole conv is ONE chain, as gemm_tile.hip computes it)
     VITSEG_CHECK_ARG((amode == SA_CONV3_ALL) == (epi == SE_RELU), VITSEG_EINVAL, "gemm_f32s: SE_RELU is the whole-conv epilogue");
     const long env = opt(OPT_SMALL_VARIANT);   // 1..5: a tile variant of gemm_f32s_kernel; 6, 7: the one-image kernel (where it applies)
     a.variant = env > 0 && env <= NVARIANTS + 2 ? (int)env - 1 : small_plan(a, kc, epi, amode);

@@ -54,7 +54,7 @@ struct GemmArgs {
     int row_base;         // added to the row index of the dropout hash when a launch covers rows [row_base, row_base + M)
 };
 
-// x3: fp32 operands split into half pairs while staged, 3 fp16 MFMAs per product (fp32-grade results, gemm.hip X3)
+// the K-sliced side launch of the CLS rows (GemmArgs::thin_scratch): at most THIN_MAX_SPLITS slices of THIN_MAX_ROWS rows
 constexpr int THIN_MAX_SPLITS = 16, THIN_MAX_ROWS = 64;
 inline size_t thin_scratch_floats(int max_n) { return (size_t)THIN_MAX_SPLITS * THIN_MAX_ROWS * max_n; }
 // Small batches: a GEMM with at most 128 output tiles leaves most of the 512 block slots idle while each tile walks its whole K
@@ -67,6 +67,7 @@ inline int whole_split(int M, int N, int K, int kstep) {
     if (s > 8) s = 8;
     return s >= 2 ? s : 0;
 }
+// The GEMM router (gemm_dispatch.hip).  x3: fp32 operands split into half pairs while staged, 3 fp16 MFMAs per product (fp32-grade results, gemm_tile.hip X3)
 int launch_gemm_f32(const GemmArgs& a, int amode, int epi, hipStream_t s, int x3 = 0);  // 1: split A and W, 2: W pre-split
 int launch_gemm_f32_bwd(const GemmArgs& a, int amode, int ta, int tb, int epi, hipStream_t s);
 size_t wgrad_scratch_floats(int M, int N, int K);
@@ -93,7 +94,7 @@ int launch_gemm_f32p(const GemmArgs& a, int epi, hipStream_t s);
 bool wgrad_p8_applies(const GemmArgs& a);
 int wgrad_p8_splits(int M, int N, int K);
 int launch_wgrad_p8(GemmArgs a, float* scratch, hipStream_t s);
-int launch_splitk_reduce(const float* partial, float* out, size_t n4, int splits, hipStream_t s);
+int launch_splitk_reduce(const float* partial, float* out, size_t n4, int splits, hipStream_t s);   // splitk.hip
 
 // LayerNorm over the last dim (a4); out_fmt: 0 fp32 output, 1 bf16, 2 IEEE half.
 int launch_layernorm(const float* x, const float* w, const float* b, void* y, int rows, int D, float eps,

@@ -46,7 +46,7 @@ inline int check_config(const vitseg_config* c, Shape* s) {
 }
 
 // What the 16-bit precisions (VITSEG_BF16 / VITSEG_F16) need beyond check_config: their GEMMs step K in whole 64-value
-// slices (gemm.hip launch_gemm_bf16 / gemm_bf16_train), and fc2 reduces over K = intermediate_size.  Called by every
+// slices (gemm_dispatch.hip launch_gemm_bf16 / gemm_bf16_train), and fc2 reduces over K = intermediate_size.  Called by every
 // workspace query and entry point before anything is launched, so that a config is refused at query time rather than
 // part-way through a launch sequence.
 inline int check_precision(const Shape& s, int precision) {

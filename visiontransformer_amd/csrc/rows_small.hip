@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void resln_kernel(const SRows p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[i][e] += b4[e];
         }
-        if (p.drop.thresh && !p.embed) {   // the branch is dropped, not the residual (the mask of gemm.hip's EPI_RESADD: same key, same bits)
+        if (p.drop.thresh && !p.embed) {   // the branch is dropped, not the residual (the mask of gemm_tile.hip's EPI_RESADD: same key, same bits)
             const unsigned key = drop_key(p.drop.seed, p.drop.stream, (unsigned)row);
 #pragma unroll
             for (int i = 0; i < NV; ++i)

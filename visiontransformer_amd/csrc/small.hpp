@@ -14,7 +14,7 @@
 //
 // Summation order (what makes the results independent of the batch size inside the regime): a linear layer's reduction is
 // cut into small_splits(N, K) chunks -- a function of the layer's shape only, never of M -- each chunk is one fp32 fmaf
-// chain in the k order of gemm.hip's kernels (k = 32 kt + 8 j + 4 h + e), and the chunk sums are added in chunk order,
+// chain in the k order of gemm_tile.hip's kernels (k = 32 kt + 8 j + 4 h + e), and the chunk sums are added in chunk order,
 // then the bias, then the residual.  Tile shapes are chosen per M (small_plan) and do not enter the order.
 #pragma once
 #include "kernels.hpp"
@@ -35,7 +35,7 @@ enum SmallAMode {
     SA_CONV3 = 1,   // chunk s = tap (ky, kx) of the 3x3 head conv: rows of the token-major map shifted by the tap, zero outside
     SA_PATCH = 2,   // im2col of the NCHW image: row (b, gy, gx), k = (c, py, px)
     SA_PLAIN_WT = 3,// A plain, W in T-form: W[k * ldw + n] (the activation-gradient GEMMs read nn.Linear weights as they lie)
-    SA_CONV3_ALL = 5,// the whole 3x3 conv in one launch and ONE fmaf chain per output, k = (ky, kx, d) as gemm.hip's implicit GEMM
+    SA_CONV3_ALL = 5,// the whole 3x3 conv in one launch and ONE fmaf chain per output, k = (ky, kx, d) as gemm_tile.hip's implicit GEMM
                     // walks it (bit-identical to that kernel; K = D per tap, 9 D in all): the training forward's head conv, whose
                     // ReLU mask must not depend on a summation order (profiles/r05_notes.md)
     SA_TT = 4       // both in T-form: C[i][j] = sum_r A[r * lda + i] W[r * ldw + j], r < kvalid (weight gradients dW = dY^T X: the
