@@ -261,6 +261,32 @@ size_t vitseg_op_colsum_scratch_floats(int M, int N);
 size_t vitseg_op_wgrad_bf16_scratch_floats(int M, int N, int K);
 int vitseg_op_wgrad_bf16(const void* dY, const void* X, float* dW, float* scratch, const void* zeros, int M, int N, int K,
                          void* stream);
+/* ---- the K-sliced GEMM paths, one entry each so that tests can reach and name them ----
+ * vitseg_op_linear_f32_ex with the router's split-K arguments: x3 = 1 multiplies on the split-operand fp16 path (as
+ * vitseg_op_linear_f32x3); scratch / scratch_floats: fp32 partials.  With scratch, a GEMM of at most 128 output tiles and
+ * K >= 512 runs as a whole on K slices when the scratch holds slices * M * N floats; otherwise thin_rows > 0 sends the last
+ * thin_rows (<= 64) rows after a body of whole 128-row tiles through the split-K side launch (K >= 256, K % 32 == 0) when the
+ * scratch holds slices * thin_rows * N floats (16 * 64 * N always suffices).  A scratch that is too small is never written:
+ * the GEMM runs unsliced. */
+int vitseg_op_linear_f32_thin(const float* A, const float* W, const float* bias, const float* R, float* C, float* aux, int M,
+                              int N, int K, int epilogue, int x3, int thin_rows, float* scratch, size_t scratch_floats,
+                              float dropout_p, uint32_t dropout_seed, uint32_t dropout_stream, void* stream);
+/* fp32 weight gradient dW[M,N] = dY^T X with dY = [K tokens][M], X = [K tokens][N] fp32 row-major, split over the token rows:
+ * fp32 partials in `scratch` (>= vitseg_op_wgrad_f32_scratch_floats floats), fixed-order reduce.  M and N multiples of 4. */
+size_t vitseg_op_wgrad_f32_scratch_floats(int M, int N, int K);
+int vitseg_op_wgrad_f32(const float* dY, const float* X, float* dW, float* scratch, int M, int N, int K, void* stream);
+/* diagnostics: the number of K slices the router cuts a GEMM with a dense [M, N] output and reduction length K into on one of
+ * its sliced paths, 0 where that path does not take the shape (then the GEMM runs unsliced or on another path).  Host
+ * arithmetic by the functions the launches call; launches nothing and needs no device (it then assumes 256 compute units).
+ * WHOLE_*: the whole-GEMM split of small linears (32-deep K steps for fp32 / x3 operands, 64-deep for 16-bit ones); THIN_*:
+ * the side launch of trailing rows (a function of K only); WGRAD_F32: vitseg_op_wgrad_f32; WGRAD_BF16_TT / _P8:
+ * vitseg_op_wgrad_bf16 on the 128x128 kernel / on the 8-phase 256x256 kernel -- exactly one of the two is nonzero for a valid
+ * shape, following the option no_p8. */
+enum vitseg_slices_path {
+    VITSEG_SLICES_WHOLE_F32 = 0, VITSEG_SLICES_WHOLE_H16 = 1, VITSEG_SLICES_THIN_F32 = 2, VITSEG_SLICES_THIN_H16 = 3,
+    VITSEG_SLICES_WGRAD_F32 = 4, VITSEG_SLICES_WGRAD_BF16_TT = 5, VITSEG_SLICES_WGRAD_BF16_P8 = 6
+};
+int vitseg_dbg_gemm_slices(int path, int M, int N, int K);
 /* lowres fp32 [B, C, g, g] -> logits fp32 [B, C, S, S] and/or mask uint8 [B, S, S] */
 int vitseg_op_upsample_argmax(const float* lowres, float* logits, uint8_t* mask, int batch, int C, int g, int S,
                               void* stream);

@@ -48,7 +48,12 @@ AT_EXPORTS = [
 REGION_EXPORTS = ["vitseg_regions_scratch_bytes", "vitseg_regions"]
 # exact distance transforms and the signed-distance targets of binary masks (sdf.py): bound on first use, the same way
 SDF_EXPORTS = ["vitseg_sdf_scratch_bytes", "vitseg_sdf"]
-EXPORTS += AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS   # every symbol include/vitseg.h declares
+# the K-sliced GEMM paths, one entry each, and the router's slice counts (tests/test_splitk_cpu.py, tests/test_gpu_splitk.py):
+# bound on first use, the same way
+SPLITK_EXPORTS = ["vitseg_op_linear_f32_thin", "vitseg_op_wgrad_f32_scratch_floats", "vitseg_op_wgrad_f32", "vitseg_dbg_gemm_slices"]
+EXPORTS += AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS   # every symbol include/vitseg.h declares
+# enum vitseg_slices_path
+SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
 VERSION = 110   # include/vitseg.h VITSEG_VERSION this binding was written against
 KERNEL_KINDS = ["gemm_bias", "gemm_gelu", "gemm_resadd", "gemm_patch", "gemm_conv3", "attention", "layernorm",
                 "head1x1", "upsample", "train_gemm_fwd", "train_dgrad", "train_wgrad", "train_attn_fwd", "train_attn_bwd"]
@@ -159,7 +164,7 @@ def lib() -> C.CDLL:
         l.vitseg_profile_enable.argtypes = [i32]
         l.vitseg_profile_collect.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
         for name in EXPORTS:
-            if name not in AT_EXPORTS and name not in REGION_EXPORTS and name not in SDF_EXPORTS:
+            if name not in AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS:
                 getattr(l, name)  # raises AttributeError if the build is stale
         for name, args in _at_argtypes(vp, sz, i32, pcfg, psz).items():
             fn = getattr(l, name, None)
@@ -173,6 +178,13 @@ def lib() -> C.CDLL:
             l.vitseg_sdf_scratch_bytes.argtypes = [i32, i32, i32]
             l.vitseg_sdf_scratch_bytes.restype = sz
             l.vitseg_sdf.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+        if getattr(l, "vitseg_dbg_gemm_slices", None) is not None:
+            l.vitseg_op_linear_f32_thin.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, C.c_float,
+                                                    C.c_uint32, C.c_uint32, vp]
+            l.vitseg_op_wgrad_f32_scratch_floats.argtypes = [i32, i32, i32]
+            l.vitseg_op_wgrad_f32_scratch_floats.restype = sz
+            l.vitseg_op_wgrad_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+            l.vitseg_dbg_gemm_slices.argtypes = [i32, i32, i32, i32]
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -219,6 +231,20 @@ def sdf_symbol(name: str):
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before distance transforms): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
+
+
+def splitk_symbol(name: str):
+    """One of SPLITK_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the split-K entry points): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def gemm_slices(path: int, M: int, N: int, K: int) -> int:
+    """K slices of a GEMM with a dense [M, N] output on one of the router's sliced paths (SLICES_*); 0: the path does not apply."""
+    return int(splitk_symbol("vitseg_dbg_gemm_slices")(path, M, N, K))
 
 
 def _native(cfg: ViTSegConfig, image_size) -> bool:

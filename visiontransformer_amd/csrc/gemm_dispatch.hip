@@ -5,26 +5,35 @@
 namespace vitseg {
 namespace {
 
-// > 0: the whole (small) GEMM goes through K slices + the reducing epilogue kernel (kernels.hpp whole_split)
+// Slice counts as functions of the shape alone; the tests below add what depends on the arguments.  gemm_slices() reports these.
+// > 0: a (small) GEMM of this shape goes through K slices as a whole (kernels.hpp whole_split)
+int whole_split_shape(int M, int N, int K, int kstep) { return K % kstep == 0 ? whole_split(M, N, K, kstep) : 0; }
+
+// > 0: trailing rows of a GEMM with this K may go through the split-K side launch, on that many slices of >= 4 K steps
+int thin_slices(int K, int kstep) {
+    if (K < 256 || K % kstep != 0) return 0;
+    const int sl = K / kstep / 4;
+    return sl > THIN_MAX_SPLITS ? THIN_MAX_SPLITS : sl < 1 ? 1 : sl;
+}
+
+// > 0: the whole (small) GEMM goes through K slices + the reducing epilogue kernel
 int whole_split_applies(const GemmArgs& a, int epi, int kstep) {
-    const int sp = whole_split(a.M, a.N, a.K, kstep);
-    const bool ok = sp && a.thin_scratch && (size_t)sp * a.M * a.N <= a.thin_capacity && a.K % kstep == 0 && !a.drop.thresh &&
+    const int sp = whole_split_shape(a.M, a.N, a.K, kstep);
+    const bool ok = sp && a.thin_scratch && (size_t)sp * a.M * a.N <= a.thin_capacity && !a.drop.thresh &&
                     !a.aux && a.splitk <= 1 && a.ldc % 4 == 0 && (epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESADD);
     return ok ? sp : 0;
 }
 
-// true when the trailing rows of `a` should go through the split-K side launch (see GemmArgs::thin_scratch)
-// h16: the 16-bit path's reducing epilogue also covers dropout, the saved GELU derivative and dGELU (training)
-bool thin_split_applies(const GemmArgs& a, int epi, bool h16 = false) {
-    return a.thin_scratch && a.thin_rows > 0 && a.thin_rows <= THIN_MAX_ROWS && a.M > a.thin_rows &&
-           (a.M - a.thin_rows) % BM == 0 && a.K >= 256 && a.K % 32 == 0 && (h16 || (!a.drop.thresh && !a.aux)) &&
-           a.splitk <= 1 && a.ldc % 4 == 0 &&
-           (epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESADD || (h16 && epi == EPI_DGELU));
-}
-
-int thin_slices(int K, int kstep) {
-    const int sl = K / kstep / 4;  // >= 4 K steps per slice
-    return sl > THIN_MAX_SPLITS ? THIN_MAX_SPLITS : sl < 1 ? 1 : sl;
+// > 0: the trailing rows of `a` go through the split-K side launch (see GemmArgs::thin_scratch) on that many slices
+// kstep 64 (16-bit operands): the reducing epilogue also covers dropout, the saved GELU derivative and dGELU (training)
+int thin_split_applies(const GemmArgs& a, int epi, int kstep) {
+    const bool h16 = kstep == 64;
+    const int sl = thin_slices(a.K, kstep);
+    const bool ok = sl && a.thin_scratch && a.thin_rows > 0 && a.thin_rows <= THIN_MAX_ROWS && a.M > a.thin_rows &&
+                    (size_t)sl * a.thin_rows * a.N <= a.thin_capacity && (a.M - a.thin_rows) % BM == 0 &&
+                    (h16 || (!a.drop.thresh && !a.aux)) && a.splitk <= 1 && a.ldc % 4 == 0 &&
+                    (epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESADD || (h16 && epi == EPI_DGELU));
+    return ok ? sl : 0;
 }
 
 // A weight gradient on `splits` K slices (grid.y): partials in `scratch`, then the fixed-order reduce into a.C (deterministic)
@@ -62,9 +71,9 @@ int launch_gemm_f32(const GemmArgs& a_in, int amode, int epi, hipStream_t s, int
             a.thin_rows = a_in.M;
             return launch_thin_rows(GT_F32, x3, a, epi, sp, s);
         }
-        if (thin_split_applies(a_in, epi)) {
+        if (const int sl = thin_split_applies(a_in, epi, 32)) {
             // the CLS rows first (tiny, split over K), then the whole-tile body: an exact number of rounds of blocks
-            if (int rc = launch_thin_rows(GT_F32, x3, a_in, epi, thin_slices(a_in.K, 32), s)) return rc;
+            if (int rc = launch_thin_rows(GT_F32, x3, a_in, epi, sl, s)) return rc;
             a.M = a_in.M - a_in.thin_rows;
         }
     }
@@ -127,9 +136,10 @@ static int route_h16(const GemmArgs& a_in, int amode, int epi, H16Route& r) {
         if (a_in.M % 256 != 0 && a_in.M % 256 <= 128 && gemm_p8_applies(a_in, epi) &&
             gemm_p8_rounds(a_in.M, a_in.N) == gemm_p8_rounds(a_in.M - a_in.M % 256, a_in.N) && !opt(OPT_NO_RAGGED_P8))
             return persistent(a_in);
-        if (thin_split_applies(a_in, epi, true) && (a_in.M - a_in.thin_rows) % LBM == 0 && a_in.K % 64 == 0) {
+        const int sl = (a_in.M - a_in.thin_rows) % LBM == 0 ? thin_split_applies(a_in, epi, 64) : 0;
+        if (sl) {
             r.tail_rows = a_in.thin_rows;  // CLS rows: split-K side launch (GemmArgs)
-            r.slices = thin_slices(a_in.K, 64);
+            r.slices = sl;
             a.M = a_in.M - a_in.thin_rows;
         }
     }
@@ -215,7 +225,7 @@ int launch_wgrad_bf16_tt(GemmArgs a, float* scratch, hipStream_t s) {
     VITSEG_CHECK_ARG(a.M % 8 == 0 && a.N % 8 == 0 && a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldc == a.N && a.zeros,
                      VITSEG_ESHAPE, "wgrad_bf16_tt: M, N and the leading dimensions must be multiples of 8");
     if (wgrad_p8_applies(a)) return launch_wgrad_p8(a, scratch, s);   // 256x256 tiles, 8-phase stream (gemm_p8.hip)
-    const int splits = wgrad_splits(a.M, a.N, a.K, 64);
+    const int splits = wgrad_bf16_splits(a.M, a.N, a.K, false);
     VITSEG_CHECK_ARG(splits <= 1 || scratch, VITSEG_EINVAL, "wgrad_bf16_tt: split-K needs scratch");
     return sliced(a, splits, scratch, s, [&](const GemmArgs& g) { return launch_gemm_tt(g, s); });
 }
@@ -239,6 +249,25 @@ int launch_gemm_bf16_train(GemmArgs a, int epi, int out_f32, float* scratch, hip
     }
     set_error("gemm_bf16_train: unsupported epilogue %d / out_f32 %d", epi, out_f32);
     return VITSEG_EINVAL;
+}
+
+// The slice count of one K-sliced path for a dense [M, N] output reduced over K (include/vitseg.h vitseg_dbg_gemm_slices); 0 where
+// the path does not take that shape.  Host arithmetic through the functions the launches above call.
+int gemm_slices(int path, int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    GemmArgs g{};   // a weight gradient as vitseg_op_wgrad_bf16 lays it out
+    g.M = M; g.N = N; g.K = K; g.lda = M; g.ldw = N; g.ldc = N;
+    const bool tt_ok = M % 8 == 0 && N % 8 == 0;
+    switch (path) {
+        case VITSEG_SLICES_WHOLE_F32: return whole_split_shape(M, N, K, 32);
+        case VITSEG_SLICES_WHOLE_H16: return whole_split_shape(M, N, K, 64);
+        case VITSEG_SLICES_THIN_F32: return thin_slices(K, 32);
+        case VITSEG_SLICES_THIN_H16: return thin_slices(K, 64);
+        case VITSEG_SLICES_WGRAD_F32: return wgrad_splits(M, N, K, 32);
+        case VITSEG_SLICES_WGRAD_BF16_TT: return tt_ok && !wgrad_p8_applies(g) ? wgrad_bf16_splits(M, N, K, false) : 0;
+        case VITSEG_SLICES_WGRAD_BF16_P8: return tt_ok && wgrad_p8_applies(g) ? wgrad_bf16_splits(M, N, K, true) : 0;
+    }
+    return 0;
 }
 
 }  // namespace vitseg

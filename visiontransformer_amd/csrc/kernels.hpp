@@ -75,6 +75,8 @@ int launch_wgrad_f32(GemmArgs a, float* scratch, hipStream_t s);
 int launch_wgrad_bf16_tt(GemmArgs a, float* scratch, hipStream_t s);
 int launch_gemm_bf16_train(GemmArgs a, int epi, int out_f32, float* scratch, hipStream_t s);
 size_t wgrad_bf16_scratch_floats(int M, int N, int K);
+int wgrad_bf16_splits(int M, int N, int K, bool p8);   // splitk.hip: the slice count of the size query AND of the launch
+int gemm_slices(int path, int M, int N, int K);        // vitseg_dbg_gemm_slices: the router's slice count per sliced path
 // 16-bit operands, fp32 accumulate; f16 selects IEEE half instead of bf16 (inference formats, common.hpp H16<>)
 int launch_gemm_bf16(const GemmArgs& a, int amode, int epi, hipStream_t s, bool f16 = false);
 // persistent 8-phase 256x256 kernel for the large plain linear layers (gemm_p8.hip); `applies` = shape / alignment test

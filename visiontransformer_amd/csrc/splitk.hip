@@ -35,13 +35,16 @@ int wgrad_splits(int M, int N, int K, int kstep) {
 
 size_t wgrad_scratch_floats(int M, int N, int K) { return (size_t)wgrad_splits(M, N, K, 32) * M * N; }
 
-// Covers the 128x128 slicing and, for whole 256x256 tiles, the 8-phase kernel's (wgrad_p8_splits).  K counts whole 64-row steps:
-// callers size with the padded length (vitseg_train.hip Kpad); a remainder below 64 rows is not counted although gemm_tt.hip's
-// launch counts it as a step (kept as it was: workspace sizes are behaviour)
+// THE slice count of the bf16 T-form weight gradient: the 8-phase kernel's (p8) or the 128x128 kernel's.  A remainder of K below
+// 64 rows is a K step of its own in both kernels; the size query and launch_wgrad_bf16_tt both ask here.
+int wgrad_bf16_splits(int M, int N, int K, bool p8) { return p8 ? wgrad_p8_splits(M, N, K) : wgrad_splits(M, N, K, 64); }
+
+// Covers the 128x128 slicing and, for whole 256x256 tiles, the 8-phase kernel's: the router may pick either (wgrad_p8_applies
+// also looks at an option and the leading dimensions)
 size_t wgrad_bf16_scratch_floats(int M, int N, int K) {
-    int splits = wgrad_splits(M, N, K / 64 * 64, 64);
+    int splits = wgrad_bf16_splits(M, N, K, false);
     if (M % 256 == 0 && N % 256 == 0) {
-        const int sp8 = wgrad_p8_splits(M, N, K);
+        const int sp8 = wgrad_bf16_splits(M, N, K, true);
         if (sp8 > splits) splits = sp8;
     }
     return (size_t)splits * M * N;

@@ -419,6 +419,40 @@ int vitseg_op_wgrad_bf16(const void* dY, const void* X, float* dW, float* scratc
     return launch_wgrad_bf16_tt(g, scratch, (hipStream_t)stream);
 }
 
+int vitseg_op_linear_f32_thin(const float* A, const float* Wt, const float* bias, const float* R, float* C, float* aux, int M,
+                              int N, int K, int epilogue, int x3, int thin_rows, float* scratch, size_t scratch_floats,
+                              float dropout_p, uint32_t dropout_seed, uint32_t dropout_stream, void* stream) {
+    VITSEG_CHECK_ARG(A && Wt && C, VITSEG_EINVAL, "linear_f32_thin: null pointer");
+    VITSEG_CHECK_ARG(epilogue >= 0 && epilogue <= (x3 ? 2 : 3), VITSEG_EINVAL, "linear_f32_thin: epilogue %d", epilogue);
+    VITSEG_CHECK_ARG(epilogue != EPI_RESADD || R, VITSEG_EINVAL, "linear_f32_thin: residual epilogue needs R");
+    VITSEG_CHECK_ARG(x3 == 0 || x3 == 1, VITSEG_EINVAL, "linear_f32_thin: x3 %d", x3);
+    VITSEG_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, VITSEG_EINVAL, "linear_f32_thin: dropout_p %f", dropout_p);
+    VITSEG_CHECK_ARG(!aux || epilogue == EPI_GELU, VITSEG_EINVAL, "linear_f32_thin: aux belongs to the GELU epilogue");
+    VITSEG_CHECK_ARG(thin_rows >= 0, VITSEG_EINVAL, "linear_f32_thin: thin_rows %d", thin_rows);
+    GemmArgs g{};
+    g.A = A; g.W = Wt; g.bias = bias; g.R = R; g.C = C; g.aux = aux;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
+    if (scratch && scratch_floats) {
+        g.thin_rows = thin_rows;
+        g.thin_scratch = scratch;
+        g.thin_capacity = scratch_floats;
+    }
+    if (epilogue == EPI_RESADD) g.drop = drop_args(dropout_p, dropout_seed, dropout_stream);
+    return launch_gemm_f32(g, A_PLAIN, epilogue, (hipStream_t)stream, x3);
+}
+
+size_t vitseg_op_wgrad_f32_scratch_floats(int M, int N, int K) { return M > 0 && N > 0 && K > 0 ? wgrad_scratch_floats(M, N, K) : 0; }
+
+int vitseg_op_wgrad_f32(const float* dY, const float* X, float* dW, float* scratch, int M, int N, int K, void* stream) {
+    VITSEG_CHECK_ARG(dY && X && dW, VITSEG_EINVAL, "wgrad_f32: null pointer");
+    GemmArgs g{};
+    g.A = dY; g.W = X; g.C = dW;
+    g.M = M; g.N = N; g.K = K; g.lda = M; g.ldw = N; g.ldc = N;
+    return launch_wgrad_f32(g, scratch, (hipStream_t)stream);
+}
+
+int vitseg_dbg_gemm_slices(int path, int M, int N, int K) { return gemm_slices(path, M, N, K); }
+
 int vitseg_op_gemm_f32(const float* A, const float* Wt, const float* R, float* C, int M, int N, int K, int ta, int tb,
                        int epilogue, void* stream) {
     VITSEG_CHECK_ARG(A && Wt && C, VITSEG_EINVAL, "gemm: null pointer");
