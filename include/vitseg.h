@@ -298,12 +298,44 @@ int vitseg_op_upsample_bwd(const float* grad_logits, float* grad_lowres, int bat
  * lowres: fp32 [B, C, g, g] low-resolution logits (VITSEG_BUF_LOWRES after vitseg_forward); target: class
  * indices [B, S, S], int64 (torch.long, as the reference passes them) or uint8.  Writes the mean loss to
  * *loss (device fp32).  scratch: >= vitseg_ce_scratch_bytes() device bytes.  grad_logits (optional, fp32
- * [B, C, S, S]) receives d loss / d logits.  Labels must lie in [0, C); ignore_index is not supported: a pixel
+ * [B, C, S, S]) receives d loss / d logits.  Labels must lie in [0, C); these calls have no ignore_index: a pixel
  * with any other label (uint8 255, int64 -100 or C) makes the loss NaN and gets a NaN gradient (also in
- * vitseg_backward's fused loss). */
+ * vitseg_backward's fused loss).  ignore_index, class weights and label smoothing: the _opts calls below. */
 size_t vitseg_ce_scratch_bytes(int batch, int S);
 int vitseg_ce_loss(const float* lowres, const void* target, int target_is_u8, float* grad_logits, void* scratch,
                    float* loss, int batch, int C, int g, int S, void* stream);
+
+/* ---- the other constructor arguments of nn.CrossEntropyLoss: F.cross_entropy(up, y, weight=w, ignore_index=ii,
+ *      label_smoothing=eps, reduction="mean") on the same regenerated logits ----
+ *   keep = (y != ii);  den = sum over kept pixels of w[y];
+ *   loss = [ (1 - eps) sum_keep w[y] (lse - z_y) + (eps / C) sum_keep sum_c w[c] (lse - z_c) ] / den
+ *   d loss / d z_c = keep [ (1 - eps) w[y] (p_c - 1[c = y]) + (eps / C) (p_c sum_k w[k] - w[c]) ] loss_scale / den
+ * den depends on the targets: a count pass over them (fp64 per-block partials, fixed-order reduce, no atomics) leaves it
+ * in `scratch` on the device before the loss / gradient kernel runs; the host never reads it.
+ *  - a pixel whose label equals ignore_index contributes nothing; its grad_logits entries are written as 0.0f;
+ *  - den == 0 (everything ignored, or every kept pixel has weight 0): the loss is NaN, kept pixels get NaN gradients,
+ *    ignored pixels 0 -- torch's 0 / 0;
+ *  - a label outside [0, C) that is not ignore_index: NaN loss and NaN gradient at that pixel, as in vitseg_ce_loss; it
+ *    counts 1 in den, so every other pixel keeps its gradient;
+ *  - with has_ignore_index = 0, class_weight = NULL and label_smoothing = 0 the results are bit for bit vitseg_ce_loss's.
+ * C <= 255.  VITSEG_EINVAL before any launch: label_smoothing outside [0, 1], scratch NULL / not 8-byte aligned / smaller
+ * than vitseg_ce_options_scratch_bytes, a null pointer. */
+typedef struct vitseg_ce_options {
+    int32_t has_ignore_index;  /* 0: no label is ignored (ignore_index is not read) */
+    int32_t reserved;          /* 0 */
+    int64_t ignore_index;      /* compared with the label widened to int64: 255 (uint8 void label), -100 (torch's default) */
+    const float* class_weight; /* device fp32 [C], finite and >= 0; NULL = all ones */
+    float label_smoothing;     /* eps, 0 <= eps <= 1 */
+    void* scratch;             /* caller-owned device memory, >= vitseg_ce_options_scratch_bytes(batch, S); every word read
+                                  is written within the call */
+    size_t scratch_bytes;
+} vitseg_ce_options;
+size_t vitseg_ce_options_scratch_bytes(int batch, int S);
+/* vitseg_ce_loss with the options; loss_scale multiplies grad_logits (not *loss), as in vitseg_backward.  opts == NULL:
+ * exactly vitseg_ce_loss (the same launches), with loss_scale applied. */
+int vitseg_ce_loss_opts(const float* lowres, const void* target, int target_is_u8, float* grad_logits, void* scratch,
+                        float* loss, int batch, int C, int g, int S, const vitseg_ce_options* opts, float loss_scale,
+                        void* stream);
 
 /* ---- training (replaces autograd behind LightningViTModel.training_step, classes.py:276-285, and
  *      torch.optim.Adam(lr=1e-5).step(), classes.py:296-297).  dropout_p (the reference trains with 0.1,
@@ -349,6 +381,15 @@ int vitseg_backward_at(const vitseg_config* cfg, int image_size_in, const float*
                        const float* x, int batch, int precision, float dropout_p, uint64_t dropout_seed, const void* target,
                        int target_is_u8, const float* grad_logits, float* grads, float* loss, float loss_scale,
                        void* const* bucket_events, void* workspace, size_t workspace_bytes, void* stream);
+/* vitseg_backward / vitseg_backward_at (image_size_in == cfg->image_size: the plain geometry) whose fused CE loss takes
+ * the options of vitseg_ce_loss_opts: ce_options is read by the fused-CE branch (target != NULL) only; together with
+ * grad_logits it must be NULL (VITSEG_EINVAL).  ce_options == NULL: exactly the calls above.  The options' scratch is the
+ * caller's, so the training workspace keeps its size and layout. */
+int vitseg_backward_opts(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16,
+                         const float* x, int batch, int precision, float dropout_p, uint64_t dropout_seed, const void* target,
+                         int target_is_u8, const float* grad_logits, float* grads, float* loss, float loss_scale,
+                         void* const* bucket_events, void* workspace, size_t workspace_bytes, void* stream,
+                         const vitseg_ce_options* ce_options);
 int vitseg_grad_bucket_count(const vitseg_config* cfg);
 int vitseg_grad_bucket_range(const vitseg_config* cfg, int bucket, size_t* offset_floats, size_t* n_floats);
 /* ---- pre-processing (replaces transforms.Resize((S, S)) + transforms.ToTensor() on the PIL image,

@@ -13,7 +13,7 @@ import argparse
 import torch
 
 from classes import LightningViTModel  # noqa: F401  (the import the reference script uses)
-from visiontransformer_amd import dist as vdist, synth, trainer
+from visiontransformer_amd import dist as vdist, scripts, synth, trainer
 from visiontransformer_amd.predict import CONFIGURATIONS
 
 
@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=100)         # max_epochs=100, :72
     ap.add_argument("--patience", type=int, default=3)
     ap.add_argument("--data")
+    scripts.add_ce_loss_arguments(ap)
     ap.add_argument("--ckpt-dir", default="logs/vit-model/version_0/checkpoints")
     ap.add_argument("--resume")
     a = ap.parse_args()
@@ -34,7 +35,8 @@ def main():
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
     P, D, L, A = CONFIGURATIONS[a.model_id]
-    model = LightningViTModel(a.num_classes, P, D, L, A, image_size=a.image_size, device=dev)
+    model = LightningViTModel(a.num_classes, P, D, L, A, image_size=a.image_size, device=dev,
+                              **scripts.ce_loss_options(a))
     cfg = model.model.cfg
     if a.data:
         blob = torch.load(a.data)

@@ -3,6 +3,7 @@
 
     python3 tools/op_probe.py linear --M 32800 --N 3072 --K 768 --epi 1 --iters 10
     python3 tools/op_probe.py attention --B 32 --Np 1024 --A 12
+    python3 tools/op_probe.py ce --B 64 --S 512 --g 32 --C 2 [--u8]     # plain fused CE, then ignore + weights + smoothing
 """
 import argparse
 import os
@@ -15,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from visiontransformer_amd import _lib  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("op", choices=["linear", "attention", "layernorm", "linear_ex", "wgrad", "attn_bwd"])
+ap.add_argument("op", choices=["linear", "attention", "layernorm", "linear_ex", "wgrad", "attn_bwd", "ce"])
 ap.add_argument("--M", type=int, default=32800)
 ap.add_argument("--N", type=int, default=3072)
 ap.add_argument("--K", type=int, default=768)
@@ -25,6 +26,10 @@ ap.add_argument("--Np", type=int, default=1024)
 ap.add_argument("--A", type=int, default=12)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--bf16", action="store_true")
+ap.add_argument("--S", type=int, default=512, help="ce: image side")
+ap.add_argument("--g", type=int, default=32, help="ce: low-res grid")
+ap.add_argument("--C", type=int, default=2, help="ce: classes")
+ap.add_argument("--u8", action="store_true", help="ce: uint8 targets (what the training step feeds) instead of int64")
 ap.add_argument("--drop", type=float, default=0.0)
 ap.add_argument("--scale", type=float, default=1.0, help="attention: standard deviation of the q | k | v entries")
 ap.add_argument("--aux", action="store_true", help="linear_ex, epi 1: also write the saved GELU derivative")
@@ -33,7 +38,36 @@ a = ap.parse_args()
 dev = "cuda:0"
 st = torch.cuda.current_stream().cuda_stream
 L = _lib.lib()
-if a.op == "attn_bwd":   # bf16 attention forward (with lse) + backward, optional attention dropout
+if a.op == "ce":   # fused upsample + CE with its gradient: the plain kernels, then the options path on the same inputs
+    import ctypes
+    z = torch.randn(a.B, a.C, a.g, a.g, device=dev)
+    t = torch.randint(0, a.C, (a.B, a.S, a.S), device=dev)
+    t[torch.rand(a.B, a.S, a.S, device=dev) < 0.1] = 255
+    t = t.to(torch.uint8) if a.u8 else t
+    G = torch.empty(a.B, a.C, a.S, a.S, device=dev)
+    scr = torch.empty(L.vitseg_ce_scratch_bytes(a.B, a.S), dtype=torch.uint8, device=dev)
+    nb = int(_lib.ce_opts_symbol("vitseg_ce_options_scratch_bytes")(a.B, a.S))
+    oscr = torch.empty(nb, dtype=torch.uint8, device=dev)
+    w = torch.rand(a.C, device=dev) + 0.5
+    loss = torch.empty(1, device=dev)
+    o = _lib.CCEOptions(1, 0, 255, w.data_ptr(), 0.1, oscr.data_ptr(), nb)
+    args = (z.data_ptr(), t.data_ptr(), int(a.u8), G.data_ptr(), scr.data_ptr(), loss.data_ptr(), a.B, a.C, a.g, a.S)
+    plain = lambda: _lib.check(L.vitseg_ce_loss(*args, st))   # (the 255 labels make its loss NaN; the work is the same)
+    run = lambda: _lib.check(_lib.ce_opts_symbol("vitseg_ce_loss_opts")(*args, ctypes.byref(o), 1.0, st))
+    work = float(G.numel() * 4 + t.numel() * t.element_size())   # bytes: the gradient written, the targets read once
+    for name, fn in (("plain", plain), ("options", run)):
+        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / a.iters
+        print(f"ce {name}: {ms:.3f} ms/call, {work / ms / 1e6:.0f} GB/s of gradient written + targets read once "
+              f"(device time between events, B {a.B} C {a.C} S {a.S}, {'uint8' if a.u8 else 'int64'} targets)")
+    raise SystemExit(0)
+elif a.op == "attn_bwd":   # bf16 attention forward (with lse) + backward, optional attention dropout
     D = 64 * a.A
     Mt = a.B * a.Np + a.B
     qkv = torch.randn(Mt, 3 * D, device=dev).to(torch.bfloat16)

@@ -51,12 +51,21 @@ SDF_EXPORTS = ["vitseg_sdf_scratch_bytes", "vitseg_sdf"]
 # the K-sliced GEMM paths, one entry each, and the router's slice counts (tests/test_splitk_cpu.py, tests/test_gpu_splitk.py):
 # bound on first use, the same way
 SPLITK_EXPORTS = ["vitseg_op_linear_f32_thin", "vitseg_op_wgrad_f32_scratch_floats", "vitseg_op_wgrad_f32", "vitseg_dbg_gemm_slices"]
-EXPORTS += AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS   # every symbol include/vitseg.h declares
+# the fused cross-entropy with ignore_index / class weights / label smoothing (model.ce_loss): bound on first use, the same way
+CE_OPTS_EXPORTS = ["vitseg_ce_options_scratch_bytes", "vitseg_ce_loss_opts", "vitseg_backward_opts"]
+EXPORTS += AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
 VERSION = 110   # include/vitseg.h VITSEG_VERSION this binding was written against
 KERNEL_KINDS = ["gemm_bias", "gemm_gelu", "gemm_resadd", "gemm_patch", "gemm_conv3", "attention", "layernorm",
                 "head1x1", "upsample", "train_gemm_fwd", "train_dgrad", "train_wgrad", "train_attn_fwd", "train_attn_bwd"]
+
+
+class CCEOptions(C.Structure):
+    """struct vitseg_ce_options (include/vitseg.h)."""
+    _fields_ = [("has_ignore_index", C.c_int32), ("reserved", C.c_int32), ("ignore_index", C.c_int64),
+                ("class_weight", C.c_void_p), ("label_smoothing", C.c_float), ("scratch", C.c_void_p),
+                ("scratch_bytes", C.c_size_t)]
 
 
 class CConfig(C.Structure):
@@ -164,7 +173,7 @@ def lib() -> C.CDLL:
         l.vitseg_profile_enable.argtypes = [i32]
         l.vitseg_profile_collect.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
         for name in EXPORTS:
-            if name not in AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS:
+            if name not in AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS:
                 getattr(l, name)  # raises AttributeError if the build is stale
         for name, args in _at_argtypes(vp, sz, i32, pcfg, psz).items():
             fn = getattr(l, name, None)
@@ -185,6 +194,10 @@ def lib() -> C.CDLL:
             l.vitseg_op_wgrad_f32_scratch_floats.restype = sz
             l.vitseg_op_wgrad_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
             l.vitseg_dbg_gemm_slices.argtypes = [i32, i32, i32, i32]
+        if getattr(l, "vitseg_backward_opts", None) is not None:
+            for name, args in _ce_opts_argtypes(vp, sz, i32, pcfg).items():
+                getattr(l, name).argtypes = args
+            l.vitseg_ce_options_scratch_bytes.restype = sz
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -204,6 +217,25 @@ def _at_argtypes(vp, sz, i32, pcfg, psz) -> dict:
         "vitseg_pos_interp": [vp, vp, i32, i32, i32, vp],
         "vitseg_pos_interp_bwd": [vp, vp, vp, i32, i32, i32, vp],
     }
+
+
+def _ce_opts_argtypes(vp, sz, i32, pcfg) -> dict:
+    f32, popt = C.c_float, C.POINTER(CCEOptions)
+    return {
+        "vitseg_ce_options_scratch_bytes": [i32, i32],
+        "vitseg_ce_loss_opts": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, popt, f32, vp],
+        "vitseg_backward_opts": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp,
+                                 popt],
+    }
+
+
+def ce_opts_symbol(name: str):
+    """One of CE_OPTS_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the cross-entropy options): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
 
 
 def at_symbol(name: str):

@@ -401,6 +401,8 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// (ce_fixed_order_sum below restates this reduction for the options path, so that this kernel's code stays as it is:
+// an edit to the order here is mirrored there -- the options path at its defaults must give this kernel's bits)
 __global__ __launch_bounds__(1024) void ce_finish_kernel(const double* __restrict__ partial, int n, double inv_count,
                                                          float* __restrict__ loss) {
     __shared__ double red[1024];
@@ -423,6 +425,185 @@ __global__ __launch_bounds__(1024) void ce_finish_kernel(const double* __restric
     if (threadIdx.x == 0) *loss = (float)(red[0] * inv_count);
 }
 
+// ---- cross-entropy with options: F.cross_entropy(up, y, weight=w, ignore_index=ii, label_smoothing=eps) ----
+//   keep = (y != ii);  den = sum_keep w[y];
+//   loss = [ (1 - eps) sum_keep w[y] (lse - z_y) + (eps / C) sum_keep sum_c w[c] (lse - z_c) ] / den
+//   dL/dz_c = keep [ (1 - eps) w[y] (p_c - 1[c = y]) + (eps / C) (p_c sum_k w[k] - w[c]) ] gscale / den
+// The mean's denominator depends on the targets, and the gradient kernel needs it before it writes G: a count pass over
+// the targets alone (ce_count_kernel: fp64 per-block partials of w[y] keep) and a fixed-order reduce to one device double
+// (ce_count_finish_kernel) run first on the same stream -- no atomics, no host read.  A label outside [0, C) that is not
+// the ignored one stays what it is in ce_loss_kernel (NaN loss, NaN gradient at its pixel) and counts 1 in den, as it does
+// in the plain mean over B S S pixels, so that every other pixel keeps the gradient it would have had.
+// The picked-class sum and the smoothing sum are reduced apart and each is divided by den, and each gradient term is scaled
+// by 1 / den on its own, as torch forms them: with den == 0 the picked-class part is 0 * inf = NaN whatever the smoothing
+// part holds (kept pixels of weight 0 under smoothing: NaN, not inf).
+// With no label ignored, no weights and eps = 0 every product below is by 1 or adds +0: the bits of ce_loss_kernel.
+constexpr int CE_COUNT_PER_THREAD = 4;   // targets per thread of the count pass (block = 1024 consecutive targets)
+
+// the fixed-order sum of ce_finish_kernel: 4 independent strided chains per thread, then a tree; the result is in red[0]
+__device__ __forceinline__ void ce_fixed_order_sum(const double* __restrict__ partial, int n, double* red) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int i = threadIdx.x;
+    for (; i + 3 * 1024 < n; i += 4 * 1024) {
+        s0 += partial[i];
+        s1 += partial[i + 1024];
+        s2 += partial[i + 2 * 1024];
+        s3 += partial[i + 3 * 1024];
+    }
+    for (; i < n; i += 1024) s0 += partial[i];
+    red[threadIdx.x] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+}
+
+struct CeOpt {
+    const float* weight;   // [C] or null (all ones)
+    long long ignore;      // read only when has_ignore
+    int has_ignore;
+    float eps;
+};
+
+// class weights of the block in LDS (C <= 255); every thread of the block calls this
+__device__ __forceinline__ void ce_stage_weights(float* wsh, const float* __restrict__ weight, int C) {
+    if ((int)threadIdx.x < C) wsh[threadIdx.x] = weight ? weight[threadIdx.x] : 1.f;
+    __syncthreads();
+}
+
+template <typename TargetT>
+__global__ __launch_bounds__(256) void ce_count_kernel(const TargetT* __restrict__ target, CeOpt o, double* __restrict__ partial,
+                                                       size_t npx, int C) {
+    __shared__ float wsh[256];
+    __shared__ double red[4];
+    ce_stage_weights(wsh, o.weight, C);
+    const size_t base = (size_t)blockIdx.x * (256 * CE_COUNT_PER_THREAD) + threadIdx.x;
+    double local = 0.0;
+#pragma unroll
+    for (int k = 0; k < CE_COUNT_PER_THREAD; ++k) {   // consecutive lanes read consecutive targets
+        const size_t idx = base + (size_t)k * 256;
+        if (idx < npx) {
+            const long long tl = (long long)target[idx];   // uint8 widened before the compare
+            const bool ignored = o.has_ignore && tl == o.ignore;
+            const bool bad = tl < 0 || tl >= C;
+            local += ignored ? 0.0 : (bad ? 1.0 : (double)wsh[bad ? 0 : (int)tl]);
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) local += __shfl_xor(local, s, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(1024) void ce_count_finish_kernel(const double* __restrict__ partial, int n, double* __restrict__ den) {
+    __shared__ double red[1024];
+    ce_fixed_order_sum(partial, n, red);
+    if (threadIdx.x == 0) *den = red[0];
+}
+
+// ce_loss_kernel with the options: same taps, same fma placement, same online log-sum-exp; one thread per pixel.
+template <typename TargetT>
+__global__ __launch_bounds__(256) void ce_loss_opts_kernel(const float* __restrict__ Z, const TargetT* __restrict__ target,
+                                                           float* __restrict__ G, double* __restrict__ partial,
+                                                           double* __restrict__ spartial, const double* __restrict__ den,
+                                                           CeOpt o, int B, int C, int g, int S, float gscale) {
+    __shared__ float wsh[256];
+    __shared__ double red[4], sred[4];
+    ce_stage_weights(wsh, o.weight, C);
+    const size_t npx = (size_t)B * S * S;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double local = 0.0, slocal = 0.0;   // the picked-class term and the smoothing term of this pixel
+    const bool smooth = o.eps > 0.f;
+    if (idx < npx) {
+        const int X = (int)(idx % S), Y = (int)((idx / S) % S), b = (int)(idx / ((size_t)S * S));
+        const long long tl = (long long)target[idx];
+        if (o.has_ignore && tl == o.ignore) {   // contributes nothing; G arrives uninitialised, so its zeros are written
+            if (G)
+                for (int c = 0; c < C; ++c) G[(((size_t)b * C + c) * S + Y) * S + X] = 0.0f;
+        } else {
+            const float scale = (float)g / (float)S;
+            int y0, y1, x0, x1;
+            float wy0, wy1, wx0, wx1;
+            taps(Y, scale, g, y0, y1, wy0, wy1);
+            taps(X, scale, g, x0, x1, wx0, wx1);
+            const bool bad = tl < 0 || tl >= C;
+            const int t = bad ? -1 : (int)tl;
+            auto logit = [&](int c) {
+                const float* zt = Z + (((size_t)b * C + c) * g + y0) * g;
+                const float* zb = Z + (((size_t)b * C + c) * g + y1) * g;
+                const float top = __fmaf_rn(zt[x0], wx0, __fmul_rn(zt[x1], wx1));
+                const float bot = __fmaf_rn(zb[x0], wx0, __fmul_rn(zb[x1], wx1));
+                return __fmaf_rn(top, wy0, __fmul_rn(bot, wy1));
+            };
+            float m = -INFINITY, ssum = 0.f, picked = 0.f;
+            // label smoothing: sum_c w[c] z_c and sum_c w[c] in fp64 (exact products, one rounding per add), so that
+            // lse sum w - sum w z cancels no fp32 roundings
+            double swz = 0.0, sw = 0.0;
+            for (int c = 0; c < C; ++c) {  // online logsumexp
+                const float v = logit(c);
+                if (c == t) picked = v;
+                const float mn = fmaxf(m, v);
+                ssum = ssum * expf(m - mn) + expf(v - mn);
+                m = mn;
+                if (smooth) {
+                    const double wc = (double)wsh[c];
+                    swz += wc * (double)v;
+                    sw += wc;
+                }
+            }
+            const float lse = m + logf(ssum);
+            const float wy = bad ? 1.f : wsh[t];
+            const float a = (1.f - o.eps) * wy;          // weight of the picked-class term
+            const float bsm = o.eps / (float)C;          // weight of each class's smoothing term
+            local = (double)a * (double)(lse - picked);
+            if (smooth) slocal = (double)bsm * ((double)lse * sw - swz);
+            if (bad) local = (double)NAN;
+            if (G) {
+                const float inv = gscale / (float)*den;   // den == 0: inf, and 0 * inf = NaN as the arithmetic gives
+                const float swf = (float)sw;
+                for (int c = 0; c < C; ++c) {
+                    const float pc = expf(logit(c) - lse);
+                    float v = (a * (pc - (c == t ? 1.f : 0.f))) * inv;
+                    if (smooth) v += (bsm * (pc * swf - wsh[c])) * inv;
+                    G[(((size_t)b * C + c) * S + Y) * S + X] = bad ? NAN : v;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) local += __shfl_xor(local, s, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
+    __syncthreads();
+    if (smooth) {   // (uniform over the grid)
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) slocal += __shfl_xor(slocal, s, 64);
+        if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = slocal;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        if (smooth) spartial[blockIdx.x] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+    }
+}
+
+// spartial: the smoothing partials, or null (eps == 0: they were not written)
+__global__ __launch_bounds__(1024) void ce_finish_opts_kernel(const double* __restrict__ partial,
+                                                              const double* __restrict__ spartial, int n,
+                                                              const double* __restrict__ den, float* __restrict__ loss) {
+    __shared__ double red[1024];
+    const double inv = 1.0 / *den;
+    ce_fixed_order_sum(partial, n, red);
+    double total = red[0] * inv;   // den == 0: 0 * inf = NaN, torch's 0 / 0
+    if (spartial) {
+        __syncthreads();   // red[0] is read above by every thread before the second sum overwrites it
+        ce_fixed_order_sum(spartial, n, red);
+        total += red[0] * inv;
+    }
+    if (threadIdx.x == 0) *loss = (float)total;
+}
+
 }  // namespace
 
 size_t ce_partial_count(int B, int S) { return ((size_t)B * S * S + 255) / 256; }
@@ -440,6 +621,55 @@ int launch_ce_loss(const float* Z, const void* target, int target_is_u8, float* 
     VITSEG_LAUNCH_CHECK("ce_loss");
     hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(1024), 0, s, partial, (int)nb, 1.0 / ((double)B * S * S), loss);
     VITSEG_LAUNCH_CHECK("ce_finish");
+    return VITSEG_OK;
+}
+
+// scratch of the options: the denominator (one double in a 16-byte slot) | the count pass's per-block partials | the loss
+// kernel's per-block partials of the smoothing term
+size_t ce_count_partial_count(int B, int S) {
+    return ((size_t)B * S * S + 256 * CE_COUNT_PER_THREAD - 1) / (256 * CE_COUNT_PER_THREAD);
+}
+size_t ce_opts_scratch_bytes(int B, int S) {
+    return 16 + (ce_count_partial_count(B, S) + ce_partial_count(B, S)) * sizeof(double);
+}
+
+int check_ce_options(const vitseg_ce_options& o, int B, int C, int S) {
+    VITSEG_CHECK_ARG(o.label_smoothing >= 0.f && o.label_smoothing <= 1.f, VITSEG_EINVAL,
+                     "ce options: label_smoothing %f outside [0, 1]", (double)o.label_smoothing);   // (a NaN fails both)
+    VITSEG_CHECK_ARG(C >= 1 && C <= 255, VITSEG_EINVAL, "ce options: %d classes (1..255)", C);
+    VITSEG_CHECK_ARG(o.scratch && ((uintptr_t)o.scratch & 7) == 0, VITSEG_EINVAL, "ce options: scratch is null or not 8-byte aligned");
+    VITSEG_CHECK_ARG(o.scratch_bytes >= ce_opts_scratch_bytes(B, S), VITSEG_EINVAL, "ce options: scratch %zu < required %zu",
+                     o.scratch_bytes, ce_opts_scratch_bytes(B, S));
+    return VITSEG_OK;
+}
+
+int launch_ce_loss_opts(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B,
+                        int C, int g, int S, const vitseg_ce_options& opts, hipStream_t s, float gscale) {
+    VITSEG_CHECK_ARG(Z && target && partial && loss, VITSEG_EINVAL, "ce_loss: null pointer");
+    if (int rc = check_ce_options(opts, B, C, S)) return rc;
+    const size_t npx = (size_t)B * S * S;
+    const unsigned nb = (unsigned)ce_partial_count(B, S), nc = (unsigned)ce_count_partial_count(B, S);
+    double* den = (double*)opts.scratch;
+    double* cpart = (double*)((char*)opts.scratch + 16);
+    double* spart = cpart + nc;
+    const CeOpt o{opts.class_weight, (long long)opts.ignore_index, opts.has_ignore_index != 0, opts.label_smoothing};
+    if (target_is_u8)
+        hipLaunchKernelGGL(ce_count_kernel<uint8_t>, dim3(nc), dim3(256), 0, s, (const uint8_t*)target, o, cpart, npx, C);
+    else
+        hipLaunchKernelGGL(ce_count_kernel<long long>, dim3(nc), dim3(256), 0, s, (const long long*)target, o, cpart, npx, C);
+    VITSEG_LAUNCH_CHECK("ce_count");
+    hipLaunchKernelGGL(ce_count_finish_kernel, dim3(1), dim3(1024), 0, s, cpart, (int)nc, den);
+    VITSEG_LAUNCH_CHECK("ce_count_finish");
+    if (target_is_u8)
+        hipLaunchKernelGGL(ce_loss_opts_kernel<uint8_t>, dim3(nb), dim3(256), 0, s, Z, (const uint8_t*)target, G, partial, spart, den,
+                           o, B, C, g, S, gscale);
+    else
+        hipLaunchKernelGGL(ce_loss_opts_kernel<long long>, dim3(nb), dim3(256), 0, s, Z, (const long long*)target, G, partial,
+                           spart, den, o, B, C, g, S, gscale);
+    VITSEG_LAUNCH_CHECK("ce_loss_opts");
+    hipLaunchKernelGGL(ce_finish_opts_kernel, dim3(1), dim3(1024), 0, s, partial,
+                       opts.label_smoothing > 0.f ? (const double*)spart : nullptr, (int)nb, den, loss);
+    VITSEG_LAUNCH_CHECK("ce_finish_opts");
     return VITSEG_OK;
 }
 

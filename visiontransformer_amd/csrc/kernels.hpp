@@ -132,6 +132,13 @@ int launch_upsample(const float* Z, float* logits, uint8_t* mask, int B, int C, 
 size_t ce_partial_count(int B, int S);
 int launch_ce_loss(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B,
                    int C, int g, int S, hipStream_t s, float gscale = 1.0f);
+// ... with ignore_index / class weights / label smoothing (vitseg_ce_options): a count pass over the targets leaves the
+// mean's denominator on the device (opts.scratch, ce_opts_scratch_bytes), then the loss / gradient kernel with the options.
+// check_ce_options: the argument checks of the options alone (VITSEG_EINVAL), for callers that launch other work first.
+size_t ce_opts_scratch_bytes(int B, int S);
+int check_ce_options(const vitseg_ce_options& o, int B, int C, int S);
+int launch_ce_loss_opts(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B,
+                        int C, int g, int S, const vitseg_ce_options& opts, hipStream_t s, float gscale = 1.0f);
 
 // CLS token rows of the embedding output: X[B*Np + b] = cls + pos[0]  (a3)
 int launch_cls_rows(const float* cls, const float* pos, float* X, int B, int Np, int D, hipStream_t s);

@@ -288,6 +288,21 @@ int vitseg_ce_loss(const float* lowres, const void* target, int target_is_u8, fl
                           (hipStream_t)stream);
 }
 
+size_t vitseg_ce_options_scratch_bytes(int batch, int S) {
+    return batch >= 1 && S >= 1 ? ce_opts_scratch_bytes(batch, S) : 0;
+}
+
+int vitseg_ce_loss_opts(const float* lowres, const void* target, int target_is_u8, float* grad_logits, void* scratch,
+                        float* loss, int batch, int C, int g, int S, const vitseg_ce_options* opts, float loss_scale,
+                        void* stream) {
+    VITSEG_CHECK_ARG(batch >= 1 && C >= 1 && g >= 1 && S >= g, VITSEG_EINVAL, "ce_loss: bad shape");
+    if (!opts)   // the plain kernels, as vitseg_ce_loss launches them
+        return launch_ce_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S,
+                              (hipStream_t)stream, loss_scale);
+    return launch_ce_loss_opts(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S, *opts,
+                               (hipStream_t)stream, loss_scale);
+}
+
 int vitseg_profile_enable(int on) {
     profiler().clear();
     profiler().on = on != 0;

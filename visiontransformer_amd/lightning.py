@@ -14,18 +14,26 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .model import ViTSegmentationModel
+from .model import ViTSegmentationModel, check_ce_options
 
 
 class LightningViTModel(nn.Module):
     def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, *,
-                 interpolate_pos_encoding: bool = False, **kw):
+                 interpolate_pos_encoding: bool = False, ignore_index=None, class_weight=None,
+                 label_smoothing: float = 0.0, **kw):
         """`interpolate_pos_encoding`: inputs of other (square, multiple-of-P) sizes than `image_size` run with the
-        position table resampled to their grid (ViTSegmentationModel.forward); targets are resized to the input's size."""
+        position table resampled to their grid (ViTSegmentationModel.forward); targets are resized to the input's size.
+        `ignore_index`, `class_weight`, `label_smoothing`: the arguments of the reference's `nn.CrossEntropyLoss()`
+        (classes.py:268) it leaves at their defaults -- a void label whose pixels do not count, one weight per class,
+        smoothed targets (ViTSegmentationModel.ce_loss); used by the training and the validation step alike."""
         super().__init__()
         self.model = ViTSegmentationModel(num_classes, patch_size, hidden_size, num_hidden_layers,
                                           num_attention_heads, **kw)
         self.interpolate_pos_encoding = bool(interpolate_pos_encoding)
+        check_ce_options(num_classes, ignore_index, class_weight, label_smoothing)   # ValueError here, not at the first step
+        self.ignore_index, self.label_smoothing = ignore_index, label_smoothing
+        # a tuple: one device copy, found again by value on every step
+        self.class_weight = None if class_weight is None else tuple(float(v) for v in class_weight)
         self.logged = {}
 
     def forward(self, x):
@@ -49,11 +57,16 @@ class LightningViTModel(nn.Module):
         S = self.model.cfg.image_size  # the reference hard-codes (224, 224) = its image_size (classes.py:278)
         if self.interpolate_pos_encoding:
             S = int(x.shape[-1])       # ... which is also its input size: with other input sizes, the input's
-        # uint8 class indices: what the fused CE kernels read (a quarter of the int64 bytes); C <= 32 in training
-        y = self._resize_target(y.to(x.device, non_blocking=True), size=(S, S), dtype=torch.uint8)
+        # uint8 class indices: what the fused CE kernels read (a quarter of the int64 bytes); C <= 32 in training.  An
+        # ignored label that a byte cannot hold (torch's -100) keeps the targets int64
+        wide = self.ignore_index is not None and not 0 <= self.ignore_index <= 255
+        y = self._resize_target(y.to(x.device, non_blocking=True), size=(S, S), dtype=torch.long if wide else torch.uint8)
+        opts = {}
+        if self.ignore_index is not None or self.class_weight is not None or self.label_smoothing != 0:
+            opts = dict(ignore_index=self.ignore_index, class_weight=self.class_weight, label_smoothing=self.label_smoothing)
         if self.interpolate_pos_encoding:
-            return self.model.ce_loss(x, y, grad_scale=grad_scale, interpolate_pos_encoding=True)
-        return self.model.ce_loss(x, y, grad_scale=grad_scale)
+            return self.model.ce_loss(x, y, grad_scale=grad_scale, interpolate_pos_encoding=True, **opts)
+        return self.model.ce_loss(x, y, grad_scale=grad_scale, **opts)
 
     # `logged` holds DEVICE scalars: reading one (float(...)) is the only host sync, and only the caller decides when
     def training_step(self, batch, batch_idx, grad_scale=None):

@@ -9,6 +9,7 @@ nn.Parameter), a cached workspace tensor and the output tensor.
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 from collections import OrderedDict
 from typing import Dict, Optional
 
@@ -25,6 +26,39 @@ _PRECISION = {"fp32": _lib.F32, "f32": _lib.F32, "float32": _lib.F32, "bf16": _l
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def check_ce_options(num_classes: int, ignore_index=None, class_weight=None, label_smoothing: float = 0.0):
+    """Host-side validation of `ce_loss`'s options (the kernels cannot raise).  Returns None when all three are at their
+    defaults -- the caller then takes the plain calls -- else (ignore_index or None, fp32 CPU tensor [C] or None, eps).
+    ValueError: an `ignore_index` that is not an integer (of int64 range), a `class_weight` that is not `num_classes`
+    finite values >= 0, a `label_smoothing` outside [0, 1]."""
+    if ignore_index is not None:
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, numbers.Integral):
+            raise ValueError(f"ignore_index must be an integer or None, got {ignore_index!r}")
+        ignore_index = int(ignore_index)
+        if not -2 ** 63 <= ignore_index < 2 ** 63:
+            raise ValueError(f"ignore_index {ignore_index} does not fit int64")
+    try:
+        eps = float(label_smoothing)
+    except (TypeError, ValueError):
+        raise ValueError(f"label_smoothing must be a number in [0, 1], got {label_smoothing!r}") from None
+    if not 0.0 <= eps <= 1.0:   # (a NaN fails both comparisons)
+        raise ValueError(f"label_smoothing must lie in [0, 1], got {label_smoothing!r}")
+    w = None
+    if class_weight is not None:
+        try:
+            w = torch.as_tensor(class_weight).detach().to("cpu", torch.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"class_weight must be a sequence or tensor of {num_classes} numbers") from None
+        if w.dim() != 1 or w.numel() != num_classes:
+            raise ValueError(f"class_weight must hold one weight per class ({num_classes}), got shape {tuple(w.shape)}")
+        w = w.to(torch.float32)   # what the kernels read: a value beyond the fp32 range is not finite there
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError("class_weight must be finite and >= 0")
+    if ignore_index is None and w is None and eps == 0.0:
+        return None
+    return ignore_index, w, eps
 
 
 class _LogitsFn(torch.autograd.Function):
@@ -51,11 +85,11 @@ class _CELossFn(torch.autograd.Function):
     steal (the model keeps a reference to its persistent buffer)."""
 
     @staticmethod
-    def forward(ctx, arena, model, x, target, grad_scale, interp=False):
+    def forward(ctx, arena, model, x, target, grad_scale, interp=False, ce_opts=None):
         drop = model._next_dropout()
         model._forward_train(x, want_logits=False, drop=drop, interp=interp)
         grads, loss = model._backward(x, target=target, drop=drop, loss_scale=1.0 if grad_scale is None else grad_scale,
-                                      interp=interp)
+                                      interp=interp, ce_opts=ce_opts)
         ctx.grads, ctx.model = grads, model
         ctx.prescaled = grad_scale is not None
         return loss
@@ -65,7 +99,7 @@ class _CELossFn(torch.autograd.Function):
         grads, ctx.grads = ctx.grads, None
         if not ctx.prescaled:
             grads.mul_(dloss)   # in place: the buffer is ours until it is delivered
-        return ctx.model._deliver_grad(grads), None, None, None, None, None
+        return ctx.model._deliver_grad(grads), None, None, None, None, None, None
 
 
 class ViTSegmentationModel(nn.Module):
@@ -359,7 +393,8 @@ class ViTSegmentationModel(nn.Module):
 
     def _backward(self, x: torch.Tensor, target: Optional[torch.Tensor] = None,
                   grad_logits: Optional[torch.Tensor] = None, drop=(0.0, 0), loss_scale: float = 1.0,
-                  interp: bool = False):
+                  interp: bool = False, ce_opts=None):
+        """`ce_opts`: a `_lib.CCEOptions` from `_ce_options` (fused CE only), or None for the plain calls."""
         x = x.to(torch.float32).contiguous()
         B, S = x.shape[0], self._size_in(x, interp)
         ws = self._train_workspace(B, S)
@@ -373,7 +408,9 @@ class ViTSegmentationModel(nn.Module):
                     grads.data_ptr(), _ptr(loss), float(loss_scale), handles, ws.data_ptr(), ws.numel(),
                     torch.cuda.current_stream().cuda_stream)
             cfg = C.byref(_lib.CConfig.from_config(self.cfg))
-            if S == self.cfg.image_size:
+            if ce_opts is not None:
+                _lib.check(_lib.ce_opts_symbol("vitseg_backward_opts")(cfg, S, *args, C.byref(ce_opts)))
+            elif S == self.cfg.image_size:
                 _lib.check(_lib.lib().vitseg_backward(cfg, *args))
             else:
                 _lib.check(_lib.at_symbol("vitseg_backward_at")(cfg, S, *args))
@@ -488,12 +525,59 @@ class ViTSegmentationModel(nn.Module):
         m = self.predict_mask(tiles)
         return m.reshape(B, ty, tx, S, S).permute(0, 1, 3, 2, 4).reshape(B, H, W).contiguous()
 
+    _CE_CACHE_ENTRIES = 8   # device weight vectors / scratch buffers kept per model, least recently used first out
+
+    def _ce_cached(self, kind: str, key, make):
+        """The device tensor cached under `key`, made by `make()` on a miss; each kind keeps the `_CE_CACHE_ENTRIES`
+        most recently used."""
+        cache = self.__dict__.setdefault("_ce_opt_cache", {}).setdefault(kind, OrderedDict())
+        t = cache.get(key)
+        if t is None:
+            t = cache[key] = make()
+            while len(cache) > self._CE_CACHE_ENTRIES:
+                cache.popitem(last=False)
+        else:
+            cache.move_to_end(key)
+        return t
+
+    def _ce_options(self, B: int, S: int, ignore_index, class_weight, label_smoothing):
+        """The `_lib.CCEOptions` of a `ce_loss` call, or None when all three options are at their defaults (the plain
+        calls).  The options are validated on the host on every call (C <= 255 numbers).  The device copy of the weights
+        is cached under the fp32 VALUES the kernels are to read, never under the identity of what was passed: another
+        tensor at a recycled address, or one edited in place, has other values and so another entry.  The small scratch
+        of the count pass is cached per (batch, size).  Both caches are bounded; the returned struct holds its tensors."""
+        checked = check_ce_options(self.cfg.num_classes, ignore_index, class_weight, label_smoothing)
+        if checked is None:
+            return None
+        ii, w, eps = checked
+        dev = self.arena.device
+        wdev = None
+        if w is not None:
+            wdev = self._ce_cached("weight", (w.numpy().tobytes(), dev), lambda: w.to(dev).contiguous())
+        nbytes = int(_lib.ce_opts_symbol("vitseg_ce_options_scratch_bytes")(B, S))
+        scratch = self._ce_cached("scratch", (B, S, dev), lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+        opts = _lib.CCEOptions(int(ii is not None), 0, 0 if ii is None else ii, _ptr(wdev), eps, scratch.data_ptr(),
+                               scratch.numel())
+        opts._tensors = (wdev, scratch)   # the struct holds raw addresses: an eviction must not free them under it
+        return opts
+
     def ce_loss(self, x: torch.Tensor, target: torch.Tensor, grad_scale: Optional[float] = None,
-                interpolate_pos_encoding: bool = False) -> torch.Tensor:
-        """`nn.CrossEntropyLoss()(self(x), target)` (model/CE/classes.py:268,280) as a device scalar, without
-        materialising the [B, C, S, S] logits: forward to the low-res map, then the fused upsample+CE kernel.
+                interpolate_pos_encoding: bool = False, ignore_index: Optional[int] = None, class_weight=None,
+                label_smoothing: float = 0.0) -> torch.Tensor:
+        """`nn.CrossEntropyLoss(weight=class_weight, ignore_index=ignore_index, label_smoothing=label_smoothing)(self(x),
+        target)` (model/CE/classes.py:268,280 with the defaults) as a device scalar, without materialising the
+        [B, C, S, S] logits: forward to the low-res map, then the fused upsample+CE kernel.
         `target`: class indices [B, S, S], torch.long (reference) or torch.uint8, on the model's device.  Labels must lie
-        in [0, C): `ignore_index` is not supported, and any other label (255, -100, C) makes the loss NaN.
+        in [0, C) or equal `ignore_index`; any other label (255, -100, C without a matching `ignore_index`) makes the loss
+        NaN.
+        `ignore_index` (None = no label is ignored; 255 for void / border pixels of uint8 masks, -100 for torch's default):
+        such pixels add nothing to the loss, get a zero gradient, and leave the mean's denominator.  `class_weight`: one
+        weight >= 0 per class (sequence or tensor); the mean divides by the summed weights of the kept pixels, as torch
+        does.  The weights are checked on the host on every call and their device copy is found again by value, so a
+        new or edited tensor is honoured; a tensor that lives on the device is read back for that (one small
+        synchronising copy per call): in a training loop pass a sequence or a CPU tensor.  `label_smoothing` in [0, 1].  When every pixel is ignored (or every kept pixel has weight 0) the loss is
+        NaN, torch's 0 / 0.  Invalid options raise ValueError on the host.  With all three at their defaults the call is
+        the plain one (the same kernels, the same bits).
         `grad_scale` (optional): the gradient `loss.backward()` deposits is grad_scale * d loss / d params, folded into
         the CE gradient inside the kernel (e.g. 1 / accumulate_grad_batches); call `.backward()` on the returned loss
         itself then -- an upstream factor is ignored in this mode.  `interpolate_pos_encoding`: as in `forward`; the
@@ -504,17 +588,22 @@ class ViTSegmentationModel(nn.Module):
         S, B = self._size_in(x, interp), x.shape[0]
         if tuple(target.shape) != (B, S, S) or target.dtype not in (torch.int64, torch.uint8):
             raise ValueError(f"target must be int64/uint8 [B, {S}, {S}], got {target.dtype} {tuple(target.shape)}")
+        opts = self._ce_options(B, S, ignore_index, class_weight, label_smoothing)
         if self._needs_grad():
-            return _CELossFn.apply(self.arena, self, x, target.to(self.arena.device).contiguous(), grad_scale, interp)
+            return _CELossFn.apply(self.arena, self, x, target.to(self.arena.device).contiguous(), grad_scale, interp, opts)
         with torch.no_grad():
             _, _ = self._run(x, False, True, interp=interp)  # fills the low-res logits (mask output is a by-product)
             low = self.debug_buffer(B, _lib.BUF_LOWRES, S)
             target = target.to(self.arena.device).contiguous()
             scratch = torch.empty(_lib.lib().vitseg_ce_scratch_bytes(B, S), dtype=torch.uint8, device=low.device)
             loss = torch.empty((), dtype=torch.float32, device=low.device)
-            _lib.check(_lib.lib().vitseg_ce_loss(low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8),
-                                                 None, scratch.data_ptr(), loss.data_ptr(), B, self.cfg.num_classes,
-                                                 S // self.cfg.patch_size, S, torch.cuda.current_stream().cuda_stream))
+            args = (low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8), None, scratch.data_ptr(),
+                    loss.data_ptr(), B, self.cfg.num_classes, S // self.cfg.patch_size, S)
+            stream = torch.cuda.current_stream().cuda_stream
+            if opts is None:
+                _lib.check(_lib.lib().vitseg_ce_loss(*args, stream))
+            else:
+                _lib.check(_lib.ce_opts_symbol("vitseg_ce_loss_opts")(*args, C.byref(opts), 1.0, stream))
         return loss
 
     @torch.no_grad()

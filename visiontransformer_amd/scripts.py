@@ -42,6 +42,30 @@ def get_latest_checkpoint(version_n: int, base_path: str) -> Optional[str]:
     return path
 
 
+def add_ce_loss_arguments(ap) -> None:
+    """The loss options of the CE training scripts: the arguments of nn.CrossEntropyLoss the reference leaves at their
+    defaults (model/CE/classes.py:268)."""
+    ap.add_argument("--ignore-index", type=int, default=None,
+                    help="label whose pixels do not count in the loss (255 for void / border pixels, -100 for torch's default)")
+    ap.add_argument("--class-weights", default=None, help="comma-separated weight per class: w0,w1,...")
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
+
+
+def ce_loss_options(a) -> dict:
+    """Keyword arguments for LightningViTModel from the flags of `add_ce_loss_arguments` (empty: the plain loss)."""
+    kw = {}
+    if a.ignore_index is not None:
+        kw["ignore_index"] = a.ignore_index
+    if a.class_weights:
+        try:
+            kw["class_weight"] = [float(v) for v in a.class_weights.split(",")]
+        except ValueError:
+            raise ValueError(f"--class-weights expects comma-separated numbers, got {a.class_weights!r}") from None
+    if a.label_smoothing:
+        kw["label_smoothing"] = a.label_smoothing
+    return kw
+
+
 def ce_batches(cfg, n_images: int, batch_size: int, data: Optional[str] = None, seed: int = 0, first: int = 0):
     """[(images [b,3,S,S] float, masks [b,256,256] long)]: StructuralDamageDataset items (model/CE/classes.py:60-89)."""
     if data:
