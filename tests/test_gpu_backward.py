@@ -221,46 +221,50 @@ def test_gradient_buffer_is_handed_over_not_cloned():
     assert (m.arena.grad - g0).abs().max().item() <= 2e-6 * max(1.0, g0.abs().max().item())
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "fp32_large"])
 def test_overlapped_bucket_allreduce_inside_backward(precision):
     """Section 8(e): vitseg_backward records one event per gradient bucket; the host queues one RCCL all-reduce
     per bucket behind its event on a side stream.  Run on a one-rank RCCL group (sum over one rank = identity):
-    gradients and loss must equal the plain backward bit for bit, and the bucket events must fire in order."""
+    gradients and loss must equal the plain backward bit for bit, and the bucket events must fire in order.
+    fp32_large: `no_small` held over forward and backward -- the fixture is small enough for the small-batch route, so
+    without the switch the large fp32 route's event placement would go untested."""
     import os
     import torch.distributed as dist
     from visiontransformer_amd.dist import sync_grads
+    large, precision = precision == "fp32_large", precision.split("_")[0]
     g = Golden("base16w_l2_224_c2_train")
     lm = _build(g, precision=precision).train()
-    m = lm.model
-    m.dropout = 0.0
-    x, y = g.images().to(DEV), lm._resize_target(g.targets().to(DEV), (224, 224))
+    with _lib.option("no_small", int(large)):
+        m = lm.model
+        m.dropout = 0.0
+        x, y = g.images().to(DEV), lm._resize_target(g.targets().to(DEV), (224, 224))
 
-    def run():
-        m.arena.grad = None
-        loss = m.ce_loss(x, y)
-        loss.backward()
-        return loss.detach().clone(), m.arena.grad.clone()
+        def run():
+            m.arena.grad = None
+            loss = m.ce_loss(x, y)
+            loss.backward()
+            return loss.detach().clone(), m.arena.grad.clone()
 
-    m.grad_sync = "after"
-    l0, g0 = run()
-    assert not m._grads_reduced
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1")
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device(DEV))
-    try:
-        m.grad_sync = "force"
-        m.grad_bucket_mb = 8.0
-        l1, g1 = run()
-        assert m._grads_reduced
-        reducer, events, _, _ = m._buckets
-        assert len(reducer.groups) > 1
-        torch.cuda.synchronize()
-        assert all(e.query() for e in events)
-        sync_grads(m)                      # consumes the flag, must not reduce again
+        m.grad_sync = "after"
+        l0, g0 = run()
         assert not m._grads_reduced
-        assert torch.equal(l0, l1) and torch.equal(g0, g1)
-    finally:
-        dist.destroy_process_group()
-        m.grad_sync = "overlap"
+        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1")
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device(DEV))
+        try:
+            m.grad_sync = "force"
+            m.grad_bucket_mb = 8.0
+            l1, g1 = run()
+            assert m._grads_reduced
+            reducer, events, _, _ = m._buckets
+            assert len(reducer.groups) > 1
+            torch.cuda.synchronize()
+            assert all(e.query() for e in events)
+            sync_grads(m)                      # consumes the flag, must not reduce again
+            assert not m._grads_reduced
+            assert torch.equal(l0, l1) and torch.equal(g0, g1)
+        finally:
+            dist.destroy_process_group()
+            m.grad_sync = "overlap"
 
 
 def test_trainer_writes_lightning_style_checkpoints(tmp_path):

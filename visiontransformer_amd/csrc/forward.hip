@@ -131,7 +131,7 @@ int walk_large(const Fwd& f) {
             g.thin_capacity = f.scratch_floats;
         }
         ProfScope ps(kind, 2.0 * g.M * g.N * g.K, st);
-        if (f.fc1_train && epi == EPI_GELU) return launch_gemm_bf16_train(g, EPI_GELU, 0, nullptr, st);
+        if (f.fc1_train && epi == EPI_GELU) return launch_gemm_bf16_train(g, EPI_GELU, st);
         return f.h16 ? launch_gemm_bf16(g, A_PLAIN, epi, st, f.h16 == 2) : launch_gemm_f32(g, A_PLAIN, epi, st, f.x3);
     };
     auto lnorm = [&](const float* X, int w, int b, int l, void* H, int rows) {

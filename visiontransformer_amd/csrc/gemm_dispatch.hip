@@ -230,24 +230,14 @@ int launch_wgrad_bf16_tt(GemmArgs a, float* scratch, hipStream_t s) {
     return sliced(a, splits, scratch, s, [&](const GemmArgs& g) { return launch_gemm_tt(g, s); });
 }
 
-// bf16 training GEMMs (all N-form: dgrad multiplies by a transposed bf16 copy of the weight, wgrad by
-// transposed copies of dY and X whose reduction length is zero-padded to a multiple of 64).
-//   out_f32 = 0: C bf16, epi EPI_BIAS (plain dgrad), EPI_GELU (forward, `aux` = bf16 pre-activation) or
-//                EPI_DGELU (R = bf16 pre-activation);
-//   out_f32 = 1: C fp32, EPI_BIAS, optional split-K into `scratch` (weight gradients).
-int launch_gemm_bf16_train(GemmArgs a, int epi, int out_f32, float* scratch, hipStream_t s) {
+// bf16 training GEMMs with a bf16 output (N-form: dgrad multiplies by a transposed bf16 copy of the weight):
+// epi EPI_BIAS (plain dgrad), EPI_GELU (forward, `aux` = bf16 pre-activation) or EPI_DGELU (R = bf16 pre-activation).
+// Same tile selection as inference (256x256 for wide outputs, 256x128 for long K, else 128x128).
+int launch_gemm_bf16_train(const GemmArgs& a, int epi, hipStream_t s) {
     VITSEG_CHECK_ARG(a.M > 0 && a.N > 0 && a.K > 0 && a.K % 64 == 0, VITSEG_ESHAPE, "gemm_bf16_train: K=%d %% 64", a.K);
     VITSEG_CHECK_ARG(a.N % 4 == 0 && a.ldc % 4 == 0 && a.lda % 8 == 0, VITSEG_ESHAPE, "gemm_bf16_train: alignment");
-    if (!out_f32) {  // same tile selection as inference (256x256 for wide outputs, 256x128 for long K, else 128x128)
-        if (epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_DGELU) return launch_gemm_bf16(a, A_PLAIN, epi, s, false);
-    } else if (epi == EPI_BIAS) {
-        const int splits = scratch ? wgrad_splits(a.M, a.N, a.K, 64) : 1;
-        VITSEG_CHECK_ARG(splits <= 1 || a.ldc == a.N, VITSEG_EINVAL, "gemm_bf16_train: split-K needs a dense output");
-        return sliced(a, splits, scratch, s, [&](const GemmArgs& g) {
-            return launch_gemm_tile(GT_BF16, true, A_PLAIN, EPI_BIAS, 0, g, s, "gemm_bf16_train");
-        });
-    }
-    set_error("gemm_bf16_train: unsupported epilogue %d / out_f32 %d", epi, out_f32);
+    if (epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_DGELU) return launch_gemm_bf16(a, A_PLAIN, epi, s, false);
+    set_error("gemm_bf16_train: unsupported epilogue %d", epi);
     return VITSEG_EINVAL;
 }
 

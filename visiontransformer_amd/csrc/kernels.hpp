@@ -73,7 +73,7 @@ int launch_gemm_f32_bwd(const GemmArgs& a, int amode, int ta, int tb, int epi, h
 size_t wgrad_scratch_floats(int M, int N, int K);
 int launch_wgrad_f32(GemmArgs a, float* scratch, hipStream_t s);
 int launch_wgrad_bf16_tt(GemmArgs a, float* scratch, hipStream_t s);
-int launch_gemm_bf16_train(GemmArgs a, int epi, int out_f32, float* scratch, hipStream_t s);
+int launch_gemm_bf16_train(const GemmArgs& a, int epi, hipStream_t s);   // bf16 output: dgrad, fc1 + saved pre-activation
 size_t wgrad_bf16_scratch_floats(int M, int N, int K);
 int wgrad_bf16_splits(int M, int N, int K, bool p8);   // splitk.hip: the slice count of the size query AND of the launch
 int gemm_slices(int path, int M, int N, int K);        // vitseg_dbg_gemm_slices: the router's slice count per sliced path
