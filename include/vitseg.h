@@ -540,6 +540,59 @@ int vitseg_op_layernorm_bwd_f32_small(const float* x, const float* w, const floa
                                       int D, float eps, float* br_out, float* br_dbias, float dropout_p, uint32_t dropout_seed,
                                       uint32_t dropout_stream, void* stream);
 
+/* ---- helper kernels: the launches of the embeddings, the seg head and the training step around the encoder layers, one
+ * entry per production call site, on caller-owned buffers (csrc/op_helpers.hip; tests/test_gpu_helpers.py).  Row layout as
+ * everywhere: patch rows b * Np + t first, the CLS rows batch * Np + b after them.  Each entry builds the arguments of its
+ * call site and makes that site's one launcher call.
+ * patch_embed: X[batch * (g*g + 1), D] = patch projection of img [batch, Cin, g*P, g*P] (weights Wp [D, Cin*P*P]: fp32, or the
+ * vitseg_cast_params_split form for x3 = 2) + bp + pos[1 + t], and the CLS rows cls + pos[0]; x3 as vitseg_op_linear_f32_thin
+ * (0 fp32, 1 split operands, 2 pre-split weights); no dropout. */
+int vitseg_op_patch_embed_f32(const float* img, const void* Wp, const float* bp, const float* pos, const float* cls, float* X,
+                              int batch, int Cin, int P, int g, int D, int x3, void* stream);
+/* 3x3 convolution, zero padding 1, as an implicit GEMM over the token-major map H [batch * g*g, channels]:
+ * C [batch * g*g, N] = H (*) W, W [N, 9 * channels] with k = (ky, kx, channel).  relu != 0: + bias, ReLU (seg_head.0 forward;
+ * x3 0 / 1 / 2 as above); relu == 0: the input-gradient form of the fp32 training step (bias may be NULL; x3 = 0). */
+int vitseg_op_conv3x3_f32(const float* H, const void* W, const float* bias, float* C, int batch, int g, int channels, int N,
+                          int relu, int x3, void* stream);
+/* the same with 16-bit H and W (bf16, or IEEE half when f16 != 0) and an fp32 C; zeros: >= 128 zero bytes, the source of the
+ * padding taps.  channels must be a multiple of 64.  relu == 0: the bf16 training step's input-gradient form. */
+int vitseg_op_conv3x3_h16(const void* H, const void* W, const float* bias, float* C, const void* zeros, int batch, int g,
+                          int channels, int N, int relu, int f16, void* stream);
+/* seg_head.2: Z [batch, C, Np] = F [batch * Np, 256] . W2 [C, 256]^T + b2 */
+int vitseg_op_head1x1(const float* F, const float* W2, const float* b2, float* Z, int batch, int num_patches, int C,
+                      void* stream);
+/* ... and its backward with the ReLU's: dFpre = (F > 0) * dZ . W2, dW2 = dZ^T F, db2 = sum dZ.  C <= 32 (VITSEG_ESHAPE). */
+size_t vitseg_op_head1x1_bwd_scratch_floats(int batch, int num_patches, int C);
+int vitseg_op_head1x1_bwd(const float* dZ, const float* F, const float* W2, float* dFpre, float* dW2, float* db2,
+                          float* scratch, int batch, int num_patches, int C, void* stream);
+/* out[N] = column sums of X [M, N] (leading dimension ld, a multiple of 4; fp32 or bf16), deterministic; scratch:
+ * vitseg_op_colsum_scratch_floats(M, N) floats */
+int vitseg_op_colsum(const void* X, int x_is_bf16, float* out, float* scratch, int M, int N, int ld, void* stream);
+/* dpos [Np + 1, D] and dcls [D] from dX [batch * (Np + 1), D] */
+int vitseg_op_embed_bwd(const float* dX, float* dpos, float* dcls, int batch, int num_patches, int D, void* stream);
+/* im2col rows of the two convolutions (operands of their weight gradients): T [batch * g*g, 9 * D] of the token-major map H
+ * (fp32 out of fp32 or bf16 H; bf16 out of bf16 H, D % 8 == 0), T [batch * (S/P)^2, Cin * P * P] of the NCHW image (fp32 or
+ * rounded to bf16) */
+int vitseg_op_im2col3x3(const void* H, int h_is_bf16, float* T, int batch, int g, int D, void* stream);
+int vitseg_op_im2col3x3_bf16(const void* H, void* T, int batch, int g, int D, void* stream);
+int vitseg_op_im2col_patch(const float* img, float* T, int batch, int Cin, int S, int P, void* stream);
+int vitseg_op_im2col_patch_bf16(const float* img, void* T, int batch, int Cin, int S, int P, void* stream);
+/* Wd [D, 9, 256] = W0 [256, 9, D] with the taps flipped: the weight of the input-gradient convolution of seg_head.0 */
+int vitseg_op_conv_dgrad_weight(const float* W0, float* Wd, int D, void* stream);
+/* bf16 out [C, Rpad] = in [R, C]^T (leading dimension ldin), zeros in columns R .. Rpad - 1 */
+int vitseg_op_transpose_bf16(const void* in, void* out, int R, int C, int ldin, int Rpad, void* stream);
+/* four bf16 matrices [R[k], C[k]] per layer, at elements src0[k] + layer * src_stride of arena, transposed into
+ * out[layer][k] (dense, one after the other) */
+int vitseg_op_transpose_layers_bf16(const void* arena, void* out, const size_t src0[4], const int R[4], const int C[4],
+                                    size_t src_stride, int layers, void* stream);
+/* dst = keep ? src * 1 / (1 - p) : 0 on [rows, cols] (cols % 4 == 0), the hidden-dropout mask of csrc/common.hpp on the
+ * given stream id; dst fp32 (may be src) or bf16; 0 < dropout_p < 1 */
+int vitseg_op_dropout_rows(const float* src, void* dst, int dst_bf16, int rows, int cols, float dropout_p, uint32_t dropout_seed,
+                           uint32_t dropout_stream, void* stream);
+/* vitseg_op_layernorm_f32 with a 16-bit output: out_fmt 1 = bf16, 2 = IEEE half */
+int vitseg_op_layernorm_h16(const float* x, const float* w, const float* b, void* y, int rows, int D, float eps, int out_fmt,
+                            void* stream);
+
 /* ---- measurement hooks (bench.py's roofline object) ----
  * While enabled, vitseg_forward brackets every kernel launch of the hot path with a pair of
  * hipEvents on the launch stream; vitseg_forward_train / vitseg_backward bracket the GEMMs and

@@ -53,7 +53,17 @@ SDF_EXPORTS = ["vitseg_sdf_scratch_bytes", "vitseg_sdf"]
 SPLITK_EXPORTS = ["vitseg_op_linear_f32_thin", "vitseg_op_wgrad_f32_scratch_floats", "vitseg_op_wgrad_f32", "vitseg_dbg_gemm_slices"]
 # the fused cross-entropy with ignore_index / class weights / label smoothing (model.ce_loss): bound on first use, the same way
 CE_OPTS_EXPORTS = ["vitseg_ce_options_scratch_bytes", "vitseg_ce_loss_opts", "vitseg_backward_opts"]
-EXPORTS += AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS   # every symbol include/vitseg.h declares
+# the embedding, seg-head and training helper kernels, one entry per production launch (csrc/op_helpers.hip,
+# tests/test_gpu_helpers.py): bound on first use, the same way
+HELPER_EXPORTS = [
+    "vitseg_op_patch_embed_f32", "vitseg_op_conv3x3_f32", "vitseg_op_conv3x3_h16", "vitseg_op_head1x1",
+    "vitseg_op_head1x1_bwd_scratch_floats", "vitseg_op_head1x1_bwd", "vitseg_op_colsum", "vitseg_op_embed_bwd",
+    "vitseg_op_im2col3x3", "vitseg_op_im2col3x3_bf16", "vitseg_op_im2col_patch", "vitseg_op_im2col_patch_bf16",
+    "vitseg_op_conv_dgrad_weight", "vitseg_op_transpose_bf16", "vitseg_op_transpose_layers_bf16", "vitseg_op_dropout_rows",
+    "vitseg_op_layernorm_h16",
+]
+_LATE_EXPORTS = AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS
+EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
 VERSION = 110   # include/vitseg.h VITSEG_VERSION this binding was written against
@@ -173,7 +183,7 @@ def lib() -> C.CDLL:
         l.vitseg_profile_enable.argtypes = [i32]
         l.vitseg_profile_collect.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
         for name in EXPORTS:
-            if name not in AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS:
+            if name not in _LATE_EXPORTS:
                 getattr(l, name)  # raises AttributeError if the build is stale
         for name, args in _at_argtypes(vp, sz, i32, pcfg, psz).items():
             fn = getattr(l, name, None)
@@ -198,6 +208,10 @@ def lib() -> C.CDLL:
             for name, args in _ce_opts_argtypes(vp, sz, i32, pcfg).items():
                 getattr(l, name).argtypes = args
             l.vitseg_ce_options_scratch_bytes.restype = sz
+        if getattr(l, "vitseg_op_patch_embed_f32", None) is not None:
+            for name, args in _helper_argtypes(vp, sz, i32).items():
+                getattr(l, name).argtypes = args
+            l.vitseg_op_head1x1_bwd_scratch_floats.restype = sz
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -227,6 +241,38 @@ def _ce_opts_argtypes(vp, sz, i32, pcfg) -> dict:
         "vitseg_backward_opts": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp,
                                  popt],
     }
+
+
+def _helper_argtypes(vp, sz, i32) -> dict:
+    f32, u32 = C.c_float, C.c_uint32
+    return {
+        "vitseg_op_patch_embed_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+        "vitseg_op_conv3x3_f32": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+        "vitseg_op_conv3x3_h16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+        "vitseg_op_head1x1": [vp, vp, vp, vp, i32, i32, i32, vp],
+        "vitseg_op_head1x1_bwd_scratch_floats": [i32, i32, i32],
+        "vitseg_op_head1x1_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+        "vitseg_op_colsum": [vp, i32, vp, vp, i32, i32, i32, vp],
+        "vitseg_op_embed_bwd": [vp, vp, vp, i32, i32, i32, vp],
+        "vitseg_op_im2col3x3": [vp, i32, vp, i32, i32, i32, vp],
+        "vitseg_op_im2col3x3_bf16": [vp, vp, i32, i32, i32, vp],
+        "vitseg_op_im2col_patch": [vp, vp, i32, i32, i32, i32, vp],
+        "vitseg_op_im2col_patch_bf16": [vp, vp, i32, i32, i32, i32, vp],
+        "vitseg_op_conv_dgrad_weight": [vp, vp, i32, vp],
+        "vitseg_op_transpose_bf16": [vp, vp, i32, i32, i32, i32, vp],
+        "vitseg_op_transpose_layers_bf16": [vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int), sz, i32, vp],
+        "vitseg_op_dropout_rows": [vp, vp, i32, i32, i32, f32, u32, u32, vp],
+        "vitseg_op_layernorm_h16": [vp, vp, vp, vp, i32, i32, f32, i32, vp],
+    }
+
+
+def helper_symbol(name: str):
+    """One of HELPER_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the helper-kernel entry points): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
 
 
 def ce_opts_symbol(name: str):
