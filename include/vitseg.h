@@ -593,6 +593,52 @@ int vitseg_op_dropout_rows(const float* src, void* dst, int dst_bf16, int rows, 
 int vitseg_op_layernorm_h16(const float* x, const float* w, const float* b, void* y, int rows, int D, float eps, int out_fmt,
                             void* stream);
 
+/* ---- sliding-window inference: overlapping windows blended on the device ----
+ * An image [H, W] larger than the model's input is covered by S x S windows `stride` apart; every window is one tile of
+ * a batch through the model, and the tiles' low-resolution head outputs are blended into the full-size result.  The
+ * reference has no counterpart: its scripts resize every image to the model's square (testViTModel.py:92-97), then
+ * forward and sigmoid -> argmax (:122-126).
+ *
+ * Window grid of one axis (host arithmetic, no GPU touched):
+ *   count = 1 + ceil((extent - S) / stride);  origin_i = min(i * stride, extent - S)   (the last window ends at the edge)
+ * vitseg_window_count returns the count or a negative vitseg_status; vitseg_window_origins writes `count` origins.
+ * VITSEG_ESHAPE (with a vitseg_last_error text): extent < S, stride < 1, stride > S, extent > 16384.
+ * The tiles of a batch of n images are numbered image-major, then window row, then window column:
+ *   tile = (image * ny + window_row) * nx + window_column.
+ *
+ * vitseg_window_gather: tiles [first, first + count) of that numbering as fp32 NCHW [count, 3, S, S].  src: fp32 NCHW
+ * [n, 3, H, W] (src_is_u8 = 0: a plain copy) or uint8 HWC [n, H, W, 3] (src_is_u8 = 1: value / 255 with one correctly
+ * rounded division, ToTensor, as vitseg_preprocess_u8 ends).  origins_y [ny] / origins_x [nx]: device int32 tables; no
+ * alignment is assumed of the origins or of W.
+ *
+ * vitseg_forward_lowres: the forward walk of vitseg_forward_at (same routes, same workspace, same bits) that stops
+ * before the upsample and leaves the head output in lowres, fp32 [batch, C, g, g] (g = image_size_in / P) -- the bytes
+ * of VITSEG_BUF_LOWRES after vitseg_forward_at on the same input.
+ *
+ * vitseg_window_blend: lowres fp32 [n * ny * nx, C, g, g] (tile numbering as above) -> logits fp32 [n, C, H, W] and / or
+ * mask uint8 [n, H, W] (either may be NULL; both NULL: VITSEG_EINVAL).  weights: device fp32 [S], all entries > 0; the
+ * weight of a tile at its local pixel (ly, lx) is wt = weights[ly] * weights[lx].  For a pixel, a class and a covering
+ * tile (origin <= coordinate < origin + S on both axes), v = the bilinear value at the tile-local coordinate with the
+ * decoder tail's arithmetic (scale g / S, taps src = max(scale * (d + 0.5) - 0.5, 0), row = fma(a, wx0, b * wx1),
+ * v = fma(top, wy0, bot * wy1)).  Then
+ *   exactly one covering tile:  result = v;
+ *   otherwise, over the covering tiles in increasing tile number from acc = 0, ws = 0:
+ *     acc = fma(wt, v, acc);  ws = ws + wt;    result = acc / ws   (IEEE division).
+ * Every operation is a single correctly rounded fp32 one, so a CPU restatement holds bit for bit (tests/window_ref.py).
+ * mask = argmax_c sigmoid(result_c), the sigmoid as ATen computes it for fp32, first maximal index.
+ * VITSEG_ESHAPE: C outside 1..255, S outside 1..4096, H or W outside S..16384, n outside 1..65535, g outside 1..S.
+ * No global atomics and no scratch; every output element is written exactly once. */
+int vitseg_window_count(int extent, int S, int stride);
+int vitseg_window_origins(int extent, int S, int stride, int32_t* origins);
+int vitseg_window_gather(const void* src, int src_is_u8, int n, int H, int W, int S, const int32_t* origins_y, int ny,
+                         const int32_t* origins_x, int nx, int first, int count, float* tiles, void* stream);
+int vitseg_forward_lowres(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16,
+                          const float* x, int batch, int precision, float* lowres, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int vitseg_window_blend(const float* lowres, const int32_t* origins_y, int ny, const int32_t* origins_x, int nx,
+                        const float* weights, int n, int C, int g, int S, int H, int W, float* logits, uint8_t* mask,
+                        void* stream);
+
 /* ---- measurement hooks (bench.py's roofline object) ----
  * While enabled, vitseg_forward brackets every kernel launch of the hot path with a pair of
  * hipEvents on the launch stream; vitseg_forward_train / vitseg_backward bracket the GEMMs and

@@ -62,7 +62,11 @@ HELPER_EXPORTS = [
     "vitseg_op_conv_dgrad_weight", "vitseg_op_transpose_bf16", "vitseg_op_transpose_layers_bf16", "vitseg_op_dropout_rows",
     "vitseg_op_layernorm_h16",
 ]
-_LATE_EXPORTS = AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS
+# sliding-window inference (model.predict_mask_windowed): the window grid, the tile gather, the forward that stops at the low-res
+# head output and the overlapping-tile blend: bound on first use, the same way
+WINDOW_EXPORTS = ["vitseg_window_count", "vitseg_window_origins", "vitseg_window_gather", "vitseg_forward_lowres",
+                  "vitseg_window_blend"]
+_LATE_EXPORTS = AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -212,6 +216,9 @@ def lib() -> C.CDLL:
             for name, args in _helper_argtypes(vp, sz, i32).items():
                 getattr(l, name).argtypes = args
             l.vitseg_op_head1x1_bwd_scratch_floats.restype = sz
+        if getattr(l, "vitseg_window_blend", None) is not None:
+            for name, args in _window_argtypes(vp, sz, i32, pcfg).items():
+                getattr(l, name).argtypes = args
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -240,6 +247,16 @@ def _ce_opts_argtypes(vp, sz, i32, pcfg) -> dict:
         "vitseg_ce_loss_opts": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, popt, f32, vp],
         "vitseg_backward_opts": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp,
                                  popt],
+    }
+
+
+def _window_argtypes(vp, sz, i32, pcfg) -> dict:
+    return {
+        "vitseg_window_count": [i32, i32, i32],
+        "vitseg_window_origins": [i32, i32, i32, vp],
+        "vitseg_window_gather": [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp],
+        "vitseg_forward_lowres": [pcfg, i32, vp, vp, vp, i32, i32, vp, vp, sz, vp],
+        "vitseg_window_blend": [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     }
 
 
@@ -309,6 +326,26 @@ def sdf_symbol(name: str):
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before distance transforms): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
+
+
+def window_symbol(name: str):
+    """One of WINDOW_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before sliding-window inference): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def window_origins(extent: int, S: int, stride: int) -> list:
+    """Origins of the windows along one axis (vitseg_window_origins): i * stride, the last one shifted back to end at the edge.
+    ValueError for an extent shorter than the window, a stride outside 1..S or an extent above 16384."""
+    n = int(window_symbol("vitseg_window_count")(int(extent), int(S), int(stride)))
+    if n < 0:
+        check(n)
+    out = (C.c_int32 * n)()
+    check(window_symbol("vitseg_window_origins")(int(extent), int(S), int(stride), out))
+    return list(out)
 
 
 def splitk_symbol(name: str):

@@ -2,6 +2,7 @@
 #include <stdlib.h>
 
 #include "kernels.hpp"
+#include "tail_math.hpp"
 
 namespace vitseg {
 namespace {
@@ -30,44 +31,10 @@ __global__ __launch_bounds__(256) void head1x1_kernel(const float* __restrict__ 
 // (model/CE/classes.py:260) fused with the scripts' post-processing
 // `logits.sigmoid()` -> `argmax(dim=class)` (model/CE/testViTModel.py:122-126).
 //
-// Bit-exact restatement of ATen's CPU kernel as built for x86+FMA (see
-// oracle/vitseg_oracle.py:upsample_bilinear): taps src = max(scale*(d+0.5)-0.5, 0),
-//   row = fma(a, wx0, b*wx1);  out = fma(row_top, wy0, row_bot*wy1).
-// Explicit __f*_rn intrinsics keep hipcc from re-contracting the expression.
+// The taps, the fma placement (row = fma(a, wx0, b*wx1); out = fma(row_top, wy0, row_bot*wy1)) and ATen's fp32 sigmoid:
+// tail_math.hpp (taps, sigmoid_aten), shared with the overlapping-window blend of window.hip.
 // Bound: HBM writes (C*S*S*4 B logits and/or S*S B mask per image); the low-res input
 // (C*g*g*4 B per image) stays in L2.  Thread = 4 consecutive x of one output row.
-__device__ __forceinline__ void taps(int d, float scale, int n_in, int& i0, int& i1, float& w0, float& w1) {
-    float src = __fsub_rn(__fmul_rn(scale, __fadd_rn((float)d, 0.5f)), 0.5f);
-    src = src < 0.f ? 0.f : src;
-    i0 = min((int)floorf(src), n_in - 1);
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    w1 = fminf(fmaxf(__fsub_rn(src, (float)i0), 0.f), 1.f);
-    w0 = __fsub_rn(1.f, w1);
-}
-
-// `logits.sigmoid()` exactly as ATen's CPU kernel computes it for fp32 (UnaryOpsKernel.cpp sigmoid_kernel, vector path:
-// a = 0 - x; a = Sleef_expf_u10(a); a = 1 + a; a = 1 / a) -- restated operation by operation (oracle/vitseg_oracle.py
-// sigmoid_aten, pinned bit-for-bit against torch.sigmoid): the mask decision hinges on fp32 sigmoid TIES between
-// classes (first index wins), so a 1-ulp difference in exp would move it.  Explicit *_rn intrinsics and fmaf keep
-// hipcc from contracting or re-associating.
-__device__ __forceinline__ float sigmoid_aten(float x) {
-    const float d = __fsub_rn(0.0f, x);
-    const float q = __builtin_rintf(__fmul_rn(d, 1.4426950408889634f));        // ties to even, as cvtps_epi32
-    float s = __fmaf_rn(q, -0.693145751953125f, d);
-    s = __fmaf_rn(q, -1.428606765330187045e-06f, s);
-    float u = 0.000198527617612853646278381f;
-    u = __fmaf_rn(u, s, 0.00139304355252534151077271f);
-    u = __fmaf_rn(u, s, 0.00833336077630519866943359f);
-    u = __fmaf_rn(u, s, 0.0416664853692054748535156f);
-    u = __fmaf_rn(u, s, 0.166666671633720397949219f);
-    u = __fmaf_rn(u, s, 0.5f);
-    u = __fadd_rn(1.0f, __fmaf_rn(__fmul_rn(s, s), u, s));
-    const int qi = (int)q, h = qi >> 1;
-    u = __fmul_rn(__fmul_rn(u, __int_as_float((h + 127) << 23)), __int_as_float((qi - h + 127) << 23));
-    u = d < -104.0f ? 0.0f : u;
-    u = d > 100.0f ? INFINITY : u;
-    return __fdiv_rn(1.0f, __fadd_rn(1.0f, u));
-}
 
 // Thread = a 4 (x) by UPR (y) block of output pixels: the x taps are computed once, and the two horizontally
 // interpolated source rows (`top`, `bot`) are reused while consecutive output rows keep the same source rows (at

@@ -127,6 +127,12 @@ int launch_attn_dropmask(unsigned* W, int B, int Np, int A, DropArgs dr, hipStre
 int launch_head1x1(const float* F, const float* W2, const float* b2, float* Z, int B, int Np, int C, hipStream_t s);
 // bilinear upsample + optional sigmoid->argmax mask (a12 + a14)
 int launch_upsample(const float* Z, float* logits, uint8_t* mask, int B, int C, int g, int S, hipStream_t s);
+// sliding-window inference (window.hip): the window grid of one axis, the tile gather and the overlapping-tile blend
+int window_count(int extent, int S, int stride);
+int launch_window_gather(const void* src, int src_is_u8, int n, int H, int W, int S, const int* oy, int ny, const int* ox,
+                         int nx, int first, int count, float* out, hipStream_t s);
+int launch_window_blend(const float* lowres, const int* oy, int ny, const int* ox, int nx, const float* w, int n, int C, int g,
+                        int S, int H, int W, float* logits, uint8_t* mask, hipStream_t s);
 
 // CE loss on the (virtually) upsampled logits (a13); optional full-resolution gradient G
 size_t ce_partial_count(int B, int S);

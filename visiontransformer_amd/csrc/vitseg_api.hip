@@ -232,14 +232,16 @@ int vitseg_forward(const vitseg_config* cfg, const float* params, const void* pa
 
 // s: the input's shape (activations, outputs); s0 / lay: the arena's.  With another grid the position table is resampled
 // into the workspace first and the embedding launches read it there instead of the arena's (the one pointer they take).
-int vitseg_forward_at(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16, const float* x,
-                      int batch, int precision, float* logits, uint8_t* mask, void* workspace, size_t workspace_bytes,
-                      void* stream_) {
+// lowres (vitseg_forward_lowres): the head writes its [batch, C, g, g] output there instead of into the workspace and the
+// walk ends before the upsample (no logits, no mask); NULL: vitseg_forward_at.
+static int forward_walk(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16, const float* x,
+                        int batch, int precision, float* logits, uint8_t* mask, float* lowres, void* workspace,
+                        size_t workspace_bytes, void* stream_) {
     Shape s, s0;
     vitseg_config cin;
     if (int rc = derive_input(cfg, image_size_in, &cin, &s, &s0)) return rc;
     VITSEG_CHECK_ARG(params && x && workspace && batch >= 1, VITSEG_EINVAL, "null pointer or batch < 1");
-    VITSEG_CHECK_ARG(logits || mask, VITSEG_EINVAL, "both outputs are null");
+    VITSEG_CHECK_ARG(lowres || logits || mask, VITSEG_EINVAL, "both outputs are null");
     VITSEG_CHECK_ARG(precision >= VITSEG_F32 && precision <= VITSEG_F32X3, VITSEG_EINVAL, "precision %d", precision);
     if (int rc = check_precision(s, precision)) return rc;
     VITSEG_CHECK_ARG(precision == VITSEG_F32 || precision == VITSEG_F32X3 || params_bf16, VITSEG_EINVAL,
@@ -270,13 +272,28 @@ int vitseg_forward_at(const vitseg_config* cfg, int image_size_in, const float* 
     // fp32 storage, GEMMs on the fp16 pipe with split operands; 2 = the weights come pre-split (params_bf16 slot)
     f.x3 = precision == VITSEG_F32X3 ? (params_bf16 ? 2 : 1) : 0;
     f.layer = [&](int) { return io; };
-    f.hf = H; f.F = (float*)(ws + p.f); f.Z = (float*)(ws + p.z); f.zeros = ws + p.zero;
+    f.hf = H; f.F = (float*)(ws + p.f); f.Z = lowres ? lowres : (float*)(ws + p.z); f.zeros = ws + p.zero;
     f.scratch = (float*)(ws + p.thin); f.scratch_floats = p.thin_floats;
     f.logits = logits; f.mask = mask;
     f.thin_rows = true; f.whole_split = true; f.attn_small = attn_small_infer; f.conv_dma = true;
     f.prof = FwdProf{VITSEG_K_GEMM_PATCH, VITSEG_K_LAYERNORM, VITSEG_K_GEMM_BIAS, VITSEG_K_ATTENTION, VITSEG_K_GEMM_RESADD,
                      VITSEG_K_GEMM_GELU, VITSEG_K_GEMM_RESADD, VITSEG_K_GEMM_CONV3, VITSEG_K_HEAD1X1, VITSEG_K_UPSAMPLE, false};
     return small_applies(&cin, batch, precision) ? walk_small(f) : walk_large(f);
+}
+
+int vitseg_forward_at(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16, const float* x,
+                      int batch, int precision, float* logits, uint8_t* mask, void* workspace, size_t workspace_bytes,
+                      void* stream_) {
+    return forward_walk(cfg, image_size_in, params, params_bf16, x, batch, precision, logits, mask, nullptr, workspace,
+                        workspace_bytes, stream_);
+}
+
+int vitseg_forward_lowres(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16,
+                          const float* x, int batch, int precision, float* lowres, void* workspace, size_t workspace_bytes,
+                          void* stream_) {
+    VITSEG_CHECK_ARG(lowres, VITSEG_EINVAL, "forward_lowres: the output is null");
+    return forward_walk(cfg, image_size_in, params, params_bf16, x, batch, precision, nullptr, nullptr, lowres, workspace,
+                        workspace_bytes, stream_);
 }
 
 size_t vitseg_ce_scratch_bytes(int batch, int S) { return ce_partial_count(batch, S) * sizeof(double); }

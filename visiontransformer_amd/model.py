@@ -525,6 +525,97 @@ class ViTSegmentationModel(nn.Module):
         m = self.predict_mask(tiles)
         return m.reshape(B, ty, tx, S, S).permute(0, 1, 3, 2, 4).reshape(B, H, W).contiguous()
 
+    @torch.no_grad()
+    def predict_mask_windowed(self, x: torch.Tensor, *, stride: Optional[int] = None, weights: str = "linear",
+                              tile_batch: int = 32, window_size: Optional[int] = None, return_logits: bool = False):
+        """Masks for images of ANY size >= the window by overlapping sliding-window inference: the image is covered by
+        S x S windows `stride` apart (the last one of an axis shifted back to end at the edge), every window runs through
+        the model as a tile, and the tiles' low-resolution head outputs are blended on the device -- each covering tile
+        upsampled on the fly with the decoder tail's arithmetic, weighted, normalised, then sigmoid -> argmax
+        (vitseg_window_blend, include/vitseg.h); the per-tile full-resolution logits are never materialised.
+        x: [B, 3, H, W] fp32 or [B, H, W, 3] uint8 (decoded bytes; converted as ToTensor does while the tiles are gathered)
+        -> uint8 [B, H, W], and the blended fp32 logits [B, C, H, W] with `return_logits`.
+        `stride`: default 3 S / 4 rounded down to a multiple of the patch size.  `weights`: "uniform" (all ones: the mean of
+        the covering tiles) or "linear" (min(i + 1, S - i) along each axis: a tile counts most at its centre, so the hard
+        tile edges, where the ViT had no context, fade out).  `window_size`: the window's side S, default the model's image
+        size; another size runs with the position table resampled (interpolate_pos_encoding).  `tile_batch`: tiles per
+        forward; the result does not depend on it (a short last chunk that would take another kernel route than the full
+        ones is padded with repeated tiles).  With H = W = S the result is `predict_mask`'s, bit for bit."""
+        cfg = self.cfg
+        S = cfg.image_size if window_size is None else int(window_size)
+        u8 = x.dtype == torch.uint8
+        if x.dim() != 4 or (x.shape[-1] if u8 else x.shape[1]) != cfg.num_channels:
+            raise ValueError(f"expected [B, {cfg.num_channels}, H, W] fp32 or [B, H, W, {cfg.num_channels}] uint8, got "
+                             f"{x.dtype} {tuple(x.shape)}")
+        if not x.is_cuda or x.device != self.arena.device:
+            raise RuntimeError("ViTSegmentationModel runs on the MI355X only: move the model and the input to the "
+                               f"same HIP device (input on {x.device}, parameters on {self.arena.device}). "
+                               "There is no CPU fallback.")
+        B, (H, W) = int(x.shape[0]), ((x.shape[1], x.shape[2]) if u8 else (x.shape[2], x.shape[3]))
+        H, W, P = int(H), int(W), cfg.patch_size
+        if S < P or S % P:
+            raise ValueError(f"window size {S} is not a positive multiple of the patch size {P}.")
+        if H < S or W < S:
+            raise ValueError(f"image {H}x{W} is smaller than the {S}x{S} window")
+        if stride is None:
+            stride = max(P, (3 * S // 4) // P * P)
+        if weights not in ("uniform", "linear"):
+            raise ValueError(f'weights must be "uniform" or "linear", got {weights!r}')
+        if int(tile_batch) < 1:
+            raise ValueError(f"tile_batch must be >= 1, got {tile_batch}")
+        plan = self._window_lowres(x, u8, S, int(stride), weights, int(tile_batch))
+        return self._window_blend(plan, return_logits, True)
+
+    def _window_lowres(self, x, u8: bool, S: int, stride: int, weights: str, tile_batch: int) -> dict:
+        """The tiles of `x` gathered and forwarded `tile_batch` at a time into one low-res buffer [T, C, g, g]; returns what
+        `_window_blend` needs (tools/window_probe.py times the two halves apart)."""
+        cfg, P = self.cfg, self.cfg.patch_size
+        B, (H, W) = int(x.shape[0]), ((int(x.shape[1]), int(x.shape[2])) if u8 else (int(x.shape[2]), int(x.shape[3])))
+        oy, ox = _lib.window_origins(H, S, stride), _lib.window_origins(W, S, stride)   # ValueError on a bad stride
+        ny, nx = len(oy), len(ox)
+        T, g, Cc, dev = B * ny * nx, S // P, cfg.num_classes, x.device
+        x = x.contiguous() if u8 else x.to(torch.float32).contiguous()
+        tab = torch.tensor(oy + ox, dtype=torch.int32).to(dev)
+        i = torch.arange(S, dtype=torch.float32)
+        wtab = (torch.ones(S) if weights == "uniform" else torch.minimum(i + 1, S - i)).to(dev)
+        chunk = min(int(tile_batch), T)
+        tiles = torch.empty((chunk, cfg.num_channels, S, S), dtype=torch.float32, device=dev)
+        lowres = torch.empty((T, Cc, g, g), dtype=torch.float32, device=dev)
+        ws, lp = self.workspace(chunk, S), self._bf16_arena()
+        ccfg = C.byref(_lib.CConfig.from_config(cfg))
+        gather, fwd = _lib.window_symbol("vitseg_window_gather"), _lib.window_symbol("vitseg_forward_lowres")
+        route = self.forward_route(chunk, S)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            for first in range(0, T, chunk):
+                cnt = min(chunk, T - first)
+                _lib.check(gather(x.data_ptr(), int(u8), B, H, W, S, tab.data_ptr(), ny, tab[ny:].data_ptr(), nx, first, cnt,
+                                  tiles.data_ptr(), stream))
+                # results are bit-identical across batch sizes inside one route only: a short chunk on another route is
+                # padded to the full size with repeats of its first tile, and the extras are dropped
+                run = cnt if cnt == chunk or self.forward_route(cnt, S) == route else chunk
+                if run != cnt:
+                    tiles[cnt:] = tiles[0]
+                out = lowres[first:first + cnt] if run == cnt else torch.empty((run, Cc, g, g), dtype=torch.float32, device=dev)
+                wsr = ws if run == chunk else self.workspace(run, S)
+                _lib.check(fwd(ccfg, S, self.arena.data_ptr(), _ptr(lp), tiles.data_ptr(), run, self.precision, out.data_ptr(),
+                               wsr.data_ptr(), wsr.numel(), stream))
+                if run != cnt:
+                    lowres[first:first + cnt] = out[:cnt]
+        return dict(lowres=lowres, tab=tab, ny=ny, nx=nx, wtab=wtab, B=B, g=g, S=S, H=H, W=W)
+
+    def _window_blend(self, p: dict, want_logits: bool, want_mask: bool):
+        """One vitseg_window_blend launch over the low-res tiles of `_window_lowres`."""
+        B, H, W, Cc, dev = p["B"], p["H"], p["W"], self.cfg.num_classes, p["lowres"].device
+        logits = torch.empty((B, Cc, H, W), dtype=torch.float32, device=dev) if want_logits else None
+        mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_mask else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.window_symbol("vitseg_window_blend")(p["lowres"].data_ptr(), p["tab"].data_ptr(), p["ny"],
+                                                                 p["tab"][p["ny"]:].data_ptr(), p["nx"], p["wtab"].data_ptr(), B,
+                                                                 Cc, p["g"], p["S"], H, W, _ptr(logits), _ptr(mask),
+                                                                 torch.cuda.current_stream().cuda_stream))
+        return (mask, logits) if want_logits and want_mask else (mask if want_mask else logits)
+
     _CE_CACHE_ENTRIES = 8   # device weight vectors / scratch buffers kept per model, least recently used first out
 
     def _ce_cached(self, kind: str, key, make):

@@ -68,18 +68,30 @@ def preprocess(image, size: int, device="cuda:0") -> torch.Tensor:
 
 
 def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, index_to_color=None,
-            return_logits: bool = False, serve_size: Optional[int] = None, return_boxes: bool = False):
+            return_logits: bool = False, serve_size: Optional[int] = None, return_boxes: bool = False,
+            sliding: bool = False, stride: Optional[int] = None, weights: str = "linear"):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
     resampled to it (interpolate_pos_encoding).  `return_boxes`: also, last, the reference's "Predicted Regions with
     Boxes" as {class: [(y_min, x_min, y_max, x_max), ...]} for every class present but 0 (testViTModel.py:171-185; the
-    4-connected regions of regions.region_boxes, computed on the device)."""
+    4-connected regions of regions.region_boxes, computed on the device).
+    `sliding`: the image is NOT resized: its decoded bytes are uploaded and S x S windows `stride` apart run at the image's
+    own resolution, blended with `weights` (ViTSegmentationModel.predict_mask_windowed); the mask is [H, W], the logits
+    [C, H, W].  An image with a side shorter than S raises ValueError."""
     seg = model.model if isinstance(model, LightningViTModel) else model
     S = serve_size if serve_size is not None else getattr(model, "serve_size", None)
     S = seg.cfg.image_size if S is None else int(S)
-    x = preprocess(image, S, seg.arena.device)
-    out = seg.predict_mask(x, return_logits=return_logits, interpolate_pos_encoding=S != seg.cfg.image_size)
+    if sliding:
+        img = torch.from_numpy(decode(image))
+        if img.dim() != 3 or min(img.shape[0], img.shape[1]) < S:
+            raise ValueError(f"sliding-window prediction needs an image of at least {S}x{S}, got "
+                             f"{tuple(img.shape[:2])[0]}x{tuple(img.shape[:2])[1]}")
+        out = seg.predict_mask_windowed(img[None].to(seg.arena.device), stride=stride, weights=weights, window_size=S,
+                                        return_logits=return_logits)
+    else:
+        x = preprocess(image, S, seg.arena.device)
+        out = seg.predict_mask(x, return_logits=return_logits, interpolate_pos_encoding=S != seg.cfg.image_size)
     mask_dev = (out[0] if return_logits else out)[0]
     boxes = None
     if return_boxes:
