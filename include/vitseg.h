@@ -337,6 +337,49 @@ int vitseg_ce_loss_opts(const float* lowres, const void* target, int target_is_u
                         float* loss, int batch, int C, int g, int S, const vitseg_ce_options* opts, float loss_scale,
                         void* stream);
 
+/* ---- CE + soft Dice on the same regenerated logits (the region term of the binary trainer's loss, dice_loss of
+ *      model/PAED/classes.py:608-620 with smooth 1e-6 flattened over the batch, applied per class to the softmax) ----
+ *   up = the bilinear upsample of lowres (the taps and fma placement of vitseg_ce_loss);  p = softmax_c(up);  t = one-hot(y)
+ *   keep = (y != ce->ignore_index), every pixel when ce is NULL or has_ignore_index = 0
+ *   K = the classes counted: 0 .. C-1, or 1 .. C-1 with include_background = 0 (C >= 2 then)
+ *   per class c in K, summed over the kept pixels of the whole batch:
+ *     I_c = sum p_c t_c;  P_c = sum p_c;  T_c = sum t_c;  D_c = P_c + T_c + smooth
+ *   dice = mean over c in K of [ 1 - (2 I_c + smooth) / D_c ]
+ *   loss = ce_weight * CE + dice_weight * dice
+ *     CE: what vitseg_ce_loss_opts computes for the same `ce` (vitseg_ce_loss when ce is NULL); class weights and label
+ *     smoothing act on CE only, ignore_index on both terms.  ce_weight == 0: the CE term is not formed (no count pass, an
+ *     exact 0, never 0 * NaN); dice_weight == 0: the Dice term is not formed (no sum pass) and grad_logits and terms[1]
+ *     are, bit for bit, vitseg_ce_loss_opts's.
+ *   a_c = -[2 t_c D_c - (2 I_c + smooth)] / (|K| D_c^2) for c in K on kept pixels, else 0
+ *   d loss / d up_c = ce_weight * (the CE gradient above) + dice_weight * p_c (a_c - sum_k a_k p_k) * loss_scale
+ * The gradient at one pixel depends on sums over the whole batch, so the call is three passes on one stream, no atomics,
+ * no host read: a sum pass (the logits regenerated per pixel, fp64 per-block partials of I, P, T: wavefront shuffles, then
+ * LDS; one block per 2048 pixels), a fixed-order reduce to 3 C device doubles, and one loss / gradient kernel (one thread
+ * per pixel, one store per element of grad_logits); a finish kernel writes terms[3] = {loss, CE, dice} (device fp32; a
+ * term that is not formed reads 0).  Results are bitwise reproducible and the same for int64 and uint8 targets.
+ *  - a class absent from the targets (T_c = 0) is still counted;
+ *  - everything ignored: I = P = T = 0, every dice_c = 1 - smooth / smooth = 0 (NaN when smooth == 0) and the Dice gradient
+ *    is 0; CE is NaN as in vitseg_ce_loss_opts, so the total is NaN unless ce_weight == 0;
+ *  - ignored pixels get 0.0f for every class, and nothing is read from under them;
+ *  - a label outside [0, C) that is not ignore_index poisons the sums: loss, dice and every kept pixel's gradient are NaN.
+ * `scratch` (the call's, >= vitseg_ce_scratch_bytes) holds the CE partials; dice->scratch (caller-owned device memory,
+ * 8-byte aligned, >= vitseg_dice_options_scratch_bytes(batch, C, S); every word read is written within the call) the sums
+ * and their partials.  C <= 255.  VITSEG_EINVAL before any launch: ce_weight, dice_weight or smooth negative or not
+ * finite, both weights 0, include_background = 0 with C < 2, dice NULL, dice->scratch NULL / misaligned / too small, the
+ * errors of vitseg_ce_loss_opts. */
+typedef struct vitseg_dice_options {
+    float ce_weight;            /* >= 0, finite */
+    float dice_weight;          /* >= 0, finite; not both 0 */
+    float smooth;               /* >= 0, finite; the reference's 1e-6 */
+    int32_t include_background; /* 0: class 0 is not counted (C >= 2) */
+    void* scratch;
+    size_t scratch_bytes;
+} vitseg_dice_options;
+size_t vitseg_dice_options_scratch_bytes(int batch, int C, int S);
+int vitseg_ce_dice_loss(const float* lowres, const void* target, int target_is_u8, float* grad_logits, void* scratch,
+                        float* terms, int batch, int C, int g, int S, const vitseg_ce_options* ce,
+                        const vitseg_dice_options* dice, float loss_scale, void* stream);
+
 /* ---- training (replaces autograd behind LightningViTModel.training_step, classes.py:276-285, and
  *      torch.optim.Adam(lr=1e-5).step(), classes.py:296-297).  dropout_p (the reference trains with 0.1,
  *      classes.py:233-234) is applied at the four sites of HF ViT (embeddings, attention probabilities,
@@ -390,6 +433,16 @@ int vitseg_backward_opts(const vitseg_config* cfg, int image_size_in, const floa
                          int target_is_u8, const float* grad_logits, float* grads, float* loss, float loss_scale,
                          void* const* bucket_events, void* workspace, size_t workspace_bytes, void* stream,
                          const vitseg_ce_options* ce_options);
+/* vitseg_backward_opts whose fused loss is vitseg_ce_dice_loss: with `dice` the fused branch (target != NULL) forms
+ * ce_weight * CE + dice_weight * dice, writes {loss, CE, dice} to terms[3] (device fp32, required then) and the total to
+ * *loss as well; nothing else in the walk changes.  dice == NULL: exactly vitseg_backward_opts (terms is not touched).
+ * Together with grad_logits, dice must be NULL (VITSEG_EINVAL).  The Dice scratch is the caller's, so the training
+ * workspace keeps its size and layout. */
+int vitseg_backward_dice(const vitseg_config* cfg, int image_size_in, const float* params, const void* params_bf16,
+                         const float* x, int batch, int precision, float dropout_p, uint64_t dropout_seed, const void* target,
+                         int target_is_u8, const float* grad_logits, float* grads, float* loss, float loss_scale,
+                         void* const* bucket_events, void* workspace, size_t workspace_bytes, void* stream,
+                         const vitseg_ce_options* ce_options, const vitseg_dice_options* dice, float* terms);
 int vitseg_grad_bucket_count(const vitseg_config* cfg);
 int vitseg_grad_bucket_range(const vitseg_config* cfg, int bucket, size_t* offset_floats, size_t* n_floats);
 /* ---- pre-processing (replaces transforms.Resize((S, S)) + transforms.ToTensor() on the PIL image,

@@ -66,7 +66,10 @@ HELPER_EXPORTS = [
 # head output and the overlapping-tile blend: bound on first use, the same way
 WINDOW_EXPORTS = ["vitseg_window_count", "vitseg_window_origins", "vitseg_window_gather", "vitseg_forward_lowres",
                   "vitseg_window_blend"]
-_LATE_EXPORTS = AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
+# CE + soft Dice in one fused loss (model.ce_dice_loss): bound on first use, the same way
+DICE_EXPORTS = ["vitseg_dice_options_scratch_bytes", "vitseg_ce_dice_loss", "vitseg_backward_dice"]
+_LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
+                 + DICE_EXPORTS)
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -80,6 +83,12 @@ class CCEOptions(C.Structure):
     _fields_ = [("has_ignore_index", C.c_int32), ("reserved", C.c_int32), ("ignore_index", C.c_int64),
                 ("class_weight", C.c_void_p), ("label_smoothing", C.c_float), ("scratch", C.c_void_p),
                 ("scratch_bytes", C.c_size_t)]
+
+
+class CDiceOptions(C.Structure):
+    """struct vitseg_dice_options (include/vitseg.h)."""
+    _fields_ = [("ce_weight", C.c_float), ("dice_weight", C.c_float), ("smooth", C.c_float),
+                ("include_background", C.c_int32), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
 class CConfig(C.Structure):
@@ -219,6 +228,10 @@ def lib() -> C.CDLL:
         if getattr(l, "vitseg_window_blend", None) is not None:
             for name, args in _window_argtypes(vp, sz, i32, pcfg).items():
                 getattr(l, name).argtypes = args
+        if getattr(l, "vitseg_backward_dice", None) is not None:
+            for name, args in _dice_argtypes(vp, sz, i32, pcfg).items():
+                getattr(l, name).argtypes = args
+            l.vitseg_dice_options_scratch_bytes.restype = sz
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -247,6 +260,16 @@ def _ce_opts_argtypes(vp, sz, i32, pcfg) -> dict:
         "vitseg_ce_loss_opts": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, popt, f32, vp],
         "vitseg_backward_opts": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp,
                                  popt],
+    }
+
+
+def _dice_argtypes(vp, sz, i32, pcfg) -> dict:
+    f32, popt, pdice = C.c_float, C.POINTER(CCEOptions), C.POINTER(CDiceOptions)
+    return {
+        "vitseg_dice_options_scratch_bytes": [i32, i32, i32],
+        "vitseg_ce_dice_loss": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, popt, pdice, f32, vp],
+        "vitseg_backward_dice": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp,
+                                 popt, pdice, vp],
     }
 
 
@@ -297,6 +320,15 @@ def ce_opts_symbol(name: str):
     fn = getattr(lib(), name, None)
     if fn is None:
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before the cross-entropy options): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def dice_symbol(name: str):
+    """One of DICE_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the CE + Dice loss): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
 

@@ -145,6 +145,15 @@ size_t ce_opts_scratch_bytes(int B, int S);
 int check_ce_options(const vitseg_ce_options& o, int B, int C, int S);
 int launch_ce_loss_opts(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B,
                         int C, int g, int S, const vitseg_ce_options& opts, hipStream_t s, float gscale = 1.0f);
+// ... plus the soft-Dice region term (vitseg_dice_options): a sum pass and a fixed-order reduce leave I, P, T per class on
+// the device (dice.scratch, dice_scratch_bytes), then one kernel forms both gradients.  terms: device float[3] = {loss, CE,
+// dice}; loss_out (optional): the total once more.  ce may be null (the plain CE).  check_dice_options: the argument checks
+// of both option structs (VITSEG_EINVAL), for callers that launch other work first.
+size_t dice_scratch_bytes(int B, int C, int S);
+int check_dice_options(const vitseg_dice_options& d, const vitseg_ce_options* ce, int B, int C, int S);
+int launch_ce_dice_loss(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* terms,
+                        float* loss_out, int B, int C, int g, int S, const vitseg_ce_options* ce,
+                        const vitseg_dice_options& dice, hipStream_t s, float gscale = 1.0f);
 
 // CLS token rows of the embedding output: X[B*Np + b] = cls + pos[0]  (a3)
 int launch_cls_rows(const float* cls, const float* pos, float* X, int B, int Np, int D, hipStream_t s);

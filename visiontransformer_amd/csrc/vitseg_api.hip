@@ -320,6 +320,19 @@ int vitseg_ce_loss_opts(const float* lowres, const void* target, int target_is_u
                                (hipStream_t)stream, loss_scale);
 }
 
+size_t vitseg_dice_options_scratch_bytes(int batch, int C, int S) {
+    return batch >= 1 && C >= 1 && S >= 1 ? dice_scratch_bytes(batch, C, S) : 0;
+}
+
+int vitseg_ce_dice_loss(const float* lowres, const void* target, int target_is_u8, float* grad_logits, void* scratch,
+                        float* terms, int batch, int C, int g, int S, const vitseg_ce_options* ce,
+                        const vitseg_dice_options* dice, float loss_scale, void* stream) {
+    VITSEG_CHECK_ARG(batch >= 1 && C >= 1 && g >= 1 && S >= g, VITSEG_EINVAL, "ce_dice_loss: bad shape");
+    VITSEG_CHECK_ARG(dice, VITSEG_EINVAL, "ce_dice_loss: the dice options are null");
+    return launch_ce_dice_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, terms, nullptr, batch, C, g, S, ce,
+                               *dice, (hipStream_t)stream, loss_scale);
+}
+
 int vitseg_profile_enable(int on) {
     profiler().clear();
     profiler().on = on != 0;

@@ -14,18 +14,22 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .model import ViTSegmentationModel, check_ce_options
+from .model import ViTSegmentationModel, check_ce_options, check_dice_options
 
 
 class LightningViTModel(nn.Module):
     def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, *,
                  interpolate_pos_encoding: bool = False, ignore_index=None, class_weight=None,
-                 label_smoothing: float = 0.0, **kw):
+                 label_smoothing: float = 0.0, dice_weight: float = 0.0, dice_smooth: float = 1e-6,
+                 dice_include_background: bool = True, **kw):
         """`interpolate_pos_encoding`: inputs of other (square, multiple-of-P) sizes than `image_size` run with the
         position table resampled to their grid (ViTSegmentationModel.forward); targets are resized to the input's size.
         `ignore_index`, `class_weight`, `label_smoothing`: the arguments of the reference's `nn.CrossEntropyLoss()`
         (classes.py:268) it leaves at their defaults -- a void label whose pixels do not count, one weight per class,
-        smoothed targets (ViTSegmentationModel.ce_loss); used by the training and the validation step alike."""
+        smoothed targets (ViTSegmentationModel.ce_loss); used by the training and the validation step alike.
+        `dice_weight` > 0 adds that many times the soft Dice loss of the softmax probabilities to the CE
+        (ViTSegmentationModel.ce_dice_loss with `dice_smooth`, `dice_include_background`); both steps then log `*_ce` and
+        `*_dice` beside `*_loss`.  With 0 the steps call exactly what they call without the argument."""
         super().__init__()
         self.model = ViTSegmentationModel(num_classes, patch_size, hidden_size, num_hidden_layers,
                                           num_attention_heads, **kw)
@@ -34,6 +38,10 @@ class LightningViTModel(nn.Module):
         self.ignore_index, self.label_smoothing = ignore_index, label_smoothing
         # a tuple: one device copy, found again by value on every step
         self.class_weight = None if class_weight is None else tuple(float(v) for v in class_weight)
+        self.dice_weight = float(dice_weight)
+        if self.dice_weight != 0.0:
+            check_dice_options(num_classes, dice_weight, 1.0, dice_smooth, dice_include_background)
+        self.dice_smooth, self.dice_include_background = dice_smooth, bool(dice_include_background)
         self.logged = {}
 
     def forward(self, x):
@@ -52,7 +60,8 @@ class LightningViTModel(nn.Module):
             return self._prep.targets(y, tuple(size), dtype=dtype)
         return F.interpolate(y.unsqueeze(1).float(), size=size, mode="nearest").squeeze(1).to(dtype)
 
-    def _loss(self, batch, grad_scale=None):
+    def _loss(self, batch, grad_scale=None, stage=None):
+        """`stage` ("train" / "valid"): where the CE and Dice terms are logged when the Dice term is on."""
         x, y = batch
         S = self.model.cfg.image_size  # the reference hard-codes (224, 224) = its image_size (classes.py:278)
         if self.interpolate_pos_encoding:
@@ -64,19 +73,26 @@ class LightningViTModel(nn.Module):
         opts = {}
         if self.ignore_index is not None or self.class_weight is not None or self.label_smoothing != 0:
             opts = dict(ignore_index=self.ignore_index, class_weight=self.class_weight, label_smoothing=self.label_smoothing)
+        if self.dice_weight != 0.0:
+            loss, ce, dice = self.model.ce_dice_loss(
+                x, y, dice_weight=self.dice_weight, smooth=self.dice_smooth, include_background=self.dice_include_background,
+                grad_scale=grad_scale, interpolate_pos_encoding=self.interpolate_pos_encoding, return_terms=True, **opts)
+            if stage is not None:
+                self.logged[f"{stage}_ce"], self.logged[f"{stage}_dice"] = ce, dice
+            return loss
         if self.interpolate_pos_encoding:
             return self.model.ce_loss(x, y, grad_scale=grad_scale, interpolate_pos_encoding=True, **opts)
         return self.model.ce_loss(x, y, grad_scale=grad_scale, **opts)
 
     # `logged` holds DEVICE scalars: reading one (float(...)) is the only host sync, and only the caller decides when
     def training_step(self, batch, batch_idx, grad_scale=None):
-        loss = self._loss(batch, grad_scale)
+        loss = self._loss(batch, grad_scale, stage="train")
         self.logged["train_loss"] = loss.detach()
         return loss
 
     def validation_step(self, batch, batch_idx):
         with torch.no_grad():
-            loss = self._loss(batch)
+            loss = self._loss(batch, stage="valid")
         self.logged["valid_loss"] = loss
         return loss
 

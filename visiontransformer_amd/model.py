@@ -61,6 +61,26 @@ def check_ce_options(num_classes: int, ignore_index=None, class_weight=None, lab
     return ignore_index, w, eps
 
 
+def check_dice_options(num_classes: int, dice_weight=1.0, ce_weight=1.0, smooth=1e-6, include_background=True):
+    """Host-side validation of `ce_dice_loss`'s Dice options (the kernels cannot raise).  Returns (dice_weight, ce_weight,
+    smooth, include_background) as the fp32 values and the flag the kernels read.  ValueError: a weight or `smooth` that is
+    not a finite number >= 0 (in fp32), both weights 0, `include_background=False` with fewer than 2 classes."""
+    out = []
+    for name, v in (("dice_weight", dice_weight), ("ce_weight", ce_weight), ("smooth", smooth)):
+        try:
+            f = float(torch.tensor(float(v), dtype=torch.float32))   # what the kernels read
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}") from None
+        if not (0.0 <= f < float("inf")):   # (a NaN fails both comparisons)
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+        out.append(f)
+    if out[0] == 0.0 and out[1] == 0.0:
+        raise ValueError("dice_weight and ce_weight are both 0: there is no loss to form")
+    if not include_background and num_classes < 2:
+        raise ValueError("include_background=False needs at least 2 classes")
+    return out[0], out[1], out[2], bool(include_background)
+
+
 class _LogitsFn(torch.autograd.Function):
     """logits = forward(x) with libvitseg's backward: d loss / d logits -> d loss / d arena."""
 
@@ -100,6 +120,28 @@ class _CELossFn(torch.autograd.Function):
         if not ctx.prescaled:
             grads.mul_(dloss)   # in place: the buffer is ours until it is delivered
         return ctx.model._deliver_grad(grads), None, None, None, None, None, None
+
+
+class _CEDiceLossFn(torch.autograd.Function):
+    """`_CELossFn` for ce_weight CE + dice_weight dice (vitseg_backward_dice): returns the device float[3] {loss, CE, dice};
+    only element 0 carries a gradient (the other two are reported values), delivered the same way."""
+
+    @staticmethod
+    def forward(ctx, arena, model, x, target, grad_scale, interp, ce_opts, dice_opts):
+        drop = model._next_dropout()
+        model._forward_train(x, want_logits=False, drop=drop, interp=interp)
+        grads, terms = model._backward(x, target=target, drop=drop, loss_scale=1.0 if grad_scale is None else grad_scale,
+                                       interp=interp, ce_opts=ce_opts, dice_opts=dice_opts)
+        ctx.grads, ctx.model = grads, model
+        ctx.prescaled = grad_scale is not None
+        return terms
+
+    @staticmethod
+    def backward(ctx, dterms):
+        grads, ctx.grads = ctx.grads, None
+        if not ctx.prescaled:
+            grads.mul_(dterms[0])   # in place: the buffer is ours until it is delivered
+        return ctx.model._deliver_grad(grads), None, None, None, None, None, None, None
 
 
 class ViTSegmentationModel(nn.Module):
@@ -393,8 +435,10 @@ class ViTSegmentationModel(nn.Module):
 
     def _backward(self, x: torch.Tensor, target: Optional[torch.Tensor] = None,
                   grad_logits: Optional[torch.Tensor] = None, drop=(0.0, 0), loss_scale: float = 1.0,
-                  interp: bool = False, ce_opts=None):
-        """`ce_opts`: a `_lib.CCEOptions` from `_ce_options` (fused CE only), or None for the plain calls."""
+                  interp: bool = False, ce_opts=None, dice_opts=None):
+        """`ce_opts`: a `_lib.CCEOptions` from `_ce_options` (fused CE only), or None for the plain calls.  `dice_opts`: a
+        `_lib.CDiceOptions` from `_dice_options` (fused loss only): the second value returned is then the device float[3]
+        {loss, CE, dice} of vitseg_backward_dice instead of the scalar loss."""
         x = x.to(torch.float32).contiguous()
         B, S = x.shape[0], self._size_in(x, interp)
         ws = self._train_workspace(B, S)
@@ -408,7 +452,12 @@ class ViTSegmentationModel(nn.Module):
                     grads.data_ptr(), _ptr(loss), float(loss_scale), handles, ws.data_ptr(), ws.numel(),
                     torch.cuda.current_stream().cuda_stream)
             cfg = C.byref(_lib.CConfig.from_config(self.cfg))
-            if ce_opts is not None:
+            if dice_opts is not None:
+                terms = torch.zeros(3, dtype=torch.float32, device=x.device)
+                _lib.check(_lib.dice_symbol("vitseg_backward_dice")(
+                    cfg, S, *args, C.byref(ce_opts) if ce_opts is not None else None, C.byref(dice_opts), terms.data_ptr()))
+                loss = terms
+            elif ce_opts is not None:
                 _lib.check(_lib.ce_opts_symbol("vitseg_backward_opts")(cfg, S, *args, C.byref(ce_opts)))
             elif S == self.cfg.image_size:
                 _lib.check(_lib.lib().vitseg_backward(cfg, *args))
@@ -696,6 +745,56 @@ class ViTSegmentationModel(nn.Module):
             else:
                 _lib.check(_lib.ce_opts_symbol("vitseg_ce_loss_opts")(*args, C.byref(opts), 1.0, stream))
         return loss
+
+    def _dice_options(self, B: int, S: int, dice_weight, ce_weight, smooth, include_background):
+        """The `_lib.CDiceOptions` of a `ce_dice_loss` call (validated on the host); its scratch is cached per (batch, size)."""
+        dw, cw, sm, bg = check_dice_options(self.cfg.num_classes, dice_weight, ce_weight, smooth, include_background)
+        dev = self.arena.device
+        nbytes = int(_lib.dice_symbol("vitseg_dice_options_scratch_bytes")(B, self.cfg.num_classes, S))
+        scratch = self._ce_cached("dice scratch", (B, S, dev), lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+        opts = _lib.CDiceOptions(cw, dw, sm, int(bg), scratch.data_ptr(), scratch.numel())
+        opts._tensors = (scratch,)   # the struct holds a raw address: an eviction must not free it under the struct
+        return opts
+
+    def ce_dice_loss(self, x: torch.Tensor, target: torch.Tensor, *, dice_weight: float = 1.0, ce_weight: float = 1.0,
+                     smooth: float = 1e-6, include_background: bool = True, ignore_index: Optional[int] = None,
+                     class_weight=None, label_smoothing: float = 0.0, grad_scale: Optional[float] = None,
+                     interpolate_pos_encoding: bool = False, return_terms: bool = False):
+        """`ce_weight * CE + dice_weight * dice` on `self(x)` as a device scalar, without materialising the [B, C, S, S]
+        logits or their gradient: CE is `ce_loss` with the same `ignore_index`, `class_weight` and `label_smoothing`; dice
+        is the soft Dice loss of the softmax probabilities, `mean_c [1 - (2 I_c + smooth) / (P_c + T_c + smooth)]` with
+        I_c = sum p_c t_c, P_c = sum p_c, T_c = sum t_c over the kept pixels of the whole batch (the binary trainer's
+        `dice_loss`, model/PAED/classes.py:608-620, per class).  `include_background=False` leaves class 0 out of the
+        mean.  `ignore_index` acts on both terms, the class weights and the smoothing on CE only.  A weight of 0 leaves
+        its term out altogether (an exact 0; with `dice_weight=0` the value and the gradient are `ce_loss`'s).  A class
+        no target pixel carries is still counted; when every pixel is ignored dice is 0 and CE is NaN.  A label outside
+        [0, C) that is not `ignore_index` makes the loss NaN.  Invalid options raise ValueError on the host.
+        `return_terms=True` returns (loss, ce, dice), the last two detached device scalars.  `target`, `grad_scale` and
+        `interpolate_pos_encoding`: as in `ce_loss`."""
+        interp = bool(interpolate_pos_encoding)
+        if interp:
+            self._check_input(x, True)
+        S, B = self._size_in(x, interp), x.shape[0]
+        if tuple(target.shape) != (B, S, S) or target.dtype not in (torch.int64, torch.uint8):
+            raise ValueError(f"target must be int64/uint8 [B, {S}, {S}], got {target.dtype} {tuple(target.shape)}")
+        dopts = self._dice_options(B, S, dice_weight, ce_weight, smooth, include_background)
+        opts = self._ce_options(B, S, ignore_index, class_weight, label_smoothing)
+        target = target.to(self.arena.device).contiguous()
+        if self._needs_grad():
+            terms = _CEDiceLossFn.apply(self.arena, self, x, target, grad_scale, interp, opts, dopts)
+        else:
+            with torch.no_grad():
+                _, _ = self._run(x, False, True, interp=interp)  # fills the low-res logits (mask output is a by-product)
+                low = self.debug_buffer(B, _lib.BUF_LOWRES, S)
+                scratch = torch.empty(_lib.lib().vitseg_ce_scratch_bytes(B, S), dtype=torch.uint8, device=low.device)
+                terms = torch.empty(3, dtype=torch.float32, device=low.device)
+                _lib.check(_lib.dice_symbol("vitseg_ce_dice_loss")(
+                    low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8), None, scratch.data_ptr(),
+                    terms.data_ptr(), B, self.cfg.num_classes, S // self.cfg.patch_size, S,
+                    C.byref(opts) if opts is not None else None, C.byref(dopts), 1.0, torch.cuda.current_stream().cuda_stream))
+        if return_terms:
+            return terms[0], terms[1].detach(), terms[2].detach()
+        return terms[0]
 
     @torch.no_grad()
     def debug_buffer(self, batch: int, which: int, image_size: Optional[int] = None) -> torch.Tensor:

@@ -49,6 +49,10 @@ def add_ce_loss_arguments(ap) -> None:
                     help="label whose pixels do not count in the loss (255 for void / border pixels, -100 for torch's default)")
     ap.add_argument("--class-weights", default=None, help="comma-separated weight per class: w0,w1,...")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
+    ap.add_argument("--dice-weight", type=float, default=0.0,
+                    help="train on CE + this many times the soft Dice loss of the softmax probabilities (0: CE alone)")
+    ap.add_argument("--dice-smooth", type=float, default=1e-6)
+    ap.add_argument("--dice-no-background", action="store_true", help="leave class 0 out of the Dice mean")
 
 
 def ce_loss_options(a) -> dict:
@@ -63,6 +67,8 @@ def ce_loss_options(a) -> dict:
             raise ValueError(f"--class-weights expects comma-separated numbers, got {a.class_weights!r}") from None
     if a.label_smoothing:
         kw["label_smoothing"] = a.label_smoothing
+    if getattr(a, "dice_weight", 0.0):
+        kw.update(dice_weight=a.dice_weight, dice_smooth=a.dice_smooth, dice_include_background=not a.dice_no_background)
     return kw
 
 
