@@ -540,6 +540,34 @@ size_t vitseg_sdf_scratch_bytes(int n, int H, int W);
 int vitseg_sdf(const uint8_t* mask, int n, int H, int W, int normalize, float* sdf_ext, float* sdf_int, void* scratch,
                size_t scratch_bytes, void* stream);
 
+/* ---- boundary-distance statistics of class maps: the integers and fp64 sums behind PAED (the pixel average Euclidean
+ *      distance of model/PAED/classes.py:209-258, there two Python loops over all pixel pairs), the Hausdorff distance, its
+ *      percentiles (HD95) and the average symmetric distance ----
+ * pred, gt uint8 [n, H, W] class maps of one size; classes: K label values 0..255 in HOST memory.  Per image and class c,
+ * A = {gt == c} and P = {pred == c}; mode 0 (sets) takes them whole, mode 1 (borders) first replaces each by
+ * S ^ binary_erosion(S) (cross structure, border_value 0: a pixel of S one of whose four neighbours is outside S or outside
+ * the image).  d2_P(x) = the exact squared distance from pixel x to the nearest pixel of P.
+ * stats_i int64 [n, K, 6] (device): n = |A|, m = |P|, max_d2_AP = max over A of d2_P, max_d2_PA = max over P of d2_A (their
+ *   roots are the directed Hausdorff distances), d2_lo, d2_hi = the order statistics lo = pct_num (N - 1) / pct_den (integer
+ *   division) and hi = min(lo + 1, N - 1) of the pooled multiset {d2_P(x): x in A} u {d2_A(x): x in P}, N = n + m; the
+ *   percentile of the distances is sqrt(d2_lo) + (sqrt(d2_hi) - sqrt(d2_lo)) frac(pct_num (N - 1) / pct_den), as np.percentile.
+ * stats_f double [n, K, 2] (device): sumAP = sum over A of sqrt((double) d2_P), sumPA = sum over P of sqrt((double) d2_A).
+ * Empty sets (decided on the device): with n == 0 or m == 0 the maxima and order statistics are -1; the sums are 0 in mode 1;
+ *   in mode 0 both sums are 0 when both sets are empty, and when one is empty the other's sum is sum sqrt(y^2 + x^2) over its
+ *   pixels' (row, column) indices, the reference's rule (classes.py:230-235).
+ * scratch: vitseg_distance_scratch_bytes(n, H, W) device bytes (about 10 bytes per pixel of the batch plus histograms and
+ * partial sums; every word read is written within the call).  Classes are processed one after another on `stream`; no
+ * allocation or synchronisation.  The integers come from order-independent integer operations and the sums are added in an
+ * order fixed by H * W: the same bits on every call, and per image the same bits in any batch.
+ * VITSEG_EINVAL: null pointer, mode not 0 / 1, a class value outside 0..255, not 0 <= pct_num <= pct_den <= 1000 (pct_den
+ * >= 1); VITSEG_ESHAPE: H or W outside 1..16384, n outside 1..32767 (the planes are a batch of 2 n), K outside 1..256;
+ * VITSEG_EWORKSPACE: scratch smaller than vitseg_distance_scratch_bytes (0 for a bad shape).  Nothing is launched when a
+ * check fails. */
+size_t vitseg_distance_scratch_bytes(int n, int H, int W);
+int vitseg_distance_stats(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, const int32_t* classes, int K, int mode,
+                          int pct_num, int pct_den, int64_t* stats_i, double* stats_f, void* scratch, size_t scratch_bytes,
+                          void* stream);
+
 /* one Adam step over a flat fp32 buffer (torch.optim.Adam semantics, weight_decay 0, amsgrad off: torch's L2 weight decay,
  * g += weight_decay * p, is not implemented, and FusedAdam refuses a nonzero weight_decay);
  * step is 1-based; gradients are multiplied by grad_scale first (1/world for summed all-reduce). */

@@ -27,6 +27,9 @@ def main():
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--data")
     ap.add_argument("--out", default="test")
+    ap.add_argument("--distance-metrics", nargs="?", const="sets", choices=["sets", "borders"],
+                    help="also write <model>_distance_metrics.csv: PAED, Hausdorff, HD95 and ASSD per image, between the "
+                         "pixel sets of each class (sets, the default) or between their borders")
     a = ap.parse_args()
     dev = "cuda:0"
     cwd = os.getcwd()
@@ -40,7 +43,8 @@ def main():
         name = f"ID{vid}P{P}H{D}A{A}"
         batches = scripts.ce_batches(model.model.cfg, a.num_batches * a.batch_size, a.batch_size, a.data, seed=3)
         rows = scripts.evaluate_to_csv(model, batches, (vid, name, P, D, L, A), os.path.join(cwd, a.out, name, f"{name}_metrics.csv"),
-                                       a.num_classes, a.num_batches, dev)
+                                       a.num_classes, a.num_batches, dev,
+                                       distance_mode=a.distance_metrics)
         acc = sum(r[8] for r in rows) / max(len(rows), 1)
         print(f"{name}: {len(rows)} images, mean accuracy {acc:.2f} %, {rows[0][11] * 1e3:.2f} ms/image")
 

@@ -30,6 +30,9 @@ def main():
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--data")
     ap.add_argument("--out", default="test")
+    ap.add_argument("--distance-metrics", nargs="?", const="sets", choices=["sets", "borders"],
+                    help="also write <model>_distance_metrics.csv: PAED, Hausdorff, HD95 and ASSD per image, between the "
+                         "pixel sets of each class (sets, the default) or between their borders")
     a = ap.parse_args()
     dev = "cuda:0"
     cwd = os.getcwd()
@@ -45,7 +48,8 @@ def main():
         name = f"ID{vid}P{P}H{D}A{A}"
         batches = scripts.paed_binary_batches(model.model.cfg, a.num_batches * a.batch_size, a.batch_size, a.data, seed=5)
         rows = scripts.evaluate_to_csv(model, batches, (vid, name, P, D, L, A), os.path.join(cwd, a.out, name, f"{name}_metrics.csv"),
-                                       max(a.num_classes, 2), a.num_batches, dev)
+                                       max(a.num_classes, 2), a.num_batches, dev,
+                                       distance_mode=a.distance_metrics)
         print(f"{name}: {len(rows)} images evaluated -> {os.path.join(a.out, name)}")
 
 

@@ -196,4 +196,14 @@ int launch_pos_interp_bwd(const float* dout, float* din, float* scratch, int g0,
 int launch_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step,
                 float grad_scale, hipStream_t s, float weight_decay = 0.f);
 
+// exact squared Euclidean distance fields of binary masks (sdf.hip): the column and row launches of vitseg_sdf for the "ext"
+// field alone, stopped before the float conversion: d2 int32 [n, H, W] = squared distance to the nearest non-zero byte of
+// the image (an image without one gets the virtual feature at (-1, 0)).  maxw: 2 n ints, zeroed by the caller; 1 <= n <= 65535.
+int launch_sdf_d2(const unsigned char* mask, int n, int H, int W, int* d2, int* maxw, hipStream_t s);
+// boundary-distance statistics of class maps (distance.hip: vitseg_distance_stats)
+size_t distance_scratch_bytes(int n, int H, int W);
+int launch_distance_stats(const unsigned char* pred, const unsigned char* gt, int n, int H, int W, const int* classes, int K,
+                          int mode, int pct_num, int pct_den, long long* stats_i, double* stats_f, void* scratch,
+                          size_t scratch_bytes, hipStream_t s);
+
 }  // namespace vitseg

@@ -175,6 +175,21 @@ RowPlan row_plan(int W) {
     return p;
 }
 
+// the column and row launches: d2 of the fields f0 .. f0 + nf - 1 as int32 bits in o.f[], their maxima folded into maxw (zeroed
+// by the caller)
+int launch_d2(const unsigned char* mask, int n, int H, int W, const SdfOut& o, int f0, int nf, int* maxw, hipStream_t s) {
+    hipLaunchKernelGGL(sdf_column_kernel, dim3((W + 255) / 256, n), dim3(256), 0, s, mask, o, H, W);
+    VITSEG_LAUNCH_CHECK("sdf column");
+    const RowPlan p = row_plan(W);
+    if (p.lds > 65536) {
+        const hipError_t e = hipFuncSetAttribute((const void*)sdf_row_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(sdf row)");
+    }
+    hipLaunchKernelGGL(sdf_row_kernel, dim3((H + p.R - 1) / p.R, nf, n), dim3(WAVE), p.lds, s, o, maxw, H, W, p.R, p.Wp, f0);
+    VITSEG_LAUNCH_CHECK("sdf row");
+    return VITSEG_OK;
+}
+
 }  // namespace
 
 size_t sdf_scratch_bytes(int n, int H, int W) { return shape_ok(n, H, W) ? scratch_bytes(n) : 0; }
@@ -193,19 +208,16 @@ int launch_sdf(const unsigned char* mask, int n, int H, int W, int normalize, fl
     int* maxw = (int*)scratch;
     hipError_t e = hipMemsetAsync(maxw, 0, (size_t)n * 2 * sizeof(int), s);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(sdf maxima)");
-    hipLaunchKernelGGL(sdf_column_kernel, dim3((W + 255) / 256, n), dim3(256), 0, s, mask, o, H, W);
-    VITSEG_LAUNCH_CHECK("sdf column");
-    const RowPlan p = row_plan(W);
-    if (p.lds > 65536) {
-        e = hipFuncSetAttribute((const void*)sdf_row_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(sdf row)");
-    }
-    hipLaunchKernelGGL(sdf_row_kernel, dim3((H + p.R - 1) / p.R, nf, n), dim3(WAVE), p.lds, s, o, maxw, H, W, p.R, p.Wp, f0);
-    VITSEG_LAUNCH_CHECK("sdf row");
+    const int rc = launch_d2(mask, n, H, W, o, f0, nf, maxw, s);
+    if (rc != VITSEG_OK) return rc;
     const int P = H * W;
     hipLaunchKernelGGL(sdf_finish_kernel, dim3((P + 1023) / 1024, n, nf), dim3(256), 0, s, o, maxw, P, normalize, f0);
     VITSEG_LAUNCH_CHECK("sdf finish");
     return VITSEG_OK;
+}
+
+int launch_sdf_d2(const unsigned char* mask, int n, int H, int W, int* d2, int* maxw, hipStream_t s) {
+    return launch_d2(mask, n, H, W, SdfOut{{d2, nullptr}}, 0, 1, maxw, s);
 }
 
 }  // namespace vitseg

@@ -7,11 +7,20 @@ loops over classes in numpy to get, per image: pixel accuracy (%), mean IoU and 
 integer class statistics on the GPU -- the ground truth is nearest-resized on the fly exactly as
 `Image.fromarray(gt).resize(pred.shape[::-1], Image.NEAREST)` does -- and the metrics follow from those integers with
 the reference's own formulas, so the CSV is identical (tests/test_preproc_cpu.py, tests/test_gpu_preproc.py).
+
+Boundary distances (`Evaluator.distance_metrics`): how far a predicted region lies from the true one.  The reference's PAED
+(pixel average Euclidean distance, model/PAED/classes.py:209-258) is two Python loops over all pixel pairs and was left
+switched off; `vitseg_distance_stats` (csrc/distance.hip) gets the same sums from two exact distance transforms and a masked
+reduction per class, together with the integers behind the Hausdorff distance, its percentiles (HD95, pooled as MedPy's
+`hd95`) and the average symmetric distance.  `distances_from_stats` is the host arithmetic on those numbers.
 """
 from __future__ import annotations
 
 import csv
+import ctypes
+import math
 import warnings
+from fractions import Fraction
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -45,6 +54,65 @@ def metrics_from_counts(counts: np.ndarray, num_classes: int, total_pixels: int)
     return dict(Accuracy=acc, Mean_IoU=miou, Mean_Dice=mdice, GT_Classes=gtc, Pred_Classes=prc,
                 Missing_Classes=sorted(set(gtc) - set(prc)), False_Positive_Classes=sorted(set(prc) - set(gtc)),
                 ious=ious, dices=dices)
+
+
+DISTANCE_MODES = {"sets": 0, "borders": 1}
+DISTANCE_KEYS = ("paed", "hausdorff", "hd_percentile", "assd", "mean_AP", "mean_PA")
+# header of <model>_distance_metrics.csv (--distance-metrics of the evaluation scripts): the nan-aware class means per image
+DISTANCE_CSV_COLUMNS = ["Model_ID", "Model_Name", "Batch_Num", "Image_Idx", "Mode", "Percentile", "Mean_PAED",
+                        "Mean_Hausdorff", "Mean_HD_Percentile", "Mean_ASSD", "Per_Class"]
+
+
+def percentile_fraction(percentile):
+    """A percentile 0..100 as the rational (pct_num, pct_den) of vitseg_distance_stats: 95 -> (19, 20), 99.5 -> (199, 200).
+    ValueError outside 0..100 or when the denominator would pass 1000."""
+    f = Fraction(str(percentile)) / 100
+    if not 0 <= f <= 1 or f.denominator > 1000:
+        raise ValueError(f"percentile must lie in 0..100 with at most one decimal, got {percentile!r}")
+    return f.numerator, f.denominator
+
+
+def distances_from_stats(stats_i, stats_f, pct_num: int, pct_den: int) -> list:
+    """stats_i int64 [n, K, 6] and stats_f float64 [n, K, 2] of vitseg_distance_stats (include/vitseg.h) -> per image a list of
+    K dicts.  A = the ground truth's pixels of the class (n of them), P = the prediction's (m):
+      paed           the reference's formula (model/PAED/classes.py:228-254): 0 when both are empty, the sum / count of the
+                     other when one is, else (sumAP + sumPA + 0.001) / (n + m + 0.001)
+      hausdorff      sqrt(max(max_d2_AP, max_d2_PA))
+      hd_percentile  np.percentile of the pooled distances at pct_num / pct_den, from the two order statistics
+      assd           (sumAP + sumPA) / (n + m)
+      mean_AP, mean_PA  the directed means sumAP / n, sumPA / m
+    and n, m.  Everything but paed is nan when either set is empty (no distance is defined)."""
+    si = np.asarray(stats_i, dtype=np.int64)
+    sf = np.asarray(stats_f, dtype=np.float64)
+    if si.ndim != 3 or si.shape[2] != 6 or sf.shape != si.shape[:2] + (2,):
+        raise ValueError(f"stats_i must be [n, K, 6] and stats_f [n, K, 2], got {si.shape} and {sf.shape}")
+    if not (0 <= pct_num <= pct_den and 1 <= pct_den <= 1000):
+        raise ValueError(f"percentile {pct_num} / {pct_den} outside 0 <= num <= den <= 1000")
+    nan = float("nan")
+    out = []
+    for i in range(si.shape[0]):
+        row = []
+        for k in range(si.shape[1]):
+            n, m, mx_ap, mx_pa, lo2, hi2 = (int(v) for v in si[i, k])
+            s_ap, s_pa = float(sf[i, k, 0]), float(sf[i, k, 1])
+            d = dict(n=n, m=m, hausdorff=nan, hd_percentile=nan, assd=nan, mean_AP=nan, mean_PA=nan)
+            if n == 0 and m == 0:
+                d["paed"] = 0.0
+            elif n == 0:
+                d["paed"] = s_pa / m
+            elif m == 0:
+                d["paed"] = s_ap / n
+            else:
+                d["paed"] = (s_ap + s_pa + 0.001) / (n + m + 0.001)
+                d["hausdorff"] = math.sqrt(max(mx_ap, mx_pa))
+                frac = (pct_num * (n + m - 1) % pct_den) / pct_den
+                lo, hi = math.sqrt(lo2), math.sqrt(hi2)
+                d["hd_percentile"] = lo + (hi - lo) * frac
+                d["assd"] = (s_ap + s_pa) / (n + m)
+                d["mean_AP"], d["mean_PA"] = s_ap / n, s_pa / m
+            row.append(d)
+        out.append(row)
+    return out
 
 
 class Evaluator:
@@ -82,6 +150,64 @@ class Evaluator:
                                                      torch.cuda.current_stream().cuda_stream))
         return out
 
+    def distance_stats(self, pred: torch.Tensor, gt: torch.Tensor, classes: Sequence[int], mode: int, pct_num: int,
+                       pct_den: int):
+        """(stats_i int64 [n, K, 6], stats_f float64 [n, K, 2]) device tensors of vitseg_distance_stats for uint8 predictions
+        [n, H, W]; a ground truth of another size is nearest-resized first, as `counts` does on the fly."""
+        if pred.dtype != torch.uint8 or pred.dim() != 3:
+            raise ValueError(f"pred must be uint8 [n, H, W], got {pred.dtype} {tuple(pred.shape)}")
+        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
+            raise ValueError("Number of images and masks must be equal!")
+        classes = [int(c) for c in classes]
+        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
+            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
+        pred = pred.to(self.device).contiguous()
+        gt = gt.to(self.device).to(torch.uint8).contiguous()
+        n, H, W = (int(d) for d in pred.shape)
+        K = len(classes)
+        cls = (ctypes.c_int32 * K)(*classes)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            if tuple(gt.shape[1:]) != (H, W):
+                Hg, Wg = (int(d) for d in gt.shape[1:])
+                g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
+                _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
+                                                               self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
+                                                               st))
+                gt = g2
+            nbytes = _lib.distance_symbol("vitseg_distance_scratch_bytes")(n, H, W)
+            if nbytes == 0:
+                raise ValueError(f"distance metrics: H and W must lie in 1..16384 and n in 1..32767, got {n} x {H} x {W}")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            si = torch.empty((n, K, 6), dtype=torch.int64, device=self.device)
+            sf = torch.empty((n, K, 2), dtype=torch.float64, device=self.device)
+            _lib.check(_lib.distance_symbol("vitseg_distance_stats")(pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K, int(mode),
+                                                                     int(pct_num), int(pct_den), si.data_ptr(), sf.data_ptr(),
+                                                                     scratch.data_ptr(), nbytes, st))
+        return si, sf
+
+    def distance_metrics(self, pred: torch.Tensor, gt: torch.Tensor, classes: Optional[Sequence[int]] = None,
+                         mode: str = "sets", percentile=95) -> List[dict]:
+        """Per image: dict(per_class={class: the dict of `distances_from_stats`}, paed=, hausdorff=, hd_percentile=, assd=,
+        mean_AP=, mean_PA= the nan-aware means over the classes).  mode "sets": distances between the whole pixel sets of a
+        class (the reference's PAED); "borders": between their 4-neighbour borders (the surface form of MedPy's hd / hd95 /
+        assd).  classes=None: range(num_classes).  percentile: 0..100, at most one decimal (95 = HD95)."""
+        if mode not in DISTANCE_MODES:
+            raise ValueError(f"mode must be one of {sorted(DISTANCE_MODES)}, got {mode!r}")
+        num, den = percentile_fraction(percentile)
+        classes = list(range(self.num_classes)) if classes is None else [int(c) for c in classes]
+        si, sf = self.distance_stats(pred, gt, classes, DISTANCE_MODES[mode], num, den)
+        rows = distances_from_stats(si.cpu().numpy(), sf.cpu().numpy(), num, den)
+        out = []
+        for row in rows:
+            d = dict(per_class=dict(zip(classes, row)))
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)   # all-nan -> nan, as the overlap means
+                for key in DISTANCE_KEYS:
+                    d[key] = float(np.nanmean([r[key] for r in row]))
+            out.append(d)
+        return out
+
     def evaluate(self, pred: torch.Tensor, gt: torch.Tensor) -> List[dict]:
         c = self.counts(pred, gt).cpu().numpy()
         px = int(pred.shape[1] * pred.shape[2])
@@ -100,4 +226,20 @@ def write_metrics_csv(path: str, rows: Sequence[Sequence]) -> None:
     with open(path, mode="w", newline="") as f:
         w = csv.writer(f)
         w.writerow(CSV_COLUMNS)
+        w.writerows(rows)
+
+
+def distance_csv_row(model_info: Sequence, batch_num: int, image_idx: int, mode: str, percentile, m: dict) -> list:
+    """One row of <model>_distance_metrics.csv from one image's dict of `Evaluator.distance_metrics`; Per_Class holds
+    class:paed:hausdorff:hd_percentile:assd for every class present in either map, joined by "|"."""
+    per = "|".join(f"{c}:{r['paed']:.6g}:{r['hausdorff']:.6g}:{r['hd_percentile']:.6g}:{r['assd']:.6g}"
+                   for c, r in m["per_class"].items() if r["n"] or r["m"])
+    return [model_info[0], model_info[1], batch_num, image_idx, mode, percentile, m["paed"], m["hausdorff"],
+            m["hd_percentile"], m["assd"], per]
+
+
+def write_distance_csv(path: str, rows: Sequence[Sequence]) -> None:
+    with open(path, mode="w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(DISTANCE_CSV_COLUMNS)
         w.writerows(rows)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import synth
-from .metrics import Evaluator, csv_row, write_metrics_csv
+from .metrics import Evaluator, csv_row, distance_csv_row, write_distance_csv, write_metrics_csv
 
 
 def checkpoint_epoch(path: str) -> Optional[int]:
@@ -131,14 +131,18 @@ def run_validation(model, batches, device) -> dict:
     return {k: float(torch.stack([t.to("cpu") for t in v]).mean()) for k, v in acc.items()}
 
 
-def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device) -> List[list]:
+def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
+                    distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
+                    percentile=95) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
-    the GPU (fused sigmoid -> argmax mask, vitseg_eval_counts)."""
+    the GPU (fused sigmoid -> argmax mask, vitseg_eval_counts).  distance_mode "sets" / "borders": the boundary distances of
+    every image (Evaluator.distance_metrics: PAED, Hausdorff, its percentile, ASSD) go to a second file, distance_csv_path
+    (default: <csv_path minus "_metrics.csv">_distance_metrics.csv); the first file is the same with and without it."""
     seg = getattr(model, "model", model)
     ev = Evaluator(num_classes, device)
-    rows = []
+    rows, drows = [], []
     model.eval()
     for bn, batch in enumerate(batches):
         if bn >= num_batches:
@@ -153,6 +157,14 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         gt = gt.reshape(gt.shape[0], gt.shape[-2], gt.shape[-1])
         for idx, m in enumerate(ev.evaluate(mask, gt)):
             rows.append(csv_row(model_info, bn, idx, m, per_image))
+        if distance_mode is not None:
+            for idx, m in enumerate(ev.distance_metrics(mask, gt, mode=distance_mode, percentile=percentile)):
+                drows.append(distance_csv_row(model_info, bn, idx, distance_mode, percentile, m))
     os.makedirs(os.path.dirname(os.path.abspath(csv_path)), exist_ok=True)
     write_metrics_csv(csv_path, rows)
+    if distance_mode is not None:
+        if distance_csv_path is None:
+            stem = csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
+            distance_csv_path = stem + "_distance_metrics.csv"
+        write_distance_csv(distance_csv_path, drows)
     return rows
