@@ -568,6 +568,42 @@ int vitseg_distance_stats(const uint8_t* pred, const uint8_t* gt, int n, int H, 
                           int pct_num, int pct_den, int64_t* stats_i, double* stats_f, void* scratch, size_t scratch_bytes,
                           void* stream);
 
+/* ---- skeletons of binary masks and the crack statistics on them: centre-line Dice (clDice), crack length and width
+ *      (replaces CrackSeg.skeletonize = skimage.morphology.skeletonize per image on the host, model/PAED/segmentation.py:89-111) ----
+ * The contract is the published algorithm, T. Y. Zhang and C. Y. Suen, "A Fast Parallel Algorithm for Thinning Digital
+ * Patterns", CACM 1984: a non-zero byte is a mask pixel, pixels outside the image are background; neighbours clockwise from
+ * north P2 = N .. P9 = NW; B = the set neighbours, A = the 0 -> 1 steps in P2, P3, ..., P9, P2; a pass is sub-iteration 1 then
+ * 2, each deciding for all pixels from the state before it; a set pixel is deleted when 2 <= B <= 6, A = 1 and
+ * (1) P2 P4 P6 = 0 and P4 P6 P8 = 0, (2) P2 P4 P8 = 0 and P2 P6 P8 = 0; the loop stops after the first pass that deleted
+ * nothing.  Its quirks are part of the contract: an isolated 2 x 2 square vanishes, a full rectangle thins to a short
+ * segment or a single pixel.
+ * vitseg_skeleton: mask uint8 [n, H, W] -> skeleton uint8 [n, H, W] of 0 / 1 (it may alias nothing); passes (optional) int32
+ *   [n]: the passes run per plane, counting the final one that deleted nothing.
+ * route: 0 automatic, 1 resident (one workgroup per plane, the packed plane in LDS, one launch, NO host synchronisation;
+ *   taken while 4 ((H + 2) (ceil(W / 32) + 1) + 4) bytes fit min(the device's shared memory per block, 160 KiB)), 2 global
+ *   (packed planes in the scratch, one launch per sub-iteration; the host reads a convergence word every 16 passes, so this
+ *   route SYNCHRONISES `stream`).  Route 0 takes the resident route whenever the plane fits it.
+ * vitseg_skeleton_stats: pred, gt uint8 [n, H, W] class maps; classes: K label values 0..255 in HOST memory.  Per image and
+ *   class c, G = {gt == c}, P = {pred == c}, S_X = the skeleton of X, d2_X(x) = the exact squared distance from a pixel x of X
+ *   to the nearest pixel outside X (vitseg_sdf's "int" field before the root, its virtual point (-1, 0) included when X is the
+ *   whole image).
+ *   stats_i int64 [n, K, 10] (device): |G|, |P|, |S_G|, |S_P|, |S_G n P|, |S_P n G|, max d2_G over S_G, max d2_P over S_P
+ *   (-1 when the skeleton is empty), the end points of S_G and of S_P (skeleton pixels with exactly one set 8-neighbour).
+ *   stats_f double [n, K, 2] (device): the sum over S_G of sqrt((double) d2_G), the same over S_P.
+ *   Classes are processed one after another on `stream`, 2 n planes at a time.
+ * scratch: the matching *_scratch_bytes(n, H, W, route) device bytes, with the same route (every word read is written within
+ * the call).  The integers come from order-independent integer operations and the sums are added in an order fixed by H * W:
+ * the same bits on every call and by either route, and per image the same bits in any batch.
+ * VITSEG_EINVAL: null pointer (passes excepted), route outside 0..2, a class value outside 0..255; VITSEG_ESHAPE: H or W
+ * outside 1..16384, n outside 1..32767, K outside 1..256, route 1 for a plane that does not fit; VITSEG_EWORKSPACE: scratch
+ * smaller than its size function (0 for a bad shape or route).  Nothing is launched when a check fails. */
+size_t vitseg_skeleton_scratch_bytes(int n, int H, int W, int route);
+int vitseg_skeleton(const uint8_t* mask, int n, int H, int W, int route, uint8_t* skeleton, int32_t* passes, void* scratch,
+                    size_t scratch_bytes, void* stream);
+size_t vitseg_skeleton_stats_scratch_bytes(int n, int H, int W, int route);
+int vitseg_skeleton_stats(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, const int32_t* classes, int K,
+                          int route, int64_t* stats_i, double* stats_f, void* scratch, size_t scratch_bytes, void* stream);
+
 /* one Adam step over a flat fp32 buffer (torch.optim.Adam semantics, weight_decay 0, amsgrad off: torch's L2 weight decay,
  * g += weight_decay * p, is not implemented, and FusedAdam refuses a nonzero weight_decay);
  * step is 1-based; gradients are multiplied by grad_scale first (1/world for summed all-reduce). */

@@ -33,6 +33,9 @@ def main():
     ap.add_argument("--distance-metrics", nargs="?", const="sets", choices=["sets", "borders"],
                     help="also write <model>_distance_metrics.csv: PAED, Hausdorff, HD95 and ASSD per image, between the "
                          "pixel sets of each class (sets, the default) or between their borders")
+    ap.add_argument("--crack-metrics", action="store_true",
+                    help="also write <model>_crack_metrics.csv: centre-line Dice, crack length and width per image, from the "
+                         "Zhang-Suen skeletons of every class but the background 0")
     a = ap.parse_args()
     dev = "cuda:0"
     cwd = os.getcwd()
@@ -49,7 +52,7 @@ def main():
         batches = scripts.paed_binary_batches(model.model.cfg, a.num_batches * a.batch_size, a.batch_size, a.data, seed=5)
         rows = scripts.evaluate_to_csv(model, batches, (vid, name, P, D, L, A), os.path.join(cwd, a.out, name, f"{name}_metrics.csv"),
                                        max(a.num_classes, 2), a.num_batches, dev,
-                                       distance_mode=a.distance_metrics)
+                                       distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None)
         print(f"{name}: {len(rows)} images evaluated -> {os.path.join(a.out, name)}")
 
 

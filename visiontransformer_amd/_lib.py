@@ -71,8 +71,13 @@ DICE_EXPORTS = ["vitseg_dice_options_scratch_bytes", "vitseg_ce_dice_loss", "vit
 # boundary-distance statistics of class maps: PAED, Hausdorff, HD95, ASSD (metrics.Evaluator.distance_metrics): bound on first
 # use, the same way
 DISTANCE_EXPORTS = ["vitseg_distance_scratch_bytes", "vitseg_distance_stats"]
+# skeletons by Zhang-Suen thinning and the crack statistics on them: clDice, length, width (skeleton.py,
+# metrics.Evaluator.crack_metrics): bound on first use, the same way
+SKELETON_EXPORTS = ["vitseg_skeleton_scratch_bytes", "vitseg_skeleton", "vitseg_skeleton_stats_scratch_bytes",
+                    "vitseg_skeleton_stats"]
+SKELETON_AUTO, SKELETON_RESIDENT, SKELETON_GLOBAL = 0, 1, 2   # the `route` argument
 _LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
-                 + DICE_EXPORTS + DISTANCE_EXPORTS)
+                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS)
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -218,6 +223,13 @@ def lib() -> C.CDLL:
             l.vitseg_distance_scratch_bytes.restype = sz
             l.vitseg_distance_stats.argtypes = [vp, vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, i32, vp, vp, vp,
                                                 sz, vp]
+        if getattr(l, "vitseg_skeleton_stats", None) is not None:
+            l.vitseg_skeleton_scratch_bytes.argtypes = [i32, i32, i32, i32]
+            l.vitseg_skeleton_scratch_bytes.restype = sz
+            l.vitseg_skeleton.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+            l.vitseg_skeleton_stats_scratch_bytes.argtypes = [i32, i32, i32, i32]
+            l.vitseg_skeleton_stats_scratch_bytes.restype = sz
+            l.vitseg_skeleton_stats.argtypes = [vp, vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp, vp, sz, vp]
         if getattr(l, "vitseg_dbg_gemm_slices", None) is not None:
             l.vitseg_op_linear_f32_thin.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, C.c_float,
                                                     C.c_uint32, C.c_uint32, vp]
@@ -373,6 +385,15 @@ def distance_symbol(name: str):
     fn = getattr(lib(), name, None)
     if fn is None:
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before the boundary-distance metrics): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def skeleton_symbol(name: str):
+    """One of SKELETON_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the skeletons): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
 

@@ -19,12 +19,13 @@
 // (row, column) index, the reference's rule (classes.py:230-235).  The field of an empty plane (sdf.hip's virtual feature) is
 // never read.
 #include "kernels.hpp"
+#include "plane_reduce.hpp"
 
 namespace vitseg {
 namespace {
 
 constexpr int DIST_MAX_SIDE = 16384, DIST_MAX_BATCH = 32767;   // the planes are a batch of 2 n <= 65534 for sdf.hip
-constexpr int CHUNK = 4096;    // pixels per block of the reduce and histogram passes: 256 threads x 4 groups of 4
+constexpr int CHUNK = PLANE_CHUNK;   // pixels per block of the reduce and histogram passes (plane_reduce.hpp)
 constexpr int BINS = 1024;     // 10 key bits per select round
 
 struct Layout {
@@ -95,45 +96,6 @@ __global__ __launch_bounds__(256) void dist_planes_kernel(const unsigned char* _
         if (ca) atomicAdd(&counts[2 * i], ca);
         if (cp) atomicAdd(&counts[2 * i + 1], cp);
     }
-}
-
-// The pixels of one chunk in the order every pass walks them: thread t takes the groups of 4 pixels t, t + 256, t + 512,
-// t + 768 of the chunk; f(index, key index) is called for each source pixel.  vec: P % 4 == 0, the 4 mask bytes are one word.
-template <class F>
-__device__ __forceinline__ void for_source_pixels(const unsigned char* __restrict__ src, int P, int vec, F f) {
-    for (int k = 0; k < 4; ++k) {
-        const int idx0 = blockIdx.x * CHUNK + (k * 256 + threadIdx.x) * 4;
-        if (idx0 >= P) break;
-        if (vec) {
-            const unsigned w = *reinterpret_cast<const unsigned*>(src + idx0);
-            if (w == 0) continue;
-            for (int e = 0; e < 4; ++e)
-                if ((w >> (8 * e)) & 0xffu) f(idx0 + e);
-        } else {
-            const int cnt = min(4, P - idx0);
-            for (int e = 0; e < cnt; ++e)
-                if (src[idx0 + e]) f(idx0 + e);
-        }
-    }
-}
-
-// the sum over a block of 256 threads in a fixed order: butterflies inside each wave, then the 4 waves in turn
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & (WAVE - 1)) == 0) sh[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ int block_max(int v, int* sh) {
-    for (int d = WAVE / 2; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d));
-    if ((threadIdx.x & (WAVE - 1)) == 0) sh[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    const int r = max(max(sh[0], sh[1]), max(sh[2], sh[3]));
-    __syncthreads();
-    return r;
 }
 
 // grid (NB, 2 n): partial sum and maximum of block (chunk b, source plane j)

@@ -205,5 +205,12 @@ size_t distance_scratch_bytes(int n, int H, int W);
 int launch_distance_stats(const unsigned char* pred, const unsigned char* gt, int n, int H, int W, const int* classes, int K,
                           int mode, int pct_num, int pct_den, long long* stats_i, double* stats_f, void* scratch,
                           size_t scratch_bytes, hipStream_t s);
+// skeletons by Zhang-Suen thinning and the crack statistics on them (skeleton.hip: vitseg_skeleton, vitseg_skeleton_stats)
+size_t skeleton_scratch_bytes(int n, int H, int W, int route);
+int launch_skeleton(const unsigned char* mask, int n, int H, int W, int route, unsigned char* skeleton, int* passes,
+                    void* scratch, size_t scratch_bytes, hipStream_t s);
+size_t skeleton_stats_scratch_bytes(int n, int H, int W, int route);
+int launch_skeleton_stats(const unsigned char* pred, const unsigned char* gt, int n, int H, int W, const int* classes, int K,
+                          int route, long long* stats_i, double* stats_f, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 }  // namespace vitseg

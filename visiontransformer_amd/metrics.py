@@ -13,6 +13,11 @@ Boundary distances (`Evaluator.distance_metrics`): how far a predicted region li
 switched off; `vitseg_distance_stats` (csrc/distance.hip) gets the same sums from two exact distance transforms and a masked
 reduction per class, together with the integers behind the Hausdorff distance, its percentiles (HD95, pooled as MedPy's
 `hd95`) and the average symmetric distance.  `distances_from_stats` is the host arithmetic on those numbers.
+
+Cracks (`Evaluator.crack_metrics`): structures one to five pixels wide, for which the overlap metrics barely register whether
+the crack's course was found.  `vitseg_skeleton_stats` (csrc/skeleton.hip) thins the class sets of both maps to their
+Zhang-Suen skeletons and counts what centre-line Dice (clDice), the crack length and the crack width need;
+`crack_from_stats` is the host arithmetic.
 """
 from __future__ import annotations
 
@@ -115,6 +120,51 @@ def distances_from_stats(stats_i, stats_f, pct_num: int, pct_den: int) -> list:
     return out
 
 
+CRACK_KEYS = ("cldice", "cl_precision", "cl_sensitivity", "length_gt", "length_pred", "mean_width_gt", "mean_width_pred",
+              "max_width_gt", "max_width_pred", "endpoints_gt", "endpoints_pred")
+# header of <model>_crack_metrics.csv (--crack-metrics of the evaluation scripts): the nan-aware class means per image
+CRACK_CSV_COLUMNS = ["Model_ID", "Model_Name", "Batch_Num", "Image_Idx", "Mean_clDice", "Mean_CL_Precision",
+                     "Mean_CL_Sensitivity", "Mean_Length_GT", "Mean_Length_Pred", "Mean_Width_GT", "Mean_Width_Pred",
+                     "Per_Class"]
+
+
+def crack_from_stats(stats_i, stats_f) -> list:
+    """stats_i int64 [n, K, 10] and stats_f float64 [n, K, 2] of vitseg_skeleton_stats (include/vitseg.h) -> per image a list
+    of K dicts.  G = the ground truth's pixels of the class, P = the prediction's, S_X the skeleton of X:
+      cl_precision    |S_P n G| / |S_P|: how much of the predicted centre line lies inside the true crack
+      cl_sensitivity  |S_G n P| / |S_G|: how much of the true centre line the prediction covers
+      cldice          their harmonic mean (0 when both are 0)
+      length_gt, length_pred          |S_G|, |S_P|: the crack length in pixels
+      mean_width_gt, mean_width_pred  2 sum sqrt(d2) / |S| - 1: twice the mean distance from the centre line to the edge
+      max_width_gt, max_width_pred    2 sqrt(max d2) - 1
+      endpoints_gt, endpoints_pred    skeleton pixels with exactly one set 8-neighbour
+    and n = |G|, m = |P|.  A ratio whose denominator is 0 is nan, and cldice with it."""
+    si = np.asarray(stats_i, dtype=np.int64)
+    sf = np.asarray(stats_f, dtype=np.float64)
+    if si.ndim != 3 or si.shape[2] != 10 or sf.shape != si.shape[:2] + (2,):
+        raise ValueError(f"stats_i must be [n, K, 10] and stats_f [n, K, 2], got {si.shape} and {sf.shape}")
+    nan = float("nan")
+    out = []
+    for i in range(si.shape[0]):
+        row = []
+        for k in range(si.shape[1]):
+            n, m, sg, sp, sg_p, sp_g, mx_g, mx_p, e_g, e_p = (int(v) for v in si[i, k])
+            prec = sp_g / sp if sp else nan
+            sens = sg_p / sg if sg else nan
+            if not (sp and sg):
+                cld = nan
+            else:
+                cld = 2 * prec * sens / (prec + sens) if prec + sens > 0 else 0.0
+            row.append(dict(n=n, m=m, cldice=cld, cl_precision=prec, cl_sensitivity=sens, length_gt=sg, length_pred=sp,
+                            mean_width_gt=2 * float(sf[i, k, 0]) / sg - 1 if sg else nan,
+                            mean_width_pred=2 * float(sf[i, k, 1]) / sp - 1 if sp else nan,
+                            max_width_gt=2 * math.sqrt(mx_g) - 1 if sg else nan,
+                            max_width_pred=2 * math.sqrt(mx_p) - 1 if sp else nan,
+                            endpoints_gt=e_g, endpoints_pred=e_p))
+        out.append(row)
+    return out
+
+
 class Evaluator:
     """Per-image metrics of uint8 predictions [n, S, S] against label maps of any size, counted on the GPU."""
 
@@ -208,6 +258,60 @@ class Evaluator:
             out.append(d)
         return out
 
+    def skeleton_stats(self, pred: torch.Tensor, gt: torch.Tensor, classes: Sequence[int], route: int = 0):
+        """(stats_i int64 [n, K, 10], stats_f float64 [n, K, 2]) device tensors of vitseg_skeleton_stats for uint8 predictions
+        [n, H, W]; a ground truth of another size is nearest-resized first, as `distance_stats` does.  One enqueue on the
+        current stream; planes too large for the resident route (see skeleton.py) synchronise it."""
+        if pred.dtype != torch.uint8 or pred.dim() != 3:
+            raise ValueError(f"pred must be uint8 [n, H, W], got {pred.dtype} {tuple(pred.shape)}")
+        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
+            raise ValueError("Number of images and masks must be equal!")
+        classes = [int(c) for c in classes]
+        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
+            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
+        pred = pred.to(self.device).contiguous()
+        gt = gt.to(self.device).to(torch.uint8).contiguous()
+        n, H, W = (int(d) for d in pred.shape)
+        K = len(classes)
+        cls = (ctypes.c_int32 * K)(*classes)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            if tuple(gt.shape[1:]) != (H, W):
+                Hg, Wg = (int(d) for d in gt.shape[1:])
+                g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
+                _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
+                                                               self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
+                                                               st))
+                gt = g2
+            nbytes = _lib.skeleton_symbol("vitseg_skeleton_stats_scratch_bytes")(n, H, W, int(route))
+            if nbytes == 0:
+                raise ValueError(f"crack metrics: H and W must lie in 1..16384 and n in 1..32767 (and the plane must fit the "
+                                 f"route asked for), got {n} x {H} x {W}, route {route}")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            si = torch.empty((n, K, 10), dtype=torch.int64, device=self.device)
+            sf = torch.empty((n, K, 2), dtype=torch.float64, device=self.device)
+            _lib.check(_lib.skeleton_symbol("vitseg_skeleton_stats")(pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K,
+                                                                     int(route), si.data_ptr(), sf.data_ptr(),
+                                                                     scratch.data_ptr(), nbytes, st))
+        return si, sf
+
+    def crack_metrics(self, pred: torch.Tensor, gt: torch.Tensor, classes: Optional[Sequence[int]] = None) -> List[dict]:
+        """Per image: dict(per_class={class: the dict of `crack_from_stats`}, cldice=, cl_precision=, ... the nan-aware means
+        over the classes).  classes=None: range(num_classes); for cracks pass the crack classes alone -- the skeleton of a
+        background that fills the image says little and takes as many passes as half its width."""
+        classes = list(range(self.num_classes)) if classes is None else [int(c) for c in classes]
+        si, sf = self.skeleton_stats(pred, gt, classes)
+        rows = crack_from_stats(si.cpu().numpy(), sf.cpu().numpy())
+        out = []
+        for row in rows:
+            d = dict(per_class=dict(zip(classes, row)))
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)   # all-nan -> nan, as the overlap means
+                for key in CRACK_KEYS:
+                    d[key] = float(np.nanmean([float(r[key]) for r in row]))
+            out.append(d)
+        return out
+
     def evaluate(self, pred: torch.Tensor, gt: torch.Tensor) -> List[dict]:
         c = self.counts(pred, gt).cpu().numpy()
         px = int(pred.shape[1] * pred.shape[2])
@@ -242,4 +346,20 @@ def write_distance_csv(path: str, rows: Sequence[Sequence]) -> None:
     with open(path, mode="w", newline="") as f:
         w = csv.writer(f)
         w.writerow(DISTANCE_CSV_COLUMNS)
+        w.writerows(rows)
+
+
+def crack_csv_row(model_info: Sequence, batch_num: int, image_idx: int, m: dict) -> list:
+    """One row of <model>_crack_metrics.csv from one image's dict of `Evaluator.crack_metrics`; Per_Class holds
+    class:cldice:length_gt:length_pred:mean_width_gt:mean_width_pred for every class present in either map, joined by "|"."""
+    per = "|".join(f"{c}:{r['cldice']:.6g}:{r['length_gt']}:{r['length_pred']}:{r['mean_width_gt']:.6g}:{r['mean_width_pred']:.6g}"
+                   for c, r in m["per_class"].items() if r["n"] or r["m"])
+    return [model_info[0], model_info[1], batch_num, image_idx, m["cldice"], m["cl_precision"], m["cl_sensitivity"],
+            m["length_gt"], m["length_pred"], m["mean_width_gt"], m["mean_width_pred"], per]
+
+
+def write_crack_csv(path: str, rows: Sequence[Sequence]) -> None:
+    with open(path, mode="w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(CRACK_CSV_COLUMNS)
         w.writerows(rows)

@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from . import synth
-from .metrics import Evaluator, csv_row, distance_csv_row, write_distance_csv, write_metrics_csv
+from .metrics import (Evaluator, crack_csv_row, csv_row, distance_csv_row, write_crack_csv, write_distance_csv,
+                      write_metrics_csv)
 
 
 def checkpoint_epoch(path: str) -> Optional[int]:
@@ -133,16 +134,20 @@ def run_validation(model, batches, device) -> dict:
 
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
                     distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
-                    percentile=95) -> List[list]:
+                    percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
     the GPU (fused sigmoid -> argmax mask, vitseg_eval_counts).  distance_mode "sets" / "borders": the boundary distances of
     every image (Evaluator.distance_metrics: PAED, Hausdorff, its percentile, ASSD) go to a second file, distance_csv_path
-    (default: <csv_path minus "_metrics.csv">_distance_metrics.csv); the first file is the same with and without it."""
+    (default: <csv_path minus "_metrics.csv">_distance_metrics.csv); the first file is the same with and without it.
+    crack_classes (a list of label values, or True for every class but 0): clDice, crack length and width of every image
+    (Evaluator.crack_metrics) go to crack_csv_path (default: ..._crack_metrics.csv), again beside the unchanged first file."""
     seg = getattr(model, "model", model)
     ev = Evaluator(num_classes, device)
-    rows, drows = [], []
+    rows, drows, crows = [], [], []
+    if crack_classes is True:
+        crack_classes = list(range(1, num_classes))
     model.eval()
     for bn, batch in enumerate(batches):
         if bn >= num_batches:
@@ -160,11 +165,16 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         if distance_mode is not None:
             for idx, m in enumerate(ev.distance_metrics(mask, gt, mode=distance_mode, percentile=percentile)):
                 drows.append(distance_csv_row(model_info, bn, idx, distance_mode, percentile, m))
+        if crack_classes:
+            for idx, m in enumerate(ev.crack_metrics(mask, gt, classes=crack_classes)):
+                crows.append(crack_csv_row(model_info, bn, idx, m))
     os.makedirs(os.path.dirname(os.path.abspath(csv_path)), exist_ok=True)
     write_metrics_csv(csv_path, rows)
+    stem = csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
     if distance_mode is not None:
         if distance_csv_path is None:
-            stem = csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
             distance_csv_path = stem + "_distance_metrics.csv"
         write_distance_csv(distance_csv_path, drows)
+    if crack_classes:
+        write_crack_csv(crack_csv_path or stem + "_crack_metrics.csv", crows)
     return rows
