@@ -756,6 +756,60 @@ int vitseg_window_blend(const float* lowres, const int32_t* origins_y, int ny, c
                         const float* weights, int n, int C, int g, int S, int H, int W, float* logits, uint8_t* mask,
                         void* stream);
 
+/* ---- training augmentation: paired affine warp and colour jitter in one launch ----
+ * A batch of images is warped bilinearly and colour-jittered into the fp32 [n, 3, oh, ow] model input, and up to two label
+ * planes are warped by nearest tap, every plane with its own source size, output size and per-sample matrix table.  All
+ * coordinate arithmetic is integer and every fp32 operation is a single correctly rounded one, so a CPU restatement holds
+ * bit for bit (tests/augment_ref.py).
+ *
+ * Geometry.  Each sample has six int64 Q16 entries M = (m00, m01, m02, m10, m11, m12), which map the centre of output
+ * pixel (x, y) to source coordinates
+ *   U = (m00 (2x+1) + m01 (2y+1) + 2 m02 - 65536) >> 1,   V = (m10 (2x+1) + m11 (2y+1) + 2 m12 - 65536) >> 1
+ * in int64 with an arithmetic (floor) shift; U / 65536 is the source x in pixel-index units, the identity is
+ * (65536, 0, 0, 0, 65536, 0).  On load the kernel clamps m00, m01, m10, m11 to +-2^26 and m02, m12 to +-2^40, so no
+ * table can overflow or index out of bounds, whatever it holds.
+ *
+ * Image taps.  ix = U >> 16, iy = V >> 16, fx = (U & 0xFFFF) >> 8, fy = (V & 0xFFFF) >> 8 (8-bit fractions); the weights
+ * (256-fy)(256-fx), (256-fy) fx, fy (256-fx), fy fx go on the taps (iy, ix), (iy, ix+1), (iy+1, ix), (iy+1, ix+1) in that
+ * order.  VITSEG_AUGMENT_CONSTANT: a tap outside the frame takes the channel's fill; VITSEG_AUGMENT_EDGE: tap indices are
+ * clamped to the frame.
+ *   VITSEG_AUGMENT_U8_NHWC   uint8 [n, H, W, 3]: S = the integer weighted sum (<= 255 * 65536, exact in fp32),
+ *                            v = float(S) / 16711680.0f, one correctly rounded division: the identity gives v / 255 bitwise,
+ *                            what vitseg_preprocess_u8 gives at equal size.  The fill is rintf(fill[c]) clamped to 0..255.
+ *   VITSEG_AUGMENT_F32_NCHW  float32 [n, 3, H, W]: s = ((w00 p00 + w01 p01) + w10 p10) + w11 p11, v = s * 2^-16, every
+ *                            product and sum rounded on its own.  The fill is fill[c] in the source's units.
+ * Colour.  colour: device float32 [n, 12], a 3x4 matrix per sample:
+ *   out_c = fminf(fmaxf(((c0 r + c1 g) + c2 b) + c3, 0), 1), every operation rounded on its own.
+ * A null colour table skips the step: no multiply, no clamp.
+ *
+ * Masks.  num_masks = 0, 1 or 2 descriptors.  Nearest tap jx = (U + 32768) >> 16, jy = (V + 32768) >> 16 with the
+ * descriptor's own matrix table; CONSTANT writes fill_label outside the frame, EDGE clamps.  Source uint8 or int64
+ * [n, h, w], output uint8 or int64 [n, oh, ow] (a label is truncated to a byte as in vitseg_resize_nearest_*).
+ *
+ * matrix, colour and the descriptors' pointers are device memory; masks, fill (float[3], may be null with EDGE) are host
+ * memory read during the call.  Before any launch, each with a vitseg_last_error message and nothing written:
+ * VITSEG_ESHAPE for n <= 0, any extent < 1 or > 16384 or a batch beyond one launch; VITSEG_EINVAL for a null required
+ * pointer, num_masks outside 0..2 or an unknown border / format flag.
+ *
+ * vitseg_augment_matrix (host arithmetic, no HIP call): the Q16 matrix of one (src_h, src_w) -> (dst_h, dst_w) pair from
+ * a normalised 2x3 double affine a = (a00, a01, a02, a10, a11, a12), which maps the output's unit square onto the source's
+ * ((x + 0.5) / dst_w  ->  (source x + 0.5) / src_w):
+ *   rint(65536 [[Ws a00 / Wd, Ws a01 / Hd, Ws a02], [Hs a10 / Wd, Hs a11 / Hd, Hs a12]])
+ * VITSEG_ESHAPE (nothing written) for an extent outside 1..16384 or an entry past the clamp bounds above (a NaN included). */
+enum vitseg_augment_border { VITSEG_AUGMENT_CONSTANT = 0, VITSEG_AUGMENT_EDGE = 1 };
+enum vitseg_augment_format { VITSEG_AUGMENT_U8_NHWC = 0, VITSEG_AUGMENT_F32_NCHW = 1 };
+typedef struct vitseg_augment_mask {
+    const void* src;       /* device: uint8 or int64 [n, h, w] */
+    const int64_t* matrix; /* device: int64 [n, 6] */
+    void* out;             /* device: uint8 or int64 [n, oh, ow] */
+    int32_t src_is_i64, out_is_i64;
+    int32_t h, w, oh, ow;
+} vitseg_augment_mask;
+int vitseg_augment_matrix(const double* affine, int src_h, int src_w, int dst_h, int dst_w, int64_t* matrix);
+int vitseg_augment(const void* images, int image_format, int n, int H, int W, int oh, int ow, const int64_t* matrix,
+                   const float* colour, float* out, const vitseg_augment_mask* masks, int num_masks, int border,
+                   const float* fill, int64_t fill_label, void* stream);
+
 /* ---- measurement hooks (bench.py's roofline object) ----
  * While enabled, vitseg_forward brackets every kernel launch of the hot path with a pair of
  * hipEvents on the launch stream; vitseg_forward_train / vitseg_backward bracket the GEMMs and

@@ -28,6 +28,7 @@ def main():
     ap.add_argument("--patience", type=int, default=3)
     ap.add_argument("--data")
     scripts.add_ce_loss_arguments(ap)
+    scripts.add_augment_arguments(ap)
     ap.add_argument("--ckpt-dir", default="logs/vit-model/version_0/checkpoints")
     ap.add_argument("--resume")
     a = ap.parse_args()
@@ -38,6 +39,7 @@ def main():
     model = LightningViTModel(a.num_classes, P, D, L, A, image_size=a.image_size, device=dev,
                               **scripts.ce_loss_options(a))
     cfg = model.model.cfg
+    model.augment = scripts.augmenter_from_args(a, cfg, dev)
     if a.data:
         blob = torch.load(a.data)
         xs, ys = blob["images"].float(), blob["masks"].long()

@@ -31,12 +31,14 @@ def main():
     ap.add_argument("--data")
     ap.add_argument("--exact-sdf", action="store_true",
                     help="exact SDFs of the synthetic masks (vitseg_sdf) instead of smooth stand-ins")
+    scripts.add_augment_arguments(ap)
     a = ap.parse_args()
     rank, world, local = vdist.init()
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
     model = PAEDTrainer(1, a.patch_size, a.hidden_size, a.layers, a.heads, image_size=a.image_size, precision=a.precision,
                         device=dev)
+    model.augment = scripts.augmenter_from_args(a, model.model.cfg, dev)
     batches = scripts.paed_binary_batches(model.model.cfg, a.batches * a.batch_size, a.batch_size, a.data, seed=rank,
                                           sdf="exact" if a.exact_sdf else "standin")
     log_dir = f"logs/vit-model/version_{a.version}"

@@ -28,12 +28,14 @@ def main():
     ap.add_argument("--version", type=int, default=0)
     ap.add_argument("--resume", help="checkpoint to continue from (default: the latest of --version, if any)")
     ap.add_argument("--data")
+    scripts.add_augment_arguments(ap)
     a = ap.parse_args()
     rank, world, local = vdist.init()
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
     model = LightningViTModel(17, a.patch_size, a.hidden_size, a.layers, a.heads, image_size=a.image_size,
                               precision=a.precision, device=dev)
+    model.augment = scripts.augmenter_from_args(a, model.model.cfg, dev)
     batches = scripts.ce_batches(model.model.cfg, a.batches * a.batch_size, a.batch_size, a.data, first=rank * a.batches * a.batch_size)
     log_dir = f"logs/vit-model/version_{a.version}"
     resume = a.resume or scripts.get_latest_checkpoint(a.version, os.getcwd())

@@ -76,8 +76,13 @@ DISTANCE_EXPORTS = ["vitseg_distance_scratch_bytes", "vitseg_distance_stats"]
 SKELETON_EXPORTS = ["vitseg_skeleton_scratch_bytes", "vitseg_skeleton", "vitseg_skeleton_stats_scratch_bytes",
                     "vitseg_skeleton_stats"]
 SKELETON_AUTO, SKELETON_RESIDENT, SKELETON_GLOBAL = 0, 1, 2   # the `route` argument
+# training augmentation: the paired affine warp + colour jitter launch and its host-side matrix composer (augment.py): bound on
+# first use, the same way
+AUGMENT_EXPORTS = ["vitseg_augment_matrix", "vitseg_augment"]
+AUGMENT_CONSTANT, AUGMENT_EDGE = 0, 1      # enum vitseg_augment_border
+AUGMENT_U8_NHWC, AUGMENT_F32_NCHW = 0, 1   # enum vitseg_augment_format
 _LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
-                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS)
+                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS)
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -97,6 +102,12 @@ class CDiceOptions(C.Structure):
     """struct vitseg_dice_options (include/vitseg.h)."""
     _fields_ = [("ce_weight", C.c_float), ("dice_weight", C.c_float), ("smooth", C.c_float),
                 ("include_background", C.c_int32), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+class CAugmentMask(C.Structure):
+    """struct vitseg_augment_mask (include/vitseg.h)."""
+    _fields_ = [("src", C.c_void_p), ("matrix", C.c_void_p), ("out", C.c_void_p), ("src_is_i64", C.c_int32),
+                ("out_is_i64", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("oh", C.c_int32), ("ow", C.c_int32)]
 
 
 class CConfig(C.Structure):
@@ -252,6 +263,10 @@ def lib() -> C.CDLL:
             for name, args in _dice_argtypes(vp, sz, i32, pcfg).items():
                 getattr(l, name).argtypes = args
             l.vitseg_dice_options_scratch_bytes.restype = sz
+        if getattr(l, "vitseg_augment", None) is not None:
+            l.vitseg_augment_matrix.argtypes = [vp, i32, i32, i32, i32, vp]   # (double[6] in, int64[6] out)
+            l.vitseg_augment.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(CAugmentMask), i32, i32,
+                                         C.POINTER(C.c_float), C.c_int64, vp]
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -396,6 +411,24 @@ def skeleton_symbol(name: str):
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before the skeletons): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
+
+
+def augment_symbol(name: str):
+    """One of AUGMENT_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the training augmentation): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def augment_matrix(affine, src_hw, dst_hw) -> list:
+    """The Q16 int64 matrix (six entries) of one normalised 2x3 affine for one (source, output) size pair
+    (vitseg_augment_matrix); ValueError for an extent outside 1..16384 or an entry past the kernel's clamp bounds."""
+    a = (C.c_double * 6)(*[float(v) for v in affine])
+    out = (C.c_int64 * 6)()
+    check(augment_symbol("vitseg_augment_matrix")(a, int(src_hw[0]), int(src_hw[1]), int(dst_hw[0]), int(dst_hw[1]), out))
+    return list(out)
 
 
 def window_symbol(name: str):

@@ -21,7 +21,7 @@ class LightningViTModel(nn.Module):
     def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, *,
                  interpolate_pos_encoding: bool = False, ignore_index=None, class_weight=None,
                  label_smoothing: float = 0.0, dice_weight: float = 0.0, dice_smooth: float = 1e-6,
-                 dice_include_background: bool = True, **kw):
+                 dice_include_background: bool = True, augment=None, **kw):
         """`interpolate_pos_encoding`: inputs of other (square, multiple-of-P) sizes than `image_size` run with the
         position table resampled to their grid (ViTSegmentationModel.forward); targets are resized to the input's size.
         `ignore_index`, `class_weight`, `label_smoothing`: the arguments of the reference's `nn.CrossEntropyLoss()`
@@ -29,7 +29,10 @@ class LightningViTModel(nn.Module):
         smoothed targets (ViTSegmentationModel.ce_loss); used by the training and the validation step alike.
         `dice_weight` > 0 adds that many times the soft Dice loss of the softmax probabilities to the CE
         (ViTSegmentationModel.ce_dice_loss with `dice_smooth`, `dice_include_background`); both steps then log `*_ce` and
-        `*_dice` beside `*_loss`.  With 0 the steps call exactly what they call without the argument."""
+        `*_dice` beside `*_loss`.  With 0 the steps call exactly what they call without the argument.
+        `augment`: an `augment.Augmenter`; the training step (alone) warps and colour-jitters the batch with it, the mask
+        going straight to the input's size as the class bytes the fused loss reads (one launch, in place of `_resize_target`).
+        With None the steps launch exactly what they launch without the argument."""
         super().__init__()
         self.model = ViTSegmentationModel(num_classes, patch_size, hidden_size, num_hidden_layers,
                                           num_attention_heads, **kw)
@@ -42,6 +45,7 @@ class LightningViTModel(nn.Module):
         if self.dice_weight != 0.0:
             check_dice_options(num_classes, dice_weight, 1.0, dice_smooth, dice_include_background)
         self.dice_smooth, self.dice_include_background = dice_smooth, bool(dice_include_background)
+        self.augment = augment
         self.logged = {}
 
     def forward(self, x):
@@ -60,8 +64,9 @@ class LightningViTModel(nn.Module):
             return self._prep.targets(y, tuple(size), dtype=dtype)
         return F.interpolate(y.unsqueeze(1).float(), size=size, mode="nearest").squeeze(1).to(dtype)
 
-    def _loss(self, batch, grad_scale=None, stage=None):
-        """`stage` ("train" / "valid"): where the CE and Dice terms are logged when the Dice term is on."""
+    def _loss(self, batch, grad_scale=None, stage=None, augment=None):
+        """`stage` ("train" / "valid"): where the CE and Dice terms are logged when the Dice term is on.  `augment`: the
+        Augmenter that produces the step's input and targets from the batch."""
         x, y = batch
         S = self.model.cfg.image_size  # the reference hard-codes (224, 224) = its image_size (classes.py:278)
         if self.interpolate_pos_encoding:
@@ -69,7 +74,10 @@ class LightningViTModel(nn.Module):
         # uint8 class indices: what the fused CE kernels read (a quarter of the int64 bytes); C <= 32 in training.  An
         # ignored label that a byte cannot hold (torch's -100) keeps the targets int64
         wide = self.ignore_index is not None and not 0 <= self.ignore_index <= 255
-        y = self._resize_target(y.to(x.device, non_blocking=True), size=(S, S), dtype=torch.long if wide else torch.uint8)
+        if augment is not None:   # image and mask warped by one draw; the mask lands at the augmenter's output size
+            x, y = augment.apply(x, y, mask_size=augment.S, mask_dtype=torch.long if wide else torch.uint8)
+        else:
+            y = self._resize_target(y.to(x.device, non_blocking=True), size=(S, S), dtype=torch.long if wide else torch.uint8)
         opts = {}
         if self.ignore_index is not None or self.class_weight is not None or self.label_smoothing != 0:
             opts = dict(ignore_index=self.ignore_index, class_weight=self.class_weight, label_smoothing=self.label_smoothing)
@@ -86,7 +94,7 @@ class LightningViTModel(nn.Module):
 
     # `logged` holds DEVICE scalars: reading one (float(...)) is the only host sync, and only the caller decides when
     def training_step(self, batch, batch_idx, grad_scale=None):
-        loss = self._loss(batch, grad_scale, stage="train")
+        loss = self._loss(batch, grad_scale, stage="train", augment=self.augment)
         self.logged["train_loss"] = loss.detach()
         return loss
 

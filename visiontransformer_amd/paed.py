@@ -170,10 +170,13 @@ def iou_score(preds, targets, num_classes=17):
 
 
 class _Base(nn.Module):
-    def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, **kw):
+    def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, augment=None, **kw):
+        """`augment`: an `augment.Augmenter` the training step (alone) applies to its batch; None: the steps launch exactly
+        what they launch without the argument."""
         super().__init__()
         self.model = ViTSegmentationModel(num_classes, patch_size, hidden_size, num_hidden_layers,
                                           num_attention_heads, **kw)
+        self.augment = augment
         self.logged = {}
 
     def forward(self, x):
@@ -203,12 +206,15 @@ class LightningViTModel(_Base):
     """model/PAED/classes.py:415-487 (the class count is forced to 17 there, :418)."""
 
     def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, **kw):
-        super().__init__(17, patch_size, hidden_size, num_hidden_layers, num_attention_heads, **kw)
+        super().__init__(17, patch_size, hidden_size, num_hidden_layers, num_attention_heads, **kw)   # (`augment` rides in kw)
         self.num_classes = 17
 
-    def _step(self, batch, tag):
+    def _step(self, batch, tag, augment=None):
         x, y = batch
-        y = self._resize_target(y)
+        if augment is not None:   # image and class map warped by one draw, the map straight to the input's size
+            x, y = augment.apply(x, y, mask_size=augment.S, mask_dtype=torch.long)
+        else:
+            y = self._resize_target(y)
         logits = self.forward(x)
         # softmax + one-hot + blur + weighting and their gradient run in libvitseg (csrc/paed_loss.hip)
         loss = paed_multiclass_loss_fused(logits, y)
@@ -217,7 +223,7 @@ class LightningViTModel(_Base):
         return loss
 
     def training_step(self, batch, batch_idx):
-        return self._step(batch, "train")
+        return self._step(batch, "train", augment=self.augment)
 
     def validation_step(self, batch, batch_idx):
         with torch.no_grad():
@@ -229,11 +235,18 @@ class LightningViTModel(_Base):
 
 
 class PAEDTrainer(_Base):
-    """model/PAED/classes.py:490-701; scripts build it with num_classes=1 (model/PAED/ViTscript.py:66)."""
+    """model/PAED/classes.py:490-701; scripts build it with num_classes=1 (model/PAED/ViTscript.py:66).
+    `augment`: an `augment.Augmenter`; the training step (alone) warps the batch's images and masks with it and recomputes
+    the signed-distance targets from the warped masks (Augmenter.paed_binary), in place of the batch's own.  With None the
+    steps launch exactly what they launch without the argument."""
 
-    def _forward_step_paed(self, batch, batch_idx, tag="train"):
+    def _forward_step_paed(self, batch, batch_idx, tag="train", augment=None):
         images, masks, sdf_ext, sdf_int = batch
-        masks = self._resize_target(masks).float()
+        if augment is not None:   # the mask is already float 0 / 1 at the augmenter's output size
+            images, masks, sdf_ext, sdf_int = augment.paed_binary(images, masks)
+            masks = masks[:, 0]
+        else:
+            masks = self._resize_target(masks).float()
         # sigmoid, BCE + 0.1 Dice + 5 |soft PAED| (:679-681), their gradient and the confusion counts: csrc/paed_binary.hip
         loss, terms = paed_binary_loss_fused(self.forward(images), masks, sdf_ext, sdf_int)
         with torch.no_grad():
@@ -248,7 +261,7 @@ class PAEDTrainer(_Base):
         return loss, acc, iou, dice, prec, rec
 
     def training_step(self, batch, batch_idx):
-        return self._forward_step_paed(batch, batch_idx, "train")[0]
+        return self._forward_step_paed(batch, batch_idx, "train", augment=self.augment)[0]
 
     def validation_step(self, batch, batch_idx):
         with torch.no_grad():

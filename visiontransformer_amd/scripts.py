@@ -73,6 +73,52 @@ def ce_loss_options(a) -> dict:
     return kw
 
 
+_AUGMENT_PRESETS = {
+    "flip": dict(hflip=0.5, vflip=0.5, rot90=True),
+    "geom": dict(hflip=0.5, vflip=0.5, rot90=True, rotate=15.0, scale=(0.8, 1.25), translate=0.1),
+    "full": dict(hflip=0.5, vflip=0.5, rot90=True, rotate=15.0, scale=(0.8, 1.25), translate=0.1, brightness=0.2,
+                 contrast=0.2, saturation=0.2),
+}
+
+
+def add_augment_arguments(ap) -> None:
+    """The augmentation options of the training scripts (augment.Augmenter): a preset and overrides of its ranges."""
+    ap.add_argument("--augment", choices=["none", "flip", "geom", "full"], default="none",
+                    help="none: the pixels as they are (the reference); flip: flips + quarter turns; geom: + rotation, scale "
+                         "and translate jitter; full: + brightness / contrast / saturation jitter")
+    ap.add_argument("--aug-rotate", type=float, default=None, help="degrees: the angle is uniform in [-v, v]")
+    ap.add_argument("--aug-scale", default=None, help="LO,HI: the zoom factor is uniform in [LO, HI]")
+    ap.add_argument("--aug-translate", type=float, default=None, help="fraction of the frame, uniform in [-v, v] per axis")
+    ap.add_argument("--aug-brightness", type=float, default=None)
+    ap.add_argument("--aug-contrast", type=float, default=None)
+    ap.add_argument("--aug-saturation", type=float, default=None)
+    ap.add_argument("--aug-seed", type=int, default=0)
+
+
+def augmenter_from_args(a, cfg, device):
+    """The Augmenter the flags of `add_augment_arguments` describe for a model of configuration `cfg`, or None for
+    `--augment none`.  With `--ignore-index` the out-of-frame pixels carry that label and do not count in the loss
+    (border "constant"); otherwise the frame's edge is repeated (border "edge")."""
+    if a.augment == "none":
+        return None
+    from .augment import Augmenter
+    kw = dict(_AUGMENT_PRESETS[a.augment])
+    for name in ("rotate", "translate", "brightness", "contrast", "saturation"):
+        v = getattr(a, "aug_" + name)
+        if v is not None:
+            kw[name] = v
+    if a.aug_scale is not None:
+        try:
+            lo, hi = (float(v) for v in a.aug_scale.split(","))
+        except ValueError:
+            raise ValueError(f"--aug-scale expects LO,HI, got {a.aug_scale!r}") from None
+        kw["scale"] = (lo, hi)
+    ignore = getattr(a, "ignore_index", None)
+    if ignore is not None:
+        kw.update(border="constant", fill_label=ignore)
+    return Augmenter(cfg.image_size, device=device, seed=a.aug_seed, **kw)
+
+
 def ce_batches(cfg, n_images: int, batch_size: int, data: Optional[str] = None, seed: int = 0, first: int = 0):
     """[(images [b,3,S,S] float, masks [b,256,256] long)]: StructuralDamageDataset items (model/CE/classes.py:60-89)."""
     if data:
