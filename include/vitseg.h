@@ -810,6 +810,45 @@ int vitseg_augment(const void* images, int image_format, int n, int H, int W, in
                    const float* colour, float* out, const vitseg_augment_mask* masks, int num_masks, int border,
                    const float* fill, int64_t fill_label, void* stream);
 
+/* ---- test-time augmentation: flipped, quarter-turned and rescaled views merged in one launch ----
+ * The model runs on K views of a square batch, each forwarded on its own to the low-res head output
+ * (vitseg_forward_lowres at the view's size), and the blend brings every view back to the image's frame, averages and
+ * decides.  The reference has no counterpart: its scripts look at every image once (testViTModel.py:92-126).
+ *
+ * A view's op is 0..7: f = op >> 2 is a horizontal flip applied first, r = op & 3 the number of counter-clockwise quarter
+ * turns:   view(X, op) = rot90(f ? flip(X, x axis) : X, r),   unview = its inverse
+ * (op 4 the horizontal flip, op 6 the vertical flip, op 2 the half turn).  vitseg_tta_affine (host arithmetic, no HIP
+ * call) writes the normalised 2x3 affine of view(., op) as vitseg_augment_matrix takes it; every entry is exact, so the
+ * Q16 matrix of an equal-size pair has zero fractions and vitseg_augment with it is a bit-exact permutation.
+ * VITSEG_EINVAL: a null pointer or an op outside 0..7.
+ *
+ * vitseg_tta_blend: views = K descriptors in host memory, read during the call; lowres = device fp32 [n, C, g, g] in the
+ * view's OWN frame (the grids g may differ between views).  Output: merged fp32 [n, C, S, S] and / or mask uint8
+ * [n, S, S] (either may be NULL; both NULL: VITSEG_EINVAL).  Per pixel (y, x), class c and view k, with U_k =
+ * the bilinear upsample of lowres_k to S x S by the decoder tail's arithmetic (scale g_k / S, taps
+ * src = max(scale * (d + 0.5) - 0.5, 0), row = fma(a, wx0, b * wx1) along the view's own x axis, fma(top, wy0, bot * wy1)):
+ *   u_k = unview(U_k, op_k)[y, x], read at the view-frame position of (y, x) -- with x' = f ? S - 1 - x : x that is
+ *         r = 0: (y, x')   r = 1: (S - 1 - x', y)   r = 2: (S - 1 - y, S - 1 - x')   r = 3: (x', S - 1 - y);
+ *   t_k = u_k (mode 0: mean of logits)  or  sigmoid(u_k) as ATen computes it for fp32 (mode 1: mean of probabilities);
+ *   K == 1:    result = t_1   (the weight plays no part);
+ *   otherwise: acc = 0; in view order acc = fma(w_k, t_k, acc);  result = acc / Wsum   (IEEE division),
+ *              Wsum = the fp32 sum of the weights, added in view order.
+ *   mask = the first maximal index of sigmoid(result_c) (mode 0) or of result_c (mode 1).
+ * Every operation is a single correctly rounded fp32 one, so a CPU restatement holds bit for bit (tests/tta_ref.py).
+ * No atomics and no scratch; every output element is written exactly once; no per-view full-size tensor exists.
+ * Each with a vitseg_last_error text and nothing launched -- VITSEG_EINVAL: a null pointer, K outside 1..16, an op outside
+ * 0..7, a weight that is not finite and > 0 (or weights whose fp32 sum is not finite), mode not 0 / 1; VITSEG_ESHAPE:
+ * C outside 1..255, S or a g outside 1..4096, n outside 1..65535. */
+typedef struct vitseg_tta_view {
+    const float* lowres; /* device: fp32 [n, C, g, g] */
+    int32_t g;
+    int32_t op;
+    float weight;
+} vitseg_tta_view;
+int vitseg_tta_affine(int op, double* affine6);
+int vitseg_tta_blend(const vitseg_tta_view* views, int K, int n, int C, int S, int mode, float* merged, uint8_t* mask,
+                     void* stream);
+
 /* ---- measurement hooks (bench.py's roofline object) ----
  * While enabled, vitseg_forward brackets every kernel launch of the hot path with a pair of
  * hipEvents on the launch stream; vitseg_forward_train / vitseg_backward bracket the GEMMs and

@@ -3,7 +3,7 @@
 
     python model/CE/testViTModel.py IMAGE [--model-id 0] [--num-classes 17] [--checkpoint x.ckpt]
                                           [--image-size 224] [--precision fp32|bf16] [--out mask.png]
-                                          [--boxes boxes.json]
+                                          [--boxes boxes.json] [--tta d4] [--tta-sizes 160,224] [--tta-merge probs]
 
 Without --checkpoint the weights are random (the reference's checkpoints are private)."""
 import argparse
@@ -12,6 +12,7 @@ import numpy as np
 
 from classes import LightningViTModel  # noqa: F401  (same import the reference script uses)
 from visiontransformer_amd.predict import load_model, predict
+from visiontransformer_amd.tta import parse_sizes
 
 
 def main():
@@ -25,15 +26,20 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--boxes", help="write the predicted regions' boxes, {class: [[y_min, x_min, y_max, x_max], ...]} for "
                                     "every class present but 0 (the reference's boxes panel), to this JSON file")
+    ap.add_argument("--tta", help='test-time augmentation: "hflip", "flip" or "d4" -- the mask is merged from flipped / '
+                                  "quarter-turned views (default: one look)")
+    ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
+    ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"], help="mean of the views' logits or of their sigmoids")
     a = ap.parse_args()
+    tta = dict(tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge)
     model = load_model(a.model_id, a.num_classes, a.checkpoint, image_size=a.image_size, precision=a.precision)
     if a.boxes:
         import json
-        mask, boxes = predict(a.image, model, return_boxes=True)
+        mask, boxes = predict(a.image, model, return_boxes=True, **tta)
         with open(a.boxes, "w") as f:
             json.dump({str(c): [list(b) for b in bs] for c, bs in boxes.items()}, f)
     else:
-        mask = predict(a.image, model)
+        mask = predict(a.image, model, **tta)
     print("classes present:", np.unique(mask).tolist(), "mask shape:", mask.shape)
     if a.out:
         from PIL import Image

@@ -14,6 +14,7 @@ import torch
 from classes import PAEDTrainer
 from visiontransformer_amd import scripts
 from visiontransformer_amd.predict import CONFIGURATIONS
+from visiontransformer_amd.tta import parse_sizes
 
 
 def main():
@@ -36,6 +37,10 @@ def main():
     ap.add_argument("--crack-metrics", action="store_true",
                     help="also write <model>_crack_metrics.csv: centre-line Dice, crack length and width per image, from the "
                          "Zhang-Suen skeletons of every class but the background 0")
+    ap.add_argument("--tta", help='test-time augmentation: "hflip", "flip" or "d4" -- the mask is merged from flipped / '
+                                  "quarter-turned views (default: one look)")
+    ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
+    ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"], help="mean of the views' logits or of their sigmoids")
     a = ap.parse_args()
     dev = "cuda:0"
     cwd = os.getcwd()
@@ -52,7 +57,8 @@ def main():
         batches = scripts.paed_binary_batches(model.model.cfg, a.num_batches * a.batch_size, a.batch_size, a.data, seed=5)
         rows = scripts.evaluate_to_csv(model, batches, (vid, name, P, D, L, A), os.path.join(cwd, a.out, name, f"{name}_metrics.csv"),
                                        max(a.num_classes, 2), a.num_batches, dev,
-                                       distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None)
+                                       distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None,
+                                       tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge)
         print(f"{name}: {len(rows)} images evaluated -> {os.path.join(a.out, name)}")
 
 

@@ -81,8 +81,12 @@ SKELETON_AUTO, SKELETON_RESIDENT, SKELETON_GLOBAL = 0, 1, 2   # the `route` argu
 AUGMENT_EXPORTS = ["vitseg_augment_matrix", "vitseg_augment"]
 AUGMENT_CONSTANT, AUGMENT_EDGE = 0, 1      # enum vitseg_augment_border
 AUGMENT_U8_NHWC, AUGMENT_F32_NCHW = 0, 1   # enum vitseg_augment_format
+# test-time augmentation (model.predict_mask_tta): the exact affine of a flip / quarter-turn view and the launch that merges the
+# views' low-res maps: bound on first use, the same way
+TTA_EXPORTS = ["vitseg_tta_affine", "vitseg_tta_blend"]
+TTA_LOGITS, TTA_PROBS = 0, 1   # the `mode` argument of vitseg_tta_blend
 _LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
-                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS)
+                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS)
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -108,6 +112,11 @@ class CAugmentMask(C.Structure):
     """struct vitseg_augment_mask (include/vitseg.h)."""
     _fields_ = [("src", C.c_void_p), ("matrix", C.c_void_p), ("out", C.c_void_p), ("src_is_i64", C.c_int32),
                 ("out_is_i64", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("oh", C.c_int32), ("ow", C.c_int32)]
+
+
+class CTTAView(C.Structure):
+    """struct vitseg_tta_view (include/vitseg.h)."""
+    _fields_ = [("lowres", C.c_void_p), ("g", C.c_int32), ("op", C.c_int32), ("weight", C.c_float)]
 
 
 class CConfig(C.Structure):
@@ -267,6 +276,9 @@ def lib() -> C.CDLL:
             l.vitseg_augment_matrix.argtypes = [vp, i32, i32, i32, i32, vp]   # (double[6] in, int64[6] out)
             l.vitseg_augment.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(CAugmentMask), i32, i32,
                                          C.POINTER(C.c_float), C.c_int64, vp]
+        if getattr(l, "vitseg_tta_blend", None) is not None:
+            l.vitseg_tta_affine.argtypes = [i32, vp]   # (double[6] out)
+            l.vitseg_tta_blend.argtypes = [C.POINTER(CTTAView), i32, i32, i32, i32, i32, vp, vp, vp]
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -428,6 +440,24 @@ def augment_matrix(affine, src_hw, dst_hw) -> list:
     a = (C.c_double * 6)(*[float(v) for v in affine])
     out = (C.c_int64 * 6)()
     check(augment_symbol("vitseg_augment_matrix")(a, int(src_hw[0]), int(src_hw[1]), int(dst_hw[0]), int(dst_hw[1]), out))
+    return list(out)
+
+
+def tta_symbol(name: str):
+    """One of TTA_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before test-time augmentation): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def tta_affine(op: int) -> list:
+    """The normalised 2x3 affine (six doubles) of view(., op) for `augment_matrix` (vitseg_tta_affine); ValueError for an
+    op outside 0..7."""
+    out = (C.c_double * 6)()
+    if tta_symbol("vitseg_tta_affine")(int(op), out):
+        raise ValueError(lib().vitseg_last_error().decode(errors="replace"))
     return list(out)
 
 

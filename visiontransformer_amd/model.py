@@ -665,7 +665,113 @@ class ViTSegmentationModel(nn.Module):
                                                                  torch.cuda.current_stream().cuda_stream))
         return (mask, logits) if want_logits and want_mask else (mask if want_mask else logits)
 
-    _CE_CACHE_ENTRIES = 8   # device weight vectors / scratch buffers kept per model, least recently used first out
+    # ------------------------------------------------------------------ test-time augmentation
+    @torch.no_grad()
+    def predict_mask_tta(self, x: torch.Tensor, tta="d4", sizes=None, weights=None, merge: str = "logits",
+                         return_merged: bool = False):
+        """Masks by test-time augmentation: the model runs on flipped, quarter-turned and rescaled copies of the batch (the
+        views), and ONE launch brings every view's low-resolution head output back to the image's frame -- upsampled on
+        the fly with the decoder tail's arithmetic --, averages them and takes sigmoid -> argmax (vitseg_tta_blend,
+        include/vitseg.h); no per-view full-size tensor is materialised.
+        x: fp32 [B, 3, S, S] or uint8 [B, S, S, 3] (decoded bytes, converted as ToTensor does), square, S the output size
+        -> uint8 [B, S, S], and with `return_merged` the merged fp32 [B, C, S, S] (logits, or probabilities for
+        merge="probs").
+        `tta`: "none" (op 0), "hflip" (0, 4), "flip" (0, 2, 4, 6), "d4" (0..7) or a sequence of ops; an op's `op >> 2` is a
+        horizontal flip applied first and `op & 3` the number of counter-clockwise quarter turns (tta.py).  `sizes`: the
+        sides the views are resampled to, multiples of the patch size, default (S,); `weights`: one per size, default 1.
+        The views are sizes x ops, size-major.  `merge`: "logits" (the mean of the views' logits) or "probs" (the mean of
+        their sigmoids).
+        The view images come from the training augmentation's launch (vitseg_augment, edge border, no colour step): flips
+        and quarter turns at the image's own size are bit-exact permutations; a rescale is that kernel's plain two-tap
+        bilinear WITHOUT anti-aliasing, so sizes below half the input alias.  Every view is forwarded on its own at the
+        caller's batch (vitseg_forward_lowres: the kernel route of `predict_mask` at that size), so tta="none" reproduces
+        `predict_mask` bit for bit.  Everything is enqueued on the current stream; the host never waits."""
+        from . import tta as _tta
+        _tta.merge_mode(merge)   # (refused before anything is launched)
+        plan = self._tta_lowres(x, tta, sizes, weights)
+        return self._tta_blend(plan, merge, bool(return_merged), True)
+
+    def _tta_matrix(self, op: int, src: int, dst: int, n: int) -> torch.Tensor:
+        """Device int64 [n, 6]: the Q16 matrix of view(., op) from a src x src image to a dst x dst view, once per sample;
+        cached, so a repeated call uploads nothing."""
+        cache = self.__dict__.setdefault("_tta_tabs", {})
+        key = (op, src, dst, n)
+        tab = cache.get(key)
+        if tab is None:
+            if len(cache) >= 64:
+                cache.clear()
+            m = _lib.augment_matrix(_lib.tta_affine(op), (src, src), (dst, dst))
+            tab = cache[key] = torch.tensor([m] * n, dtype=torch.int64).to(self.arena.device)
+        return tab
+
+    def _tta_view_image(self, x: torch.Tensor, u8: bool, op: int, size: int, out: torch.Tensor) -> torch.Tensor:
+        """view(x, op) resampled to size x size as fp32 NCHW, by one vitseg_augment launch into `out`.  An fp32 batch's
+        identity view at its own size is the batch itself: no launch."""
+        B, S = int(x.shape[0]), int(x.shape[2])
+        if op == 0 and size == S and not u8:
+            return x
+        tab = self._tta_matrix(op, S, size, B)
+        none = (_lib.CAugmentMask * 1)()
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.augment_symbol("vitseg_augment")(
+                x.data_ptr(), _lib.AUGMENT_U8_NHWC if u8 else _lib.AUGMENT_F32_NCHW, B, S, S, size, size, tab.data_ptr(),
+                None, out.data_ptr(), none, 0, _lib.AUGMENT_EDGE, None, 0, torch.cuda.current_stream().cuda_stream))
+        return out
+
+    def _tta_lowres(self, x: torch.Tensor, tta, sizes, weights) -> dict:
+        """The views of `x` built and forwarded one by one to their low-res maps [B, C, g, g]; returns what `_tta_blend`
+        needs (tools/tta_probe.py times the two halves apart)."""
+        from . import tta as _tta
+        cfg = self.cfg
+        u8 = x.dtype == torch.uint8
+        if x.dim() != 4 or (x.shape[-1] if u8 else x.shape[1]) != cfg.num_channels or x.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"expected [B, {cfg.num_channels}, S, S] fp32 or [B, S, S, {cfg.num_channels}] uint8, got "
+                             f"{x.dtype} {tuple(x.shape)}")
+        H, W = (int(x.shape[1]), int(x.shape[2])) if u8 else (int(x.shape[2]), int(x.shape[3]))
+        if H != W:
+            raise ValueError(f"test-time augmentation needs a square input, got {H}*{W}.")
+        if int(x.shape[0]) < 1:
+            raise ValueError("empty batch")
+        views = _tta.view_list(tta, sizes, weights, H, cfg.patch_size)
+        if not x.is_cuda or x.device != self.arena.device:
+            raise RuntimeError("ViTSegmentationModel runs on the MI355X only: move the model and the input to the "
+                               f"same HIP device (input on {x.device}, parameters on {self.arena.device}). "
+                               "There is no CPU fallback.")
+        x = x.contiguous()
+        B, Cc, P, dev = int(x.shape[0]), cfg.num_classes, cfg.patch_size, x.device
+        lp = self._bf16_arena()
+        ccfg = C.byref(_lib.CConfig.from_config(cfg))
+        fwd = _lib.window_symbol("vitseg_forward_lowres")
+        bufs, out = {}, []
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            for op, size, w in views:
+                if size not in bufs:   # one image buffer per size: the stream orders its reuse
+                    bufs[size] = torch.empty((B, cfg.num_channels, size, size), dtype=torch.float32, device=dev)
+                xv = self._tta_view_image(x, u8, op, size, bufs[size])
+                g = size // P
+                low = torch.empty((B, Cc, g, g), dtype=torch.float32, device=dev)
+                ws = self.workspace(B, size)
+                _lib.check(fwd(ccfg, size, self.arena.data_ptr(), _ptr(lp), xv.data_ptr(), B, self.precision, low.data_ptr(),
+                               ws.data_ptr(), ws.numel(), stream))
+                out.append((low, g, op, w))
+        return dict(views=out, B=B, S=H)
+
+    def _tta_blend(self, p: dict, merge: str, want_merged: bool, want_mask: bool):
+        """One vitseg_tta_blend launch over the low-res maps of `_tta_lowres`."""
+        from . import tta as _tta
+        mode = _tta.merge_mode(merge)
+        B, S, Cc, views = p["B"], p["S"], self.cfg.num_classes, p["views"]
+        dev = views[0][0].device
+        merged = torch.empty((B, Cc, S, S), dtype=torch.float32, device=dev) if want_merged else None
+        mask = torch.empty((B, S, S), dtype=torch.uint8, device=dev) if want_mask else None
+        descs = (_lib.CTTAView * len(views))(*[_lib.CTTAView(low.data_ptr(), g, op, w) for low, g, op, w in views])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.tta_symbol("vitseg_tta_blend")(descs, len(views), B, Cc, S, mode, _ptr(merged), _ptr(mask),
+                                                           torch.cuda.current_stream().cuda_stream))
+        return (mask, merged) if want_merged and want_mask else (mask if want_mask else merged)
+
+    _CE_CACHE_ENTRIES = 8  # device weight vectors / scratch buffers kept per model, least recently used first out
 
     def _ce_cached(self, kind: str, key, make):
         """The device tensor cached under `key`, made by `make()` on a miss; each kind keeps the `_CE_CACHE_ENTRIES`

@@ -69,7 +69,8 @@ def preprocess(image, size: int, device="cuda:0") -> torch.Tensor:
 
 def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, index_to_color=None,
             return_logits: bool = False, serve_size: Optional[int] = None, return_boxes: bool = False,
-            sliding: bool = False, stride: Optional[int] = None, weights: str = "linear"):
+            sliding: bool = False, stride: Optional[int] = None, weights: str = "linear", tta=None, tta_sizes=None,
+            tta_merge: str = "logits"):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
@@ -78,11 +79,20 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     4-connected regions of regions.region_boxes, computed on the device).
     `sliding`: the image is NOT resized: its decoded bytes are uploaded and S x S windows `stride` apart run at the image's
     own resolution, blended with `weights` (ViTSegmentationModel.predict_mask_windowed); the mask is [H, W], the logits
-    [C, H, W].  An image with a side shorter than S raises ValueError."""
+    [C, H, W].  An image with a side shorter than S raises ValueError.
+    `tta` (default None: one look, as before): test-time augmentation, a preset ("hflip", "flip", "d4", "none") or a
+    sequence of ops 0..7; the image is resized to S as usual and the mask is `predict_mask_tta`'s -- the views at the sides
+    `tta_sizes` (default (S,)) merged by `tta_merge` ("logits" or "probs"); `return_logits` then returns the merged fp32
+    [C, S, S] (probabilities for "probs").  With `sliding` it raises ValueError: TTA inside sliding windows is not built."""
     seg = model.model if isinstance(model, LightningViTModel) else model
     S = serve_size if serve_size is not None else getattr(model, "serve_size", None)
     S = seg.cfg.image_size if S is None else int(S)
-    if sliding:
+    if tta is not None and sliding:
+        raise ValueError("tta with sliding=True is not supported: test-time augmentation runs on the resized image")
+    if tta is not None:
+        x = preprocess(image, S, seg.arena.device)
+        out = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge, return_merged=return_logits)
+    elif sliding:
         img = torch.from_numpy(decode(image))
         if img.dim() != 3 or min(img.shape[0], img.shape[1]) < S:
             raise ValueError(f"sliding-window prediction needs an image of at least {S}x{S}, got "

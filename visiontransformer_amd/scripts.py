@@ -180,7 +180,8 @@ def run_validation(model, batches, device) -> dict:
 
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
                     distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
-                    percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None) -> List[list]:
+                    percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None,
+                    tta_merge: str = "logits") -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
@@ -188,7 +189,9 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     every image (Evaluator.distance_metrics: PAED, Hausdorff, its percentile, ASSD) go to a second file, distance_csv_path
     (default: <csv_path minus "_metrics.csv">_distance_metrics.csv); the first file is the same with and without it.
     crack_classes (a list of label values, or True for every class but 0): clDice, crack length and width of every image
-    (Evaluator.crack_metrics) go to crack_csv_path (default: ..._crack_metrics.csv), again beside the unchanged first file."""
+    (Evaluator.crack_metrics) go to crack_csv_path (default: ..._crack_metrics.csv), again beside the unchanged first file.
+    tta (default None: one look): a test-time-augmentation preset or op sequence; every file then scores the merged mask of
+    `predict_mask_tta` (views at tta_sizes, default the batch's own size, merged by tta_merge)."""
     seg = getattr(model, "model", model)
     ev = Evaluator(num_classes, device)
     rows, drows, crows = [], [], []
@@ -202,7 +205,10 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         torch.cuda.synchronize()
         t0 = time.time()
         with torch.no_grad():
-            mask = seg.predict_mask(x)
+            if tta is not None:
+                mask = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge)
+            else:
+                mask = seg.predict_mask(x)
         torch.cuda.synchronize()
         per_image = (time.time() - t0) / len(x)
         gt = gt.reshape(gt.shape[0], gt.shape[-2], gt.shape[-1])

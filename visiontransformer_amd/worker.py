@@ -113,10 +113,13 @@ class ModelSlot:
 
 
 def gpu_slot(model_id_or_config, num_classes: int, checkpoint: Optional[str] = None, *, image_size: int = 224,
-             precision: str = "fp32", device: str = "cuda:0", serve_size: Optional[int] = None) -> ModelSlot:
+             precision: str = "fp32", device: str = "cuda:0", serve_size: Optional[int] = None, tta=None, tta_sizes=None,
+             tta_merge: str = "logits") -> ModelSlot:
     """ModelSlot running on libvitseg: device pre-processing of every image (sizes may differ per job), one batched
     forward + fused sigmoid/argmax.  `image_size`: the checkpoint's; `serve_size` (default the same): the side images are
-    resized to, with the position table resampled to its grid when the two differ."""
+    resized to, with the position table resampled to its grid when the two differ.  `tta` (default None: one look):
+    a test-time-augmentation preset or op sequence; every batch then goes through `predict_mask_tta` with the views at
+    `tta_sizes` (default the served size) merged by `tta_merge`."""
     import torch
     from .predict import load_model
     from .preprocess import Preprocessor
@@ -124,13 +127,20 @@ def gpu_slot(model_id_or_config, num_classes: int, checkpoint: Optional[str] = N
                        device=device, serve_size=serve_size)
     S = image_size if serve_size is None else int(serve_size)
     seg, pre = model.model, Preprocessor(S, device)
+    if tta is not None:   # a bad preset, size or merge is refused here, not at the first job
+        from . import tta as _tta
+        _tta.view_list(tta, tta_sizes, None, S, seg.cfg.patch_size)
+        _tta.merge_mode(tta_merge)
 
     def predict_batch(images):
         x = torch.empty((len(images), 3, S, S), dtype=torch.float32, device=device)
         for i, a in enumerate(images):
             pre.images(torch.from_numpy(np.ascontiguousarray(a)), out=x[i:i + 1])
         with torch.no_grad():
-            m = seg.predict_mask(x, interpolate_pos_encoding=S != image_size)
+            if tta is not None:
+                m = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge)
+            else:
+                m = seg.predict_mask(x, interpolate_pos_encoding=S != image_size)
         return list(m.cpu().numpy())
 
     slot = ModelSlot(predict_batch, num_classes)
@@ -282,13 +292,18 @@ def main(argv=None):
                     help="vision_model_id:num_classes[:checkpoint[:config_id[:image_size[:serve_size]]]] (repeatable)")
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--max-batch", type=int, default=16)
+    ap.add_argument("--tta", default=None, help='test-time augmentation preset: "hflip", "flip", "d4" (default: off)')
+    ap.add_argument("--tta-sizes", default=None, help="comma-separated view sizes, e.g. 160,224 (default: the served size)")
+    ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"])
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
+    from .tta import parse_sizes
     slots = {}
     for spec in a.model:
         m = parse_model_spec(spec)
         slots[m["model_id"]] = gpu_slot(m["config_id"], m["num_classes"], m["checkpoint"], image_size=m["image_size"],
-                                        serve_size=m["serve_size"], precision=a.precision)
+                                        serve_size=m["serve_size"], precision=a.precision, tta=a.tta,
+                                        tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge)
     srv = Worker(slots, a.backend, a.token, max_batch=a.max_batch).serve(a.host, a.port)
     log.info("listening on %s:%d/enqueue/ -> %s", a.host, a.port, a.backend)
     srv.serve_forever()
