@@ -521,6 +521,31 @@ size_t vitseg_regions_scratch_bytes(int n, int H, int W);
 int vitseg_regions(const uint8_t* mask, int n, int H, int W, int connectivity, int background, int32_t* counts,
                    int32_t* regions, int max_regions, int32_t* labels, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- mask clean-up: small regions out, enclosed holes filled (the reference has no counterpart: its get_bounding_boxes
+ *      labels the raw argmax; the usual host answer is skimage's remove_small_objects + scipy.ndimage.binary_fill_holes
+ *      per class and image) ----
+ * mask uint8 [n, H, W] -> out uint8 [n, H, W] (out != mask; mask is never written), two steps in this order:
+ *  1. min_area > 1: every region (as above: a maximal `connectivity`-connected set of equal non-background pixels) of
+ *     fewer than min_area pixels becomes `background`; a region of exactly min_area pixels stays.  0 and 1 change nothing.
+ *  2. fill_holes != 0, on the result of step 1: a hole is a 4-connected component of background pixels that does not
+ *     touch the image frame -- 4-connected whatever `connectivity` is (scipy's binary_fill_holes default structure).  A
+ *     hole of at most max_hole_area pixels (0 = no limit) whose non-background 4-neighbours all carry one class c is
+ *     filled with c; a hole bordered by two or more classes stays background.
+ * background 0..255 (-1 is refused: clean-up needs one).
+ * stats (optional) int32 [n, 8]: regions_removed, pixels_removed, holes_filled, pixels_filled, holes_mixed (left: two or
+ *   more bordering classes), holes_over_area (left: above max_hole_area; a hole both over the limit and mixed counts here
+ *   only), 0, 0.
+ * scratch: vitseg_clean_scratch_bytes(n, H, W) device bytes (about 28 bytes per pixel; every word read is written within the
+ * call).  Everything is an integer from order-independent operations: the same bits on every call, and an image gets the
+ * same bits alone as in a batch.
+ * Each with nothing launched -- VITSEG_EINVAL: a null mask / out / scratch, out == mask, connectivity not 4 / 8, background
+ * outside 0..255, a negative min_area or max_hole_area; VITSEG_ESHAPE: non-positive sizes, H * W >= 2^31 or n > 65535;
+ * VITSEG_EWORKSPACE: scratch smaller than vitseg_clean_scratch_bytes (0 for a bad shape). */
+size_t vitseg_clean_scratch_bytes(int n, int H, int W);
+int vitseg_clean_mask(const uint8_t* mask, uint8_t* out, int n, int H, int W, int connectivity, int background, int min_area,
+                      int fill_holes, int max_hole_area, int32_t* stats /* [n, 8] or NULL */, void* scratch,
+                      size_t scratch_bytes, void* stream);
+
 /* ---- exact Euclidean distance transforms and the signed-distance targets of binary masks (replaces
  *      segmentation.compute_sdf = scipy.ndimage.distance_transform_edt of ~mask and of mask, each divided by its maximum,
  *      model/PAED/segmentation.py:6-34, called per item by StructuralDamageDataset, model/PAED/classes.py:51-85) ----

@@ -4,6 +4,7 @@
     python model/CE/testViTModel.py IMAGE [--model-id 0] [--num-classes 17] [--checkpoint x.ckpt]
                                           [--image-size 224] [--precision fp32|bf16] [--out mask.png]
                                           [--boxes boxes.json] [--tta d4] [--tta-sizes 160,224] [--tta-merge probs]
+                                          [--min-area 8] [--fill-holes] [--max-hole-area 64]
 
 Without --checkpoint the weights are random (the reference's checkpoints are private)."""
 import argparse
@@ -11,6 +12,7 @@ import argparse
 import numpy as np
 
 from classes import LightningViTModel  # noqa: F401  (same import the reference script uses)
+from visiontransformer_amd import clean
 from visiontransformer_amd.predict import load_model, predict
 from visiontransformer_amd.tta import parse_sizes
 
@@ -30,8 +32,9 @@ def main():
                                   "quarter-turned views (default: one look)")
     ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
     ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"], help="mean of the views' logits or of their sigmoids")
+    clean.add_arguments(ap)
     a = ap.parse_args()
-    tta = dict(tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge)
+    tta = dict(tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge, **clean.arguments(a))
     model = load_model(a.model_id, a.num_classes, a.checkpoint, image_size=a.image_size, precision=a.precision)
     if a.boxes:
         import json

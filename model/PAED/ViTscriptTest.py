@@ -12,7 +12,7 @@ import os
 import torch
 
 from classes import PAEDTrainer
-from visiontransformer_amd import scripts
+from visiontransformer_amd import clean, scripts
 from visiontransformer_amd.predict import CONFIGURATIONS
 from visiontransformer_amd.tta import parse_sizes
 
@@ -41,6 +41,7 @@ def main():
                                   "quarter-turned views (default: one look)")
     ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
     ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"], help="mean of the views' logits or of their sigmoids")
+    clean.add_arguments(ap)
     a = ap.parse_args()
     dev = "cuda:0"
     cwd = os.getcwd()
@@ -58,7 +59,8 @@ def main():
         rows = scripts.evaluate_to_csv(model, batches, (vid, name, P, D, L, A), os.path.join(cwd, a.out, name, f"{name}_metrics.csv"),
                                        max(a.num_classes, 2), a.num_batches, dev,
                                        distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None,
-                                       tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge)
+                                       tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge,
+                                       **clean.arguments(a))
         print(f"{name}: {len(rows)} images evaluated -> {os.path.join(a.out, name)}")
 
 

@@ -85,8 +85,11 @@ AUGMENT_U8_NHWC, AUGMENT_F32_NCHW = 0, 1   # enum vitseg_augment_format
 # views' low-res maps: bound on first use, the same way
 TTA_EXPORTS = ["vitseg_tta_affine", "vitseg_tta_blend"]
 TTA_LOGITS, TTA_PROBS = 0, 1   # the `mode` argument of vitseg_tta_blend
+# mask clean-up: regions below a minimum area out, enclosed holes filled (clean.py): bound on first use, the same way
+CLEAN_EXPORTS = ["vitseg_clean_scratch_bytes", "vitseg_clean_mask"]
+CLEAN_STATS = ("regions_removed", "pixels_removed", "holes_filled", "pixels_filled", "holes_mixed", "holes_over_area")
 _LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
-                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS)
+                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS + CLEAN_EXPORTS)
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -279,6 +282,10 @@ def lib() -> C.CDLL:
         if getattr(l, "vitseg_tta_blend", None) is not None:
             l.vitseg_tta_affine.argtypes = [i32, vp]   # (double[6] out)
             l.vitseg_tta_blend.argtypes = [C.POINTER(CTTAView), i32, i32, i32, i32, i32, vp, vp, vp]
+        if getattr(l, "vitseg_clean_mask", None) is not None:
+            l.vitseg_clean_scratch_bytes.argtypes = [i32, i32, i32]
+            l.vitseg_clean_scratch_bytes.restype = sz
+            l.vitseg_clean_mask.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -394,6 +401,15 @@ def region_symbol(name: str):
     fn = getattr(lib(), name, None)
     if fn is None:
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before connected regions): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def clean_symbol(name: str):
+    """One of CLEAN_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the mask clean-up): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
 

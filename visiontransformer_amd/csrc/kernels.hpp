@@ -212,5 +212,23 @@ int launch_skeleton(const unsigned char* mask, int n, int H, int W, int route, u
 size_t skeleton_stats_scratch_bytes(int n, int H, int W, int route);
 int launch_skeleton_stats(const unsigned char* pred, const unsigned char* gt, int n, int H, int W, const int* classes, int K,
                           int route, long long* stats_i, double* stats_f, void* scratch, size_t scratch_bytes, hipStream_t s);
+// the labelling launches of regions.hip (tile_label, seam_merge, resolve), shared with clean.hip.  region_words: the int32
+// arrays of a scratch of regions_scratch_bytes(n, H, W) bytes.  After launch_region_labels, root[p] = raster index of the first
+// pixel of p's region (-1 on background) and xmin / xmax / ymax / area at every root hold its box and area (y_min = root / W);
+// link is free for reuse; chunk_counts is what the record launches of vitseg_regions go on from.
+struct RegionWords {
+    int *link, *root, *xmin, *xmax, *ymax, *area, *chunk_counts, *offsets;
+    int nchunks;
+};
+size_t regions_scratch_bytes(int n, int H, int W);
+bool regions_shape_ok(int n, int H, int W);
+RegionWords region_words(void* scratch, int n, int H, int W);
+int launch_region_labels(const unsigned char* mask, int n, int H, int W, int connectivity, int background,
+                         const RegionWords& w, hipStream_t s);
+// mask clean-up (clean.hip: vitseg_clean_mask): regions below min_area to background, enclosed holes filled
+size_t clean_scratch_bytes(int n, int H, int W);
+int launch_clean_mask(const unsigned char* mask, unsigned char* out, int n, int H, int W, int connectivity, int background,
+                      int min_area, int fill_holes, int max_hole_area, int* stats, void* scratch, size_t scratch_bytes,
+                      hipStream_t s);
 
 }  // namespace vitseg

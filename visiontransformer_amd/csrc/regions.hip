@@ -337,6 +337,34 @@ bool shape_ok(int n, int H, int W) { return n > 0 && H > 0 && W > 0 && n <= 6553
 
 size_t regions_scratch_bytes(int n, int H, int W) { return shape_ok(n, H, W) ? layout(n, H, W).total : 0; }
 
+bool regions_shape_ok(int n, int H, int W) { return shape_ok(n, H, W); }
+
+RegionWords region_words(void* scratch, int n, int H, int W) {
+    const Layout l = layout(n, H, W);
+    char* sc = (char*)scratch;
+    return RegionWords{(int*)(sc + l.link), (int*)(sc + l.root), (int*)(sc + l.xmin), (int*)(sc + l.xmax), (int*)(sc + l.ymax),
+                       (int*)(sc + l.area), (int*)(sc + l.counts), (int*)(sc + l.offsets), l.nchunks};
+}
+
+// launches 1 - 3 of the header: the labelling alone.  Arguments are the caller's to check.
+int launch_region_labels(const unsigned char* mask, int n, int H, int W, int connectivity, int background,
+                         const RegionWords& w, hipStream_t s) {
+    const Stats st{w.xmin, w.xmax, w.ymax, w.area};
+    const int ntx = (W + TILE - 1) / TILE, nty = (H + TILE - 1) / TILE, conn8 = connectivity == 8;
+    hipLaunchKernelGGL(tile_label_kernel, dim3(ntx * nty, n), dim3(256), 0, s, mask, w.link, st, H, W, ntx, conn8, background);
+    VITSEG_LAUNCH_CHECK("regions tile_label");
+    const long long seams = (long long)(ntx - 1) * H + (long long)(nty - 1) * W;
+    if (seams > 0) {
+        hipLaunchKernelGGL(seam_merge_kernel, dim3((unsigned)((seams + 255) / 256), n), dim3(256), 0, s, mask, w.link, H, W, ntx,
+                           nty, conn8, background);
+        VITSEG_LAUNCH_CHECK("regions seam_merge");
+    }
+    hipLaunchKernelGGL(resolve_kernel, dim3(w.nchunks, n), dim3(256), 0, s, mask, w.link, w.root, st, w.chunk_counts, H, W,
+                       w.nchunks);
+    VITSEG_LAUNCH_CHECK("regions resolve");
+    return VITSEG_OK;
+}
+
 int launch_regions(const unsigned char* mask, int n, int H, int W, int connectivity, int background, int* counts,
                    int* regions, int max_regions, int* labels, void* scratch, size_t scratch_bytes, hipStream_t s) {
     VITSEG_CHECK_ARG(mask && counts && scratch && (regions || max_regions == 0) && max_regions >= 0, VITSEG_EINVAL,
@@ -348,38 +376,23 @@ int launch_regions(const unsigned char* mask, int n, int H, int W, int connectiv
     VITSEG_CHECK_ARG(!regions || ((uintptr_t)regions & 15) == 0, VITSEG_EINVAL, "regions: records must be 16-byte aligned");
     VITSEG_CHECK_ARG(shape_ok(n, H, W), VITSEG_ESHAPE, "regions: bad shape n=%d H=%d W=%d (positive sizes, H*W < 2^31, n <= 65535)",
                      n, H, W);
-    const Layout l = layout(n, H, W);
-    VITSEG_CHECK_ARG(scratch_bytes >= l.total, VITSEG_EWORKSPACE, "regions: scratch of %zu bytes, %zu needed", scratch_bytes,
-                     l.total);
-    char* sc = (char*)scratch;
-    int* link = (int*)(sc + l.link);
-    int* root = (int*)(sc + l.root);
-    const Stats st{(int*)(sc + l.xmin), (int*)(sc + l.xmax), (int*)(sc + l.ymax), (int*)(sc + l.area)};
-    int* ccount = (int*)(sc + l.counts);
-    int* offs = (int*)(sc + l.offsets);
-    const int ntx = (W + TILE - 1) / TILE, nty = (H + TILE - 1) / TILE, conn8 = connectivity == 8;
+    const size_t need = layout(n, H, W).total;
+    VITSEG_CHECK_ARG(scratch_bytes >= need, VITSEG_EWORKSPACE, "regions: scratch of %zu bytes, %zu needed", scratch_bytes, need);
+    const RegionWords w = region_words(scratch, n, H, W);
+    const Stats st{w.xmin, w.xmax, w.ymax, w.area};
     const int P = H * W;
     if (max_regions > 0) {
         hipError_t e = hipMemsetAsync(regions, 0, (size_t)n * max_regions * 8 * sizeof(int), s);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(regions)");
     }
-    hipLaunchKernelGGL(tile_label_kernel, dim3(ntx * nty, n), dim3(256), 0, s, mask, link, st, H, W, ntx, conn8, background);
-    VITSEG_LAUNCH_CHECK("regions tile_label");
-    const long long seams = (long long)(ntx - 1) * H + (long long)(nty - 1) * W;
-    if (seams > 0) {
-        hipLaunchKernelGGL(seam_merge_kernel, dim3((unsigned)((seams + 255) / 256), n), dim3(256), 0, s, mask, link, H, W, ntx,
-                           nty, conn8, background);
-        VITSEG_LAUNCH_CHECK("regions seam_merge");
-    }
-    hipLaunchKernelGGL(resolve_kernel, dim3(l.nchunks, n), dim3(256), 0, s, mask, link, root, st, ccount, H, W, l.nchunks);
-    VITSEG_LAUNCH_CHECK("regions resolve");
-    hipLaunchKernelGGL(class_scan_kernel, dim3(n), dim3(256), 0, s, ccount, offs, counts, l.nchunks);
+    if (const int rc = launch_region_labels(mask, n, H, W, connectivity, background, w, s)) return rc;
+    hipLaunchKernelGGL(class_scan_kernel, dim3(n), dim3(256), 0, s, w.chunk_counts, w.offsets, counts, w.nchunks);
     VITSEG_LAUNCH_CHECK("regions class_scan");
-    hipLaunchKernelGGL(emit_kernel, dim3(l.nchunks, n), dim3(64), 0, s, mask, root, link, st, offs, regions, max_regions, H, W,
-                       l.nchunks);
+    hipLaunchKernelGGL(emit_kernel, dim3(w.nchunks, n), dim3(64), 0, s, mask, w.root, w.link, st, w.offsets, regions, max_regions,
+                       H, W, w.nchunks);
     VITSEG_LAUNCH_CHECK("regions emit");
     if (labels) {
-        hipLaunchKernelGGL(labels_kernel, dim3((P + 255) / 256, n), dim3(256), 0, s, root, link, labels, P);
+        hipLaunchKernelGGL(labels_kernel, dim3((P + 255) / 256, n), dim3(256), 0, s, w.root, w.link, labels, P);
         VITSEG_LAUNCH_CHECK("regions labels");
     }
     return VITSEG_OK;

@@ -498,13 +498,19 @@ class ViTSegmentationModel(nn.Module):
 
     @torch.no_grad()
     def predict_regions(self, x: torch.Tensor, *, background: int = 0, connectivity: int = 4, return_mask: bool = False,
-                        interpolate_pos_encoding: bool = False):
+                        interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,
+                        max_hole_area: int = 0):
         """The regions of each image's predicted mask: a list of int32 [k, 7] numpy arrays, rows (class, y_min, x_min,
         y_max, x_max, area, first) in (class, first) order (regions.region_boxes) -- the reference's "Predicted Regions
         with Boxes" (model/CE/testViTModel.py:34-42,171-185).  The forward, the mask and the labelling are enqueued on one
-        stream; the host waits once, for the region counts.  `return_mask`: also the uint8 [B, H, W] device mask."""
-        from . import regions as _regions
+        stream; the host waits once, for the region counts.  `return_mask`: also the uint8 [B, H, W] device mask.
+        `min_area` / `fill_holes` / `max_hole_area` (defaults: off): the regions, and the mask returned, are those of the
+        mask cleaned by clean.clean_mask with this call's `connectivity` and `background`, enqueued on the same stream."""
+        from . import clean as _clean, regions as _regions
         mask = self.predict_mask(x, interpolate_pos_encoding=interpolate_pos_encoding)
+        if min_area or fill_holes or max_hole_area:   # with both steps off clean_mask checks its arguments and launches nothing
+            mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area,
+                                     connectivity=connectivity, background=background)
         recs = _regions.region_boxes(mask, background=background, connectivity=connectivity)
         return (recs, mask) if return_mask else recs
 

@@ -70,7 +70,7 @@ def preprocess(image, size: int, device="cuda:0") -> torch.Tensor:
 def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, index_to_color=None,
             return_logits: bool = False, serve_size: Optional[int] = None, return_boxes: bool = False,
             sliding: bool = False, stride: Optional[int] = None, weights: str = "linear", tta=None, tta_sizes=None,
-            tta_merge: str = "logits"):
+            tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
@@ -83,7 +83,12 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     `tta` (default None: one look, as before): test-time augmentation, a preset ("hflip", "flip", "d4", "none") or a
     sequence of ops 0..7; the image is resized to S as usual and the mask is `predict_mask_tta`'s -- the views at the sides
     `tta_sizes` (default (S,)) merged by `tta_merge` ("logits" or "probs"); `return_logits` then returns the merged fp32
-    [C, S, S] (probabilities for "probs").  With `sliding` it raises ValueError: TTA inside sliding windows is not built."""
+    [C, S, S] (probabilities for "probs").  With `sliding` it raises ValueError: TTA inside sliding windows is not built.
+    `min_area` / `fill_holes` / `max_hole_area` (defaults: off): the mask, its colour rendering and its boxes are those of
+    the mask cleaned on the device by clean.clean_mask (regions below `min_area` pixels to class 0, then enclosed holes of
+    at most `max_hole_area` pixels filled), after whichever route made it; the logits are not touched."""
+    from . import clean as _clean
+    _clean.check_options(min_area, fill_holes, max_hole_area)
     seg = model.model if isinstance(model, LightningViTModel) else model
     S = serve_size if serve_size is not None else getattr(model, "serve_size", None)
     S = seg.cfg.image_size if S is None else int(S)
@@ -103,6 +108,8 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
         x = preprocess(image, S, seg.arena.device)
         out = seg.predict_mask(x, return_logits=return_logits, interpolate_pos_encoding=S != seg.cfg.image_size)
     mask_dev = (out[0] if return_logits else out)[0]
+    if _clean.active(min_area, fill_holes):
+        mask_dev = _clean.clean_mask(mask_dev, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area)
     boxes = None
     if return_boxes:
         from .regions import boxes_by_class, region_boxes

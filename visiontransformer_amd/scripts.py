@@ -181,7 +181,8 @@ def run_validation(model, batches, device) -> dict:
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
                     distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
                     percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None,
-                    tta_merge: str = "logits") -> List[list]:
+                    tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False,
+                    max_hole_area: int = 0) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
@@ -191,7 +192,12 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     crack_classes (a list of label values, or True for every class but 0): clDice, crack length and width of every image
     (Evaluator.crack_metrics) go to crack_csv_path (default: ..._crack_metrics.csv), again beside the unchanged first file.
     tta (default None: one look): a test-time-augmentation preset or op sequence; every file then scores the merged mask of
-    `predict_mask_tta` (views at tta_sizes, default the batch's own size, merged by tta_merge)."""
+    `predict_mask_tta` (views at tta_sizes, default the batch's own size, merged by tta_merge).
+    min_area / fill_holes / max_hole_area (defaults: off): every file scores the mask cleaned on the device by
+    clean.clean_mask (regions below min_area pixels to class 0, then enclosed holes of at most max_hole_area pixels filled);
+    the clean-up is part of the time per image."""
+    from . import clean as _clean
+    min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
     seg = getattr(model, "model", model)
     ev = Evaluator(num_classes, device)
     rows, drows, crows = [], [], []
@@ -209,6 +215,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                 mask = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge)
             else:
                 mask = seg.predict_mask(x)
+            if _clean.active(min_area, fill_holes):
+                mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area)
         torch.cuda.synchronize()
         per_image = (time.time() - t0) / len(x)
         gt = gt.reshape(gt.shape[0], gt.shape[-2], gt.shape[-1])

@@ -114,13 +114,17 @@ class ModelSlot:
 
 def gpu_slot(model_id_or_config, num_classes: int, checkpoint: Optional[str] = None, *, image_size: int = 224,
              precision: str = "fp32", device: str = "cuda:0", serve_size: Optional[int] = None, tta=None, tta_sizes=None,
-             tta_merge: str = "logits") -> ModelSlot:
+             tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0) -> ModelSlot:
     """ModelSlot running on libvitseg: device pre-processing of every image (sizes may differ per job), one batched
     forward + fused sigmoid/argmax.  `image_size`: the checkpoint's; `serve_size` (default the same): the side images are
     resized to, with the position table resampled to its grid when the two differ.  `tta` (default None: one look):
     a test-time-augmentation preset or op sequence; every batch then goes through `predict_mask_tta` with the views at
-    `tta_sizes` (default the served size) merged by `tta_merge`."""
+    `tta_sizes` (default the served size) merged by `tta_merge`.  `min_area` / `fill_holes` / `max_hole_area` (defaults:
+    off): every batch's masks are cleaned on the device (clean.clean_mask) before they leave it; a bad value is refused
+    here, not at the first job."""
     import torch
+    from . import clean as _clean
+    min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
     from .predict import load_model
     from .preprocess import Preprocessor
     model = load_model(model_id_or_config, num_classes, checkpoint, image_size=image_size, precision=precision,
@@ -141,6 +145,8 @@ def gpu_slot(model_id_or_config, num_classes: int, checkpoint: Optional[str] = N
                 m = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge)
             else:
                 m = seg.predict_mask(x, interpolate_pos_encoding=S != image_size)
+            if _clean.active(min_area, fill_holes):
+                m = _clean.clean_mask(m, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area)
         return list(m.cpu().numpy())
 
     slot = ModelSlot(predict_batch, num_classes)
@@ -282,7 +288,8 @@ def parse_model_spec(spec: str) -> dict:
                 serve_size=int(parts[5]) if len(parts) > 5 and parts[5] else None)
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
+    from . import clean as _clean
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8001)
@@ -295,7 +302,13 @@ def main(argv=None):
     ap.add_argument("--tta", default=None, help='test-time augmentation preset: "hflip", "flip", "d4" (default: off)')
     ap.add_argument("--tta-sizes", default=None, help="comma-separated view sizes, e.g. 160,224 (default: the served size)")
     ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"])
-    a = ap.parse_args(argv)
+    _clean.add_arguments(ap)
+    return ap
+
+
+def main(argv=None):
+    from . import clean as _clean
+    a = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     from .tta import parse_sizes
     slots = {}
@@ -303,7 +316,7 @@ def main(argv=None):
         m = parse_model_spec(spec)
         slots[m["model_id"]] = gpu_slot(m["config_id"], m["num_classes"], m["checkpoint"], image_size=m["image_size"],
                                         serve_size=m["serve_size"], precision=a.precision, tta=a.tta,
-                                        tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge)
+                                        tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge, **_clean.arguments(a))
     srv = Worker(slots, a.backend, a.token, max_batch=a.max_batch).serve(a.host, a.port)
     log.info("listening on %s:%d/enqueue/ -> %s", a.host, a.port, a.backend)
     srv.serve_forever()
