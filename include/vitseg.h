@@ -546,6 +546,42 @@ int vitseg_clean_mask(const uint8_t* mask, uint8_t* out, int n, int H, int W, in
                       int fill_holes, int max_hole_area, int32_t* stats /* [n, 8] or NULL */, void* scratch,
                       size_t scratch_bytes, void* stream);
 
+/* ---- region-level detection statistics: the regions of a prediction matched against the regions of the ground truth, per
+ *      class (the panoptic-quality construction of Kirillov et al. 2019, PQ = SQ * RQ, and coverage hit rates beside it; the
+ *      reference draws the predicted regions and compares them with nothing; the usual host answer is scipy.ndimage.label
+ *      twice per class and image and a loop over region pairs) ----
+ * pred, gt uint8 [n, H, W] class maps; classes: K distinct label values in HOST memory, none of them the background or the
+ * ignore label.  Regions are maximal 4- / 8-connected sets of equal pixels that are not `background` (0..255): those of
+ * pred are exactly vitseg_regions' on the whole prediction.  ignore_label -1 (none) or 0..255: pixels with gt == ignore_label
+ * are void -- they form no true region and count neither in a predicted region's area nor in any intersection; a predicted
+ * region with no counted pixel does not exist for the statistics.
+ * Per image and class c, P_i the predicted regions of class c, G_j the true ones: a_i = |P_i minus void|, b_j = |G_j|,
+ * I_ij = |P_i n G_j|, U_ij = a_i + b_j - I_ij.
+ *   match      (i, j) is matched iff I_ij * thr_den > thr_num * U_ij, thr_den / 2 <= thr_num < thr_den <= 1000: at or above
+ *              one half a region has at most one partner.
+ *   coverage   G_j is found iff |G_j n {pred == c}| * cov_den >= cov_num * b_j, P_i is confirmed iff
+ *              |P_i n {gt == c}| * cov_den >= cov_num * a_i, 0 < cov_num <= cov_den <= 1000.
+ *   q_ij       floor(I_ij * 2^32 / U_ij): the IoU of a matched pair in fixed point, so that its sum is exact.
+ * stats int64 [n, K, 8]: n_gt, n_pred (regions with a_i > 0), tp (matched pairs), gt_found, pred_confirmed, the sums of q,
+ *   of I and of U over the matched pairs.  fp = n_pred - tp, fn = n_gt - tp, PQ = (sum q / 2^32) / (tp + fp / 2 + fn / 2).
+ * pred_info, gt_info (optional, either may be NULL) int32 [n, H, W, 2]: at the first pixel of every region of a class in
+ *   `classes` (of pred: with a_i > 0) the pair (raster index of the matched partner's first pixel or -1, covered pixels);
+ *   (-2, 0) at every other pixel.
+ * scratch: vitseg_region_match_scratch_bytes(n, H, W) device bytes (about 75 bytes per pixel: the labelling of 2n planes, their
+ * staged copy and a pair table of 2 * H * W slots per image; every word read is written within the call).  One enqueue on
+ * `stream`, no allocation, no host synchronisation.  Everything is an integer from order-independent operations: the same
+ * bits on every call, and an image gets the same bits alone as in a batch.
+ * Each with nothing launched -- VITSEG_EINVAL: a null pred / gt / classes / stats / scratch, connectivity not 4 / 8,
+ * background outside 0..255, ignore_label outside -1..255, equal to the background or in `classes`, a class outside 0..255,
+ * equal to the background or repeated, a threshold outside the ranges above; VITSEG_ESHAPE: non-positive sizes,
+ * H * W >= 2^31, n outside 1..32767 (the planes are labelled as a batch of 2n), K outside 1..256; VITSEG_EWORKSPACE: scratch
+ * smaller than vitseg_region_match_scratch_bytes (0 for a bad shape). */
+size_t vitseg_region_match_scratch_bytes(int n, int H, int W);
+int vitseg_region_match(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, const int32_t* classes, int K,
+                        int connectivity, int background, int ignore_label, int thr_num, int thr_den, int cov_num,
+                        int cov_den, int64_t* stats /* [n, K, 8] */, int32_t* pred_info /* [n, H, W, 2] or NULL */,
+                        int32_t* gt_info /* [n, H, W, 2] or NULL */, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- exact Euclidean distance transforms and the signed-distance targets of binary masks (replaces
  *      segmentation.compute_sdf = scipy.ndimage.distance_transform_edt of ~mask and of mask, each divided by its maximum,
  *      model/PAED/segmentation.py:6-34, called per item by StructuralDamageDataset, model/PAED/classes.py:51-85) ----

@@ -37,6 +37,12 @@ def main():
     ap.add_argument("--crack-metrics", action="store_true",
                     help="also write <model>_crack_metrics.csv: centre-line Dice, crack length and width per image, from the "
                          "Zhang-Suen skeletons of every class but the background 0")
+    ap.add_argument("--region-metrics", action="store_true",
+                    help="also write <model>_region_metrics.csv: regions found, missed and raised falsely, PQ / SQ / RQ and the "
+                         "coverage hit rates per image and class but the background 0, then pooled over all images")
+    ap.add_argument("--region-iou", type=float, default=0.5, help="a predicted and a true region match above this IoU (0.5 <= t < 1)")
+    ap.add_argument("--region-coverage", type=float, default=0.5, help="a region is found / confirmed from this covered fraction on")
+    ap.add_argument("--region-connectivity", type=int, default=4, choices=[4, 8])
     ap.add_argument("--tta", help='test-time augmentation: "hflip", "flip" or "d4" -- the mask is merged from flipped / '
                                   "quarter-turned views (default: one look)")
     ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
@@ -60,6 +66,8 @@ def main():
                                        max(a.num_classes, 2), a.num_batches, dev,
                                        distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None,
                                        tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge,
+                                       region_classes=True if a.region_metrics else None, region_iou=a.region_iou,
+                                       region_coverage=a.region_coverage, region_connectivity=a.region_connectivity,
                                        **clean.arguments(a))
         print(f"{name}: {len(rows)} images evaluated -> {os.path.join(a.out, name)}")
 

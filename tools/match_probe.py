@@ -1,0 +1,161 @@
+#!/usr/bin/env python3
+"""Times vitseg_region_match (csrc/match.hip) with hipEvents at n = 32, 512 x 512 on the mask kinds of tools/regions_probe.py
+(blobs and uniform random masks of 2 and 17 classes, a checkerboard and a serpentine), 4-connectivity, background 0, IoU and
+coverage 1/2, every class but the background, both info planes written: the mask is the ground truth and the prediction is the
+mask with 1 % of its pixels drawn again.  Beside it vitseg_regions with labels written on the predictions, in the same process,
+the two calls taken in turn so that both see the same machine; the match labels 2n planes, so two such calls are the yardstick.
+When scipy is present, also the host loop the call replaces, on one image per mask kind and on one core: scipy.ndimage.label of
+both maps per class, then the pair counts by sorting pair keys.
+
+    python tools/match_probe.py [--iters 30] [--out profiles/match_probe.json]"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import regions_ref as R  # noqa: E402
+from visiontransformer_amd import _lib, regions  # noqa: E402
+
+N, S = 32, 512
+
+
+def inputs():
+    """(kind, classes, gt, pred) uint8 [N, S, S]."""
+    rs = np.random.RandomState(0)
+    kinds = [("blobs", 2, R.blobs(1, S, S, 2, n=N)), ("blobs", 17, R.blobs(2, S, S, 17, n=N)),
+             ("uniform", 2, rs.randint(0, 2, size=(N, S, S)).astype(np.uint8)),
+             ("uniform", 17, rs.randint(0, 17, size=(N, S, S)).astype(np.uint8)),
+             ("checkerboard", 2, np.broadcast_to(R.checkerboard(S, S), (N, S, S)).copy()),
+             ("serpentine", 2, np.broadcast_to(R.serpentine(S, S), (N, S, S)).copy())]
+    for kind, C, gt in kinds:
+        pred = gt.copy()
+        hit = rs.rand(*gt.shape) < 0.01
+        pred[hit] = rs.randint(0, C, size=int(hit.sum())).astype(np.uint8)
+        yield kind, C, gt, pred
+
+
+def match_call(pred, gt, classes):
+    """One enqueue-only vitseg_region_match call on preallocated buffers: (() -> None, stats)."""
+    n, H, W = pred.shape
+    K = len(classes)
+    cls = (ctypes.c_int32 * K)(*classes)
+    nbytes = _lib.match_symbol("vitseg_region_match_scratch_bytes")(n, H, W)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    stats = torch.empty((n, K, 8), dtype=torch.int64, device=pred.device)
+    pinfo = torch.empty((n, H, W, 2), dtype=torch.int32, device=pred.device)
+    ginfo = torch.empty((n, H, W, 2), dtype=torch.int32, device=pred.device)
+    f = _lib.match_symbol("vitseg_region_match")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call():
+        _lib.check(f(pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K, 4, 0, -1, 1, 2, 1, 2, stats.data_ptr(), pinfo.data_ptr(),
+                     ginfo.data_ptr(), scratch.data_ptr(), nbytes, stream))
+    return call, stats, nbytes
+
+
+def regions_call(md):
+    n, H, W = md.shape
+    counts, _, _ = regions._launch(md, 0, 4, 0, False)
+    cap = int(counts.max())
+    scratch = torch.empty(_lib.region_symbol("vitseg_regions_scratch_bytes")(n, H, W), dtype=torch.uint8, device=md.device)
+    recs = torch.empty((n, cap, 8), dtype=torch.int32, device=md.device)
+    labels = torch.empty((n, H, W), dtype=torch.int32, device=md.device)
+    f = _lib.region_symbol("vitseg_regions")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call():
+        _lib.check(f(md.data_ptr(), n, H, W, 4, 0, counts.data_ptr(), recs.data_ptr(), cap, labels.data_ptr(),
+                     scratch.data_ptr(), scratch.numel(), stream))
+    return call
+
+
+def timed(call):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    call()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3
+
+
+def host_loop(pred, gt, classes):
+    """The host answer for one image on one core: seconds, and tp as a check against the device."""
+    from scipy import ndimage
+    t0 = time.perf_counter()
+    tp = 0
+    for c in classes:
+        lp, kp = ndimage.label(pred == c)
+        lg, kg = ndimage.label(gt == c)
+        a, b = np.bincount(lp.reshape(-1), minlength=kp + 1), np.bincount(lg.reshape(-1), minlength=kg + 1)
+        hit = (lp > 0) & (lg > 0)
+        keys, inter = np.unique(lp[hit].astype(np.int64) * (kg + 1) + lg[hit], return_counts=True)
+        union = a[keys // (kg + 1)] + b[keys % (kg + 1)] - inter
+        tp += int((2 * inter > union).sum())
+    return time.perf_counter() - t0, tp
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match_probe.json"))
+    ap.add_argument("--no-host", action="store_true", help="skip the scipy loop")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "the probe measures on the GPU"
+    torch.set_num_threads(1)
+    result = dict(n=N, size=S, iters=a.iters, connectivity=4, background=0, device=torch.cuda.get_device_name(0),
+                  note="us per call, median [min, max] of hipEvent-timed calls taken in turn; x_regions = median over "
+                       "vitseg_regions' (labels written, no truncation) on the predictions; host = scipy.ndimage.label of both "
+                       "maps per class + sorted pair keys, one image on one core, times n for the batch", rows=[])
+    print(f"{'kind':13s} {'C':>3s} {'match us':>10s} {'min':>9s} {'max':>9s} {'regions us':>10s} {'x regions':>9s} {'Mpix/s':>8s} "
+          f"{'tp/img':>8s} {'host ms/img':>11s}")
+    for kind, C, gt, pred in inputs():
+        classes = list(range(1, C))
+        pd, gd = torch.from_numpy(pred).cuda(), torch.from_numpy(gt).cuda()
+        match, stats, nbytes = match_call(pd, gd, classes)
+        calls = {"match": match, "regions": regions_call(pd)}
+        for _ in range(5):
+            for c in calls.values():
+                c()
+        torch.cuda.synchronize()
+        ts = {k: [] for k in calls}
+        for _ in range(a.iters):
+            for k, c in calls.items():
+                ts[k].append(timed(c))
+        med, base = float(np.median(ts["match"])), float(np.median(ts["regions"]))
+        st = stats.cpu().numpy().sum(axis=1)
+        row = dict(kind=kind, classes=C, match_us_median=round(med, 1), match_us_min=round(min(ts["match"]), 1),
+                   match_us_max=round(max(ts["match"]), 1), regions_us_median=round(base, 1), x_regions=round(med / base, 3),
+                   mpix_per_s=round(N * S * S / med), scratch_bytes_per_pixel=round(nbytes / (N * S * S), 2),
+                   mean_per_image=dict(zip(_lib.MATCH_STATS[:5], st[:, :5].mean(axis=0).tolist())))
+        host = ""
+        try:
+            import scipy  # noqa: F401
+            have = not a.no_host
+        except ImportError:
+            have = False
+            result.setdefault("host_note", "scipy not installed: the host loop was not timed")
+        if have:
+            sec, tp = host_loop(pred[0], gt[0], classes)
+            assert tp == int(st[0, 2]), (tp, int(st[0, 2]))
+            row.update(host_ms_per_image=round(sec * 1e3, 2), host_batch_over_device=round(sec * N * 1e6 / med))
+            host = f"{sec * 1e3:11.1f}"
+        result["rows"].append(row)
+        print(f"{kind:13s} {C:3d} {med:10.1f} {min(ts['match']):9.1f} {max(ts['match']):9.1f} {base:10.1f} {med / base:9.2f} "
+              f"{N * S * S / med:8.0f} {st[:, 2].mean():8.0f} {host}", flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(a.out)
+
+
+if __name__ == "__main__":
+    main()

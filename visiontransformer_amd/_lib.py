@@ -88,8 +88,12 @@ TTA_LOGITS, TTA_PROBS = 0, 1   # the `mode` argument of vitseg_tta_blend
 # mask clean-up: regions below a minimum area out, enclosed holes filled (clean.py): bound on first use, the same way
 CLEAN_EXPORTS = ["vitseg_clean_scratch_bytes", "vitseg_clean_mask"]
 CLEAN_STATS = ("regions_removed", "pixels_removed", "holes_filled", "pixels_filled", "holes_mixed", "holes_over_area")
+# region-level detection statistics: predicted regions matched against the true ones, PQ (metrics.Evaluator.region_metrics):
+# bound on first use, the same way
+MATCH_EXPORTS = ["vitseg_region_match_scratch_bytes", "vitseg_region_match"]
+MATCH_STATS = ("n_gt", "n_pred", "tp", "gt_found", "pred_confirmed", "sum_q", "sum_i", "sum_u")
 _LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
-                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS + CLEAN_EXPORTS)
+                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS + CLEAN_EXPORTS + MATCH_EXPORTS)
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -286,6 +290,11 @@ def lib() -> C.CDLL:
             l.vitseg_clean_scratch_bytes.argtypes = [i32, i32, i32]
             l.vitseg_clean_scratch_bytes.restype = sz
             l.vitseg_clean_mask.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]
+        if getattr(l, "vitseg_region_match", None) is not None:
+            l.vitseg_region_match_scratch_bytes.argtypes = [i32, i32, i32]
+            l.vitseg_region_match_scratch_bytes.restype = sz
+            l.vitseg_region_match.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,
+                                              sz, vp]
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -419,6 +428,15 @@ def sdf_symbol(name: str):
     fn = getattr(lib(), name, None)
     if fn is None:
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before distance transforms): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def match_symbol(name: str):
+    """One of MATCH_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the region matching): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
 

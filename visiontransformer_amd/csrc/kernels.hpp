@@ -230,5 +230,10 @@ size_t clean_scratch_bytes(int n, int H, int W);
 int launch_clean_mask(const unsigned char* mask, unsigned char* out, int n, int H, int W, int connectivity, int background,
                       int min_area, int fill_holes, int max_hole_area, int* stats, void* scratch, size_t scratch_bytes,
                       hipStream_t s);
+// region-level detection statistics (match.hip: vitseg_region_match): predicted regions matched against the true ones
+size_t region_match_scratch_bytes(int n, int H, int W);
+int launch_region_match(const unsigned char* pred, const unsigned char* gt, int n, int H, int W, const int* classes, int K,
+                        int connectivity, int background, int ignore_label, int thr_num, int thr_den, int cov_num, int cov_den,
+                        long long* stats, int* pred_info, int* gt_info, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 }  // namespace vitseg

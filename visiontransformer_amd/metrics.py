@@ -18,6 +18,12 @@ Cracks (`Evaluator.crack_metrics`): structures one to five pixels wide, for whic
 the crack's course was found.  `vitseg_skeleton_stats` (csrc/skeleton.hip) thins the class sets of both maps to their
 Zhang-Suen skeletons and counts what centre-line Dice (clDice), the crack length and the crack width need;
 `crack_from_stats` is the host arithmetic.
+
+Regions (`Evaluator.region_metrics`): how many defects were found, missed and raised falsely.  `vitseg_region_match`
+(csrc/match.hip) labels the regions of both maps, counts the intersection of every (predicted, true) pair and matches the pairs
+above an IoU threshold of one half or more, where no region has two partners (the panoptic quality of Kirillov et al. 2019,
+PQ = SQ * RQ per class), beside coverage hit rates for thin structures; `matches_from_stats` is the host arithmetic on its
+integers, and `pool_region_stats` sums them over a data set first, which is the form to report.
 """
 from __future__ import annotations
 
@@ -163,6 +169,76 @@ def crack_from_stats(stats_i, stats_f) -> list:
                             endpoints_gt=e_g, endpoints_pred=e_p))
         out.append(row)
     return out
+
+
+REGION_KEYS = ("pq", "sq", "rq", "precision", "recall", "f1", "found_rate", "confirmed_rate", "mean_matched_iou")
+# header of <model>_region_metrics.csv (--region-metrics of the evaluation scripts): one row per image and class, then one
+# pooled row per class (Batch_Num "pooled") from the integers summed over all images
+REGION_CSV_COLUMNS = ["Model_ID", "Model_Name", "Batch_Num", "Image_Idx", "Class", "IoU_Threshold", "Coverage", "N_GT", "N_Pred",
+                      "TP", "FP", "FN", "GT_Found", "Pred_Confirmed", "Sum_Q", "Sum_I", "Sum_U", "PQ", "SQ", "RQ", "Precision",
+                      "Recall", "F1", "Found_Rate", "Confirmed_Rate", "Mean_Matched_IoU"]
+
+
+def _unit_fraction(value, what: str):
+    f = Fraction(str(value))
+    if f.denominator > 1000:
+        raise ValueError(f"{what} must be a fraction with a denominator of at most 1000 (three decimals), got {value!r}")
+    return f
+
+
+def iou_threshold_fraction(threshold):
+    """An IoU threshold as the rational (thr_num, thr_den) of vitseg_region_match: 0.5 -> (1, 2), 0.75 -> (3, 4).  ValueError
+    below 0.5 (a region could have two partners), at 1 or above, or when the denominator would pass 1000."""
+    f = _unit_fraction(threshold, "iou_threshold")
+    if not Fraction(1, 2) <= f < 1:
+        raise ValueError(f"iou_threshold must lie in 0.5 <= t < 1, got {threshold!r}")
+    return f.numerator, f.denominator
+
+
+def coverage_fraction(coverage):
+    """A coverage 0 < c <= 1 as the rational (cov_num, cov_den) of vitseg_region_match; ValueError as above."""
+    f = _unit_fraction(coverage, "coverage")
+    if not 0 < f <= 1:
+        raise ValueError(f"coverage must lie in 0 < c <= 1, got {coverage!r}")
+    return f.numerator, f.denominator
+
+
+def matches_from_stats(stats):
+    """stats int64 [n, K, 8] of vitseg_region_match (include/vitseg.h) -> per image a list of K dicts (one list for a pooled
+    [K, 8]).  With fp = n_pred - tp, fn = n_gt - tp and IoU sum = sum_q / 2^32:
+      rq  tp / (tp + fp / 2 + fn / 2)     sq  IoU sum / tp     pq  IoU sum / (tp + fp / 2 + fn / 2) = sq * rq
+      precision tp / n_pred, recall tp / n_gt, f1 2 tp / (n_pred + n_gt)
+      found_rate gt_found / n_gt, confirmed_rate pred_confirmed / n_pred: the coverage hit rates
+      mean_matched_iou  sum_i / sum_u: the IoU of all matched pixels pooled (sq weighs every pair alike)
+    and the eight integers.  An entry whose denominator is 0 is nan."""
+    st = np.asarray(stats, dtype=np.int64)
+    if st.ndim not in (2, 3) or st.shape[-1] != 8:
+        raise ValueError(f"stats must be [n, K, 8] or [K, 8], got {st.shape}")
+    nan = float("nan")
+    ratio = lambda a, b: a / b if b else nan
+    out = []
+    for img in (st[None] if st.ndim == 2 else st):
+        row = []
+        for rec in img:
+            n_gt, n_pred, tp, found, confirmed, sq, si, su = (int(v) for v in rec)
+            fp, fn = n_pred - tp, n_gt - tp
+            iou_sum = sq / float(1 << 32)
+            row.append(dict(n_gt=n_gt, n_pred=n_pred, tp=tp, fp=fp, fn=fn, gt_found=found, pred_confirmed=confirmed, sum_q=sq,
+                            sum_i=si, sum_u=su, pq=ratio(iou_sum, tp + fp / 2 + fn / 2), sq=ratio(iou_sum, tp),
+                            rq=ratio(tp, tp + fp / 2 + fn / 2), precision=ratio(tp, n_pred), recall=ratio(tp, n_gt),
+                            f1=ratio(2 * tp, n_pred + n_gt), found_rate=ratio(found, n_gt),
+                            confirmed_rate=ratio(confirmed, n_pred), mean_matched_iou=ratio(si, su)))
+        out.append(row)
+    return out[0] if st.ndim == 2 else out
+
+
+def pool_region_stats(list_of_stats) -> np.ndarray:
+    """int64 [K, 8]: the integers of vitseg_region_match summed over the images of every [n, K, 8] (or [K, 8]) in the list.  PQ
+    is a data-set quantity: `matches_from_stats` of this sum is the figure to report, not a mean of per-image ratios."""
+    parts = [np.asarray(s.cpu() if torch.is_tensor(s) else s, dtype=np.int64) for s in list_of_stats]
+    if not parts or any(p.ndim not in (2, 3) or p.shape[-2:] != parts[0].shape[-2:] or p.shape[-1] != 8 for p in parts):
+        raise ValueError("pool_region_stats needs a non-empty list of [n, K, 8] arrays with one K")
+    return sum(p.reshape(-1, *p.shape[-2:]).sum(axis=0) for p in parts)
 
 
 class Evaluator:
@@ -312,6 +388,120 @@ class Evaluator:
             out.append(d)
         return out
 
+    def region_match_stats(self, pred: torch.Tensor, gt: torch.Tensor, classes: Sequence[int], iou=(1, 2), coverage=(1, 2),
+                           connectivity: int = 4, background: int = 0, ignore_label: int = -1, return_info: bool = False):
+        """stats int64 [n, K, 8] device tensor of vitseg_region_match for uint8 predictions [n, H, W]; a ground truth of
+        another size is nearest-resized first, exactly as `distance_stats` does.  iou and coverage are (num, den) pairs.
+        return_info: (stats, pred_info, gt_info, gt as compared), the int32 [n, H, W, 2] planes of include/vitseg.h.  One
+        enqueue on the current stream."""
+        if pred.dtype != torch.uint8 or pred.dim() != 3:
+            raise ValueError(f"pred must be uint8 [n, H, W], got {pred.dtype} {tuple(pred.shape)}")
+        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
+            raise ValueError("Number of images and masks must be equal!")
+        classes = [int(c) for c in classes]
+        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
+            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
+        pred = pred.to(self.device).contiguous()
+        gt = gt.to(self.device).to(torch.uint8).contiguous()
+        n, H, W = (int(d) for d in pred.shape)
+        K = len(classes)
+        cls = (ctypes.c_int32 * K)(*classes)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            if tuple(gt.shape[1:]) != (H, W):
+                Hg, Wg = (int(d) for d in gt.shape[1:])
+                g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
+                _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
+                                                               self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
+                                                               st))
+                gt = g2
+            nbytes = _lib.match_symbol("vitseg_region_match_scratch_bytes")(n, H, W)
+            if nbytes == 0:
+                raise ValueError(f"region metrics: H * W must stay below 2^31 and n in 1..32767, got {n} x {H} x {W}")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            stats = torch.empty((n, K, 8), dtype=torch.int64, device=self.device)
+            pinfo = torch.empty((n, H, W, 2), dtype=torch.int32, device=self.device) if return_info else None
+            ginfo = torch.empty((n, H, W, 2), dtype=torch.int32, device=self.device) if return_info else None
+            _lib.check(_lib.match_symbol("vitseg_region_match")(
+                pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K, int(connectivity), int(background), int(ignore_label),
+                int(iou[0]), int(iou[1]), int(coverage[0]), int(coverage[1]), stats.data_ptr(),
+                None if pinfo is None else pinfo.data_ptr(), None if ginfo is None else ginfo.data_ptr(), scratch.data_ptr(),
+                nbytes, st))
+        return (stats, pinfo, ginfo, gt) if return_info else stats
+
+    def _region_arguments(self, classes, iou_threshold, coverage, connectivity, background, ignore_label):
+        """The arguments of `region_metrics`, checked before anything reaches the library."""
+        thr, cov = iou_threshold_fraction(iou_threshold), coverage_fraction(coverage)
+        if connectivity not in (4, 8):
+            raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
+        if isinstance(background, bool) or not isinstance(background, (int, np.integer)) or not 0 <= int(background) <= 255:
+            raise ValueError(f"background must be an integer in 0..255, got {background!r}")
+        background = int(background)
+        if ignore_label is None:
+            ignore_label = -1
+        elif (isinstance(ignore_label, bool) or not isinstance(ignore_label, (int, np.integer))
+              or not 0 <= int(ignore_label) <= 255 or int(ignore_label) == background):
+            raise ValueError(f"ignore_label must be None or an integer in 0..255 other than the background, got {ignore_label!r}")
+        ignore_label = int(ignore_label)
+        if classes is None:
+            classes = [c for c in range(self.num_classes) if c not in (background, ignore_label)]
+        classes = [int(c) for c in classes]
+        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
+            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
+        if len(set(classes)) != len(classes) or background in classes or ignore_label in classes:
+            raise ValueError(f"classes must be distinct and hold neither the background {background} nor the ignore label, "
+                             f"got {classes}")
+        return classes, thr, cov, background, ignore_label
+
+    def region_metrics(self, pred: torch.Tensor, gt: torch.Tensor, classes: Optional[Sequence[int]] = None,
+                       iou_threshold=0.5, coverage=0.5, connectivity: int = 4, background: int = 0, ignore_label=None,
+                       return_matches: bool = False) -> List[dict]:
+        """Per image: dict(per_class={class: the dict of `matches_from_stats`}, pq=, sq=, rq=, precision=, recall=, f1=,
+        found_rate=, confirmed_rate=, mean_matched_iou= the nan-aware means over the classes, stats= the int64 [K, 8] behind
+        them for `pool_region_stats`).  A predicted region and a true one of a class are matched when their IoU exceeds
+        iou_threshold (0.5 <= t < 1, at most three decimals); a true region is found, a predicted one confirmed, when
+        `coverage` of it or more lies on the other map's pixels of its class.  classes=None: range(num_classes) without the
+        background.  ignore_label: ground-truth pixels of this value are void (see include/vitseg.h).
+        return_matches: every dict also holds matches={"gt": int32 [kg, 9], "pred": int32 [kp, 9]}: `region_boxes`' seven
+        fields in its (class, first) order for the regions of `classes` (of pred: those with a counted pixel), then `match`
+        (the partner's row in the other list, -1 if none) and `covered` (its pixels on the other map's class)."""
+        if not isinstance(pred, torch.Tensor) or pred.dtype != torch.uint8 or pred.dim() != 3:
+            raise ValueError(f"pred must be a uint8 tensor [n, H, W], got {getattr(pred, 'dtype', type(pred).__name__)}")
+        classes, thr, cov, background, ignore_label = self._region_arguments(classes, iou_threshold, coverage, connectivity,
+                                                                            background, ignore_label)
+        res = self.region_match_stats(pred, gt, classes, thr, cov, connectivity, background, ignore_label,
+                                      return_info=return_matches)
+        stats = (res[0] if return_matches else res).cpu().numpy()
+        out = []
+        for i, row in enumerate(matches_from_stats(stats)):
+            d = dict(per_class=dict(zip(classes, row)), stats=stats[i])
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)   # all-nan -> nan, as the overlap means
+                for key in REGION_KEYS:
+                    d[key] = float(np.nanmean([r[key] for r in row]))
+            out.append(d)
+        if return_matches:
+            from .regions import region_boxes
+            _, pinfo, ginfo, g = res
+            if ignore_label >= 0:
+                g = torch.where(g == ignore_label, torch.full_like(g, background), g)
+            sides = {"pred": (region_boxes(pred.to(self.device), background=background, connectivity=connectivity),
+                              pinfo.cpu().numpy()),
+                     "gt": (region_boxes(g, background=background, connectivity=connectivity), ginfo.cpu().numpy())}
+            for i, d in enumerate(out):
+                tabs, rows = {}, {}
+                for name, (recs, info) in sides.items():
+                    flat = info[i].reshape(-1, 2)
+                    rec = recs[i][np.isin(recs[i][:, 0], classes)]
+                    rec = rec[flat[rec[:, 6], 0] != -2]          # predicted regions without a counted pixel
+                    rows[name] = {int(f): r for r, f in enumerate(rec[:, 6])}
+                    tabs[name] = np.concatenate([rec, flat[rec[:, 6]]], axis=1).astype(np.int32).reshape(-1, 9)
+                for name, other in (("pred", "gt"), ("gt", "pred")):
+                    for r in tabs[name]:
+                        r[7] = rows[other][int(r[7])] if r[7] >= 0 else -1
+                d["matches"] = tabs
+        return out
+
     def evaluate(self, pred: torch.Tensor, gt: torch.Tensor) -> List[dict]:
         c = self.counts(pred, gt).cpu().numpy()
         px = int(pred.shape[1] * pred.shape[2])
@@ -362,4 +552,19 @@ def write_crack_csv(path: str, rows: Sequence[Sequence]) -> None:
     with open(path, mode="w", newline="") as f:
         w = csv.writer(f)
         w.writerow(CRACK_CSV_COLUMNS)
+        w.writerows(rows)
+
+
+def region_csv_row(model_info: Sequence, batch_num, image_idx, cls: int, iou_threshold, coverage, m: dict) -> list:
+    """One row of <model>_region_metrics.csv from one class's dict of `matches_from_stats`; batch_num "pooled" and an empty
+    image_idx mark a row of the integers summed over all images."""
+    return [model_info[0], model_info[1], batch_num, image_idx, cls, iou_threshold, coverage, m["n_gt"], m["n_pred"], m["tp"],
+            m["fp"], m["fn"], m["gt_found"], m["pred_confirmed"], m["sum_q"], m["sum_i"], m["sum_u"], m["pq"], m["sq"], m["rq"],
+            m["precision"], m["recall"], m["f1"], m["found_rate"], m["confirmed_rate"], m["mean_matched_iou"]]
+
+
+def write_region_csv(path: str, rows: Sequence[Sequence]) -> None:
+    with open(path, mode="w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(REGION_CSV_COLUMNS)
         w.writerows(rows)

@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from . import synth
-from .metrics import (Evaluator, crack_csv_row, csv_row, distance_csv_row, write_crack_csv, write_distance_csv,
-                      write_metrics_csv)
+from .metrics import (Evaluator, crack_csv_row, csv_row, distance_csv_row, matches_from_stats, pool_region_stats,
+                      region_csv_row, write_crack_csv, write_distance_csv, write_metrics_csv, write_region_csv)
 
 
 def checkpoint_epoch(path: str) -> Optional[int]:
@@ -182,7 +182,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                     distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
                     percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None,
                     tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False,
-                    max_hole_area: int = 0) -> List[list]:
+                    max_hole_area: int = 0, region_classes=None, region_csv_path: Optional[str] = None, region_iou=0.5,
+                    region_coverage=0.5, region_connectivity: int = 4) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
@@ -195,14 +196,19 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     `predict_mask_tta` (views at tta_sizes, default the batch's own size, merged by tta_merge).
     min_area / fill_holes / max_hole_area (defaults: off): every file scores the mask cleaned on the device by
     clean.clean_mask (regions below min_area pixels to class 0, then enclosed holes of at most max_hole_area pixels filled);
-    the clean-up is part of the time per image."""
+    the clean-up is part of the time per image.
+    region_classes (a list of label values, or True for every class but 0): the region-level detection statistics of every
+    image and class (Evaluator.region_metrics at region_iou / region_coverage / region_connectivity) go to region_csv_path
+    (default: ..._region_metrics.csv), followed by one row per class of the integers pooled over all images."""
     from . import clean as _clean
     min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
     seg = getattr(model, "model", model)
     ev = Evaluator(num_classes, device)
-    rows, drows, crows = [], [], []
+    rows, drows, crows, rrows, rstats = [], [], [], [], []
     if crack_classes is True:
         crack_classes = list(range(1, num_classes))
+    if region_classes is True:
+        region_classes = list(range(1, num_classes))
     model.eval()
     for bn, batch in enumerate(batches):
         if bn >= num_batches:
@@ -228,6 +234,12 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         if crack_classes:
             for idx, m in enumerate(ev.crack_metrics(mask, gt, classes=crack_classes)):
                 crows.append(crack_csv_row(model_info, bn, idx, m))
+        if region_classes:
+            for idx, m in enumerate(ev.region_metrics(mask, gt, classes=region_classes, iou_threshold=region_iou,
+                                                      coverage=region_coverage, connectivity=region_connectivity)):
+                rstats.append(m["stats"])
+                for c, r in m["per_class"].items():
+                    rrows.append(region_csv_row(model_info, bn, idx, c, region_iou, region_coverage, r))
     os.makedirs(os.path.dirname(os.path.abspath(csv_path)), exist_ok=True)
     write_metrics_csv(csv_path, rows)
     stem = csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
@@ -237,4 +249,9 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         write_distance_csv(distance_csv_path, drows)
     if crack_classes:
         write_crack_csv(crack_csv_path or stem + "_crack_metrics.csv", crows)
+    if region_classes:
+        if rstats:
+            for c, r in zip(region_classes, matches_from_stats(pool_region_stats(rstats))):
+                rrows.append(region_csv_row(model_info, "pooled", "", c, region_iou, region_coverage, r))
+        write_region_csv(region_csv_path or stem + "_region_metrics.csv", rrows)
     return rows
