@@ -665,6 +665,50 @@ size_t vitseg_skeleton_stats_scratch_bytes(int n, int H, int W, int route);
 int vitseg_skeleton_stats(const uint8_t* pred, const uint8_t* gt, int n, int H, int W, const int32_t* classes, int K,
                           int route, int64_t* stats_i, double* stats_f, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- per-region measurements: moments, perimeter, frame contact and, for chosen classes, each region's own skeleton length
+ *      and widths (the usual host answer is skimage.measure.regionprops plus a skeleton and a distance transform per label,
+ *      one image at a time) ----
+ * mask uint8 [n, H, W] class map.  The regions, their (class, first) order, counts (the true total, also above max_regions)
+ * and labels are exactly vitseg_regions' for the same connectivity (4 / 8) and background (0..255 or -1): the same labelling
+ * launches run.  props int64 [n, max_regions, VITSEG_PROPS_FIELDS]: one row per region for the first max_regions regions of
+ * each image, rows past the count zero (may be NULL when max_regions == 0):
+ *    0..6  class, first, area, y_min, x_min, y_max, x_max (box inclusive, first = raster index of the first pixel);
+ *    7..11 sum_y, sum_x, sum_yy, sum_xx, sum_xy: the sums over the region's pixels of y, x, y^2, x^2, x y (row, column);
+ *    12    perimeter: the (pixel, side) pairs whose 4-neighbour lies outside the image or has another value -- the outline
+ *          length in pixel sides, holes included;
+ *    13    frame_pixels: pixels with y in {0, H - 1} or x in {0, W - 1}, each once; > 0: the frame cuts the region off;
+ *    14    max_d2: the maximum of d2 over the region's pixels (the squared inscribed radius);
+ *    15    skel_len: skeleton pixels inside the region;   16  end_points: those with exactly one set 8-neighbour in the skeleton;
+ *    17    skel_max_d2: the maximum of d2 over the skeleton pixels, -1 when skel_len = 0;
+ *    18    skel_width_q16: the sum over the skeleton pixels of llrint(sqrt((double) d2) * 65536.0), a fixed-point sum (exact
+ *          and independent of the order, as q of vitseg_region_match);   19  0, reserved.
+ * Fields 14..18 are measured for the regions whose class is in `classes` (K distinct values 0..255 in HOST memory, none the
+ * background; NULL allowed when K == 0) and are -1 for every other region.  For a class c, X = {mask == c} of the image: the
+ * skeleton is vitseg_skeleton's of X (same kernels, same `route`, route 2 synchronises `stream` as documented there) and
+ * d2(x) the exact squared distance from x in X to the nearest pixel outside X (vitseg_sdf's "int" field before the root,
+ * virtual point (-1, 0) when X is the whole image: the field of vitseg_skeleton_stats).  A skeleton pixel belongs to the region
+ * that contains it.  Under connectivity 8 two regions of one class never share a 3 x 3 neighbourhood, so this is each
+ * region's own skeleton and own distance field.  Under connectivity 4 two diagonally touching regions of one class are
+ * thinned and measured as the one plane they share: the thinning sees them as one 8-connected figure, and each region gets
+ * the skeleton pixels and the distances that fall inside it.  K == 0 launches no skeleton or distance work, and `route`
+ * is then only range-checked.
+ * scratch: vitseg_region_props_scratch_bytes(n, H, W, K, route) device bytes (vitseg_regions' plus 4 bytes per pixel, with
+ * K > 0 7 more and the thinning's; every word read is written within the call).  Classes are processed one after another on
+ * `stream`; no allocation, no host synchronisation except route 2's.  Every value is an integer from order-independent
+ * integer operations: the same bits on every call and by either route, and per image the same bits in any batch.  Regions
+ * with index >= max_regions are skipped: nothing is written outside props.
+ * VITSEG_EINVAL: null mask / counts / scratch, null props with max_regions > 0, negative max_regions, connectivity not 4 / 8,
+ * background outside -1..255, route outside 0..2, null classes with K > 0, a class outside 0..255, repeated or equal to the
+ * background; VITSEG_ESHAPE: H or W outside 1..16384, n outside 1..32767, K outside 0..256, route 1 (with K > 0) for a plane
+ * that does not fit; VITSEG_EWORKSPACE: scratch smaller than the size function (0 for a bad shape).  Nothing is launched when
+ * a check fails. */
+#define VITSEG_PROPS_FIELDS 20
+size_t vitseg_region_props_scratch_bytes(int n, int H, int W, int K, int route);
+int vitseg_region_props(const uint8_t* mask, int n, int H, int W, int connectivity, int background,
+                        const int32_t* classes /* host, K values, may be NULL when K == 0 */, int K, int route,
+                        int32_t* counts /* [n] */, int64_t* props /* [n, max_regions, 20] */, int max_regions,
+                        int32_t* labels /* [n, H, W] or NULL */, void* scratch, size_t scratch_bytes, void* stream);
+
 /* one Adam step over a flat fp32 buffer (torch.optim.Adam semantics, weight_decay 0, amsgrad off: torch's L2 weight decay,
  * g += weight_decay * p, is not implemented, and FusedAdam refuses a nonzero weight_decay);
  * step is 1-based; gradients are multiplied by grad_scale first (1/world for summed all-reduce). */

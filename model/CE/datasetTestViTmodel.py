@@ -40,6 +40,12 @@ def main():
     ap.add_argument("--region-iou", type=float, default=0.5, help="a predicted and a true region match above this IoU (0.5 <= t < 1)")
     ap.add_argument("--region-coverage", type=float, default=0.5, help="a region is found / confirmed from this covered fraction on")
     ap.add_argument("--region-connectivity", type=int, default=4, choices=[4, 8])
+    ap.add_argument("--region-props", nargs="?", const="all", metavar="C0,C1,...|all",
+                    help="also write <model>_region_props.csv: one row per region of the prediction and of the ground truth "
+                         "(position, size, axes, orientation, perimeter, frame contact) and, for the listed classes (default: "
+                         "all present but the background 0), the region's own skeleton length and widths; regions by "
+                         "--region-connectivity")
+    ap.add_argument("--pixel-size", type=float, default=1.0, help="side of a pixel: the unit of the lengths in <model>_region_props.csv")
     ap.add_argument("--tta", help='test-time augmentation: "hflip", "flip" or "d4" -- the mask is merged from flipped / '
                                   "quarter-turned views (default: one look)")
     ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
@@ -63,7 +69,8 @@ def main():
                                        tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge,
                                        region_classes=True if a.region_metrics else None, region_iou=a.region_iou,
                                        region_coverage=a.region_coverage, region_connectivity=a.region_connectivity,
-                                       **clean.arguments(a))
+                                       props_classes=scripts.parse_props_classes(a.region_props),
+                                       props_pixel_size=a.pixel_size, **clean.arguments(a))
         acc = sum(r[8] for r in rows) / max(len(rows), 1)
         print(f"{name}: {len(rows)} images, mean accuracy {acc:.2f} %, {rows[0][11] * 1e3:.2f} ms/image")
 

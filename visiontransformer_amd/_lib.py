@@ -92,8 +92,13 @@ CLEAN_STATS = ("regions_removed", "pixels_removed", "holes_filled", "pixels_fill
 # bound on first use, the same way
 MATCH_EXPORTS = ["vitseg_region_match_scratch_bytes", "vitseg_region_match"]
 MATCH_STATS = ("n_gt", "n_pred", "tp", "gt_found", "pred_confirmed", "sum_q", "sum_i", "sum_u")
+# per-region measurements: moments, perimeter, frame contact, per-region skeleton length and widths (regions.region_props):
+# bound on first use, the same way
+PROPS_EXPORTS = ["vitseg_region_props_scratch_bytes", "vitseg_region_props"]
+PROPS_FIELDS = 20   # include/vitseg.h VITSEG_PROPS_FIELDS
 _LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
-                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS + CLEAN_EXPORTS + MATCH_EXPORTS)
+                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS + CLEAN_EXPORTS + MATCH_EXPORTS
+                 + PROPS_EXPORTS)
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -295,6 +300,11 @@ def lib() -> C.CDLL:
             l.vitseg_region_match_scratch_bytes.restype = sz
             l.vitseg_region_match.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,
                                               sz, vp]
+        if getattr(l, "vitseg_region_props", None) is not None:
+            l.vitseg_region_props_scratch_bytes.argtypes = [i32, i32, i32, i32, i32]
+            l.vitseg_region_props_scratch_bytes.restype = sz
+            l.vitseg_region_props.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp, i32, vp, vp,
+                                              sz, vp]
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -437,6 +447,15 @@ def match_symbol(name: str):
     fn = getattr(lib(), name, None)
     if fn is None:
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before the region matching): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def props_symbol(name: str):
+    """One of PROPS_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the per-region measurements): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
 

@@ -225,6 +225,11 @@ bool regions_shape_ok(int n, int H, int W);
 RegionWords region_words(void* scratch, int n, int H, int W);
 int launch_region_labels(const unsigned char* mask, int n, int H, int W, int connectivity, int background,
                          const RegionWords& w, hipStream_t s);
+// launches 4 - 6 of regions.hip (class_scan, emit, labels) after launch_region_labels, shared with props.hip: counts, the
+// records (the first max_regions; none when max_regions == 0), every root's full index in link[root] and, when `labels` is
+// not null, the index of every pixel's region.
+int launch_region_index(const unsigned char* mask, int n, int H, int W, const RegionWords& w, int* counts, int* regions,
+                        int max_regions, int* labels, hipStream_t s);
 // mask clean-up (clean.hip: vitseg_clean_mask): regions below min_area to background, enclosed holes filled
 size_t clean_scratch_bytes(int n, int H, int W);
 int launch_clean_mask(const unsigned char* mask, unsigned char* out, int n, int H, int W, int connectivity, int background,
@@ -235,5 +240,10 @@ size_t region_match_scratch_bytes(int n, int H, int W);
 int launch_region_match(const unsigned char* pred, const unsigned char* gt, int n, int H, int W, const int* classes, int K,
                         int connectivity, int background, int ignore_label, int thr_num, int thr_den, int cov_num, int cov_den,
                         long long* stats, int* pred_info, int* gt_info, void* scratch, size_t scratch_bytes, hipStream_t s);
+// per-region measurements (props.hip: vitseg_region_props): moments, perimeter, frame contact, per-region skeleton and widths
+size_t region_props_scratch_bytes(int n, int H, int W, int K, int route);
+int launch_region_props(const unsigned char* mask, int n, int H, int W, int connectivity, int background, const int* classes,
+                        int K, int route, int* counts, long long* props, int max_regions, int* labels, void* scratch,
+                        size_t scratch_bytes, hipStream_t s);
 
 }  // namespace vitseg

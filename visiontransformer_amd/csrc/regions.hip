@@ -379,13 +379,19 @@ int launch_regions(const unsigned char* mask, int n, int H, int W, int connectiv
     const size_t need = layout(n, H, W).total;
     VITSEG_CHECK_ARG(scratch_bytes >= need, VITSEG_EWORKSPACE, "regions: scratch of %zu bytes, %zu needed", scratch_bytes, need);
     const RegionWords w = region_words(scratch, n, H, W);
-    const Stats st{w.xmin, w.xmax, w.ymax, w.area};
-    const int P = H * W;
     if (max_regions > 0) {
         hipError_t e = hipMemsetAsync(regions, 0, (size_t)n * max_regions * 8 * sizeof(int), s);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(regions)");
     }
     if (const int rc = launch_region_labels(mask, n, H, W, connectivity, background, w, s)) return rc;
+    return launch_region_index(mask, n, H, W, w, counts, regions, max_regions, labels, s);
+}
+
+// launches 4 - 6 of the header.  Arguments are the caller's to check.
+int launch_region_index(const unsigned char* mask, int n, int H, int W, const RegionWords& w, int* counts, int* regions,
+                        int max_regions, int* labels, hipStream_t s) {
+    const Stats st{w.xmin, w.xmax, w.ymax, w.area};
+    const int P = H * W;
     hipLaunchKernelGGL(class_scan_kernel, dim3(n), dim3(256), 0, s, w.chunk_counts, w.offsets, counts, w.nchunks);
     VITSEG_LAUNCH_CHECK("regions class_scan");
     hipLaunchKernelGGL(emit_kernel, dim3(w.nchunks, n), dim3(64), 0, s, mask, w.root, w.link, st, w.offsets, regions, max_regions,

@@ -502,6 +502,39 @@ class Evaluator:
                 d["matches"] = tabs
         return out
 
+    def region_props(self, pred: torch.Tensor, gt: Optional[torch.Tensor] = None, skeleton_classes=None,
+                     connectivity: int = 4, background: int = 0, pixel_size: float = 1.0, route: str = "auto") -> List[dict]:
+        """Per image: dict(pred=[one dict per region of the prediction], gt=[the same for the ground truth, when given]) --
+        the dicts of regions.props_from_records (position, size, axes, orientation, perimeter, frame contact and, for
+        `skeleton_classes` (None: none; "all"; or label values), the region's own skeleton length and widths), in
+        `region_boxes`' (class, first) order, lengths in units of `pixel_size`.  A ground truth of another size is
+        nearest-resized to the prediction first, as `distance_stats` does.  One regions.region_props call per map."""
+        from . import regions as _regions
+        if not isinstance(pred, torch.Tensor) or pred.dtype != torch.uint8 or pred.dim() != 3:
+            raise ValueError(f"pred must be a uint8 tensor [n, H, W], got {getattr(pred, 'dtype', type(pred).__name__)}")
+        maps = {"pred": pred.to(self.device).contiguous()}
+        if gt is not None:
+            if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
+                raise ValueError("Number of images and masks must be equal!")
+            g = gt.to(self.device).to(torch.uint8).contiguous()
+            n, H, W = (int(d) for d in pred.shape)
+            if tuple(g.shape[1:]) != (H, W):
+                Hg, Wg = (int(d) for d in g.shape[1:])
+                g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
+                with torch.cuda.device(self.device):
+                    _lib.check(_lib.lib().vitseg_resize_nearest_u8(g.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
+                                                                   self._nearest(Wg, W).data_ptr(), H, W, None, 0,
+                                                                   g2.data_ptr(), torch.cuda.current_stream().cuda_stream))
+                g = g2
+            maps["gt"] = g
+        out = [dict() for _ in range(pred.shape[0])]
+        for name, m in maps.items():
+            recs = _regions.region_props(m, skeleton_classes=skeleton_classes, background=background,
+                                         connectivity=connectivity, route=route)
+            for d, r in zip(out, recs):
+                d[name] = _regions.props_from_records(r, pixel_size)
+        return out
+
     def evaluate(self, pred: torch.Tensor, gt: torch.Tensor) -> List[dict]:
         c = self.counts(pred, gt).cpu().numpy()
         px = int(pred.shape[1] * pred.shape[2])

@@ -499,19 +499,27 @@ class ViTSegmentationModel(nn.Module):
     @torch.no_grad()
     def predict_regions(self, x: torch.Tensor, *, background: int = 0, connectivity: int = 4, return_mask: bool = False,
                         interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,
-                        max_hole_area: int = 0):
+                        max_hole_area: int = 0, props: bool = False, skeleton_classes=None):
         """The regions of each image's predicted mask: a list of int32 [k, 7] numpy arrays, rows (class, y_min, x_min,
         y_max, x_max, area, first) in (class, first) order (regions.region_boxes) -- the reference's "Predicted Regions
         with Boxes" (model/CE/testViTModel.py:34-42,171-185).  The forward, the mask and the labelling are enqueued on one
         stream; the host waits once, for the region counts.  `return_mask`: also the uint8 [B, H, W] device mask.
         `min_area` / `fill_holes` / `max_hole_area` (defaults: off): the regions, and the mask returned, are those of the
-        mask cleaned by clean.clean_mask with this call's `connectivity` and `background`, enqueued on the same stream."""
+        mask cleaned by clean.clean_mask with this call's `connectivity` and `background`, enqueued on the same stream.
+        `props` (default off): the list holds the int64 [k, 20] measurement rows of regions.region_props instead (the same
+        regions in the same order; `skeleton_classes` as there), again of the cleaned mask when the clean-up is on."""
         from . import clean as _clean, regions as _regions
+        if skeleton_classes is not None and not props:
+            raise ValueError("skeleton_classes needs props=True")
         mask = self.predict_mask(x, interpolate_pos_encoding=interpolate_pos_encoding)
         if min_area or fill_holes or max_hole_area:   # with both steps off clean_mask checks its arguments and launches nothing
             mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area,
                                      connectivity=connectivity, background=background)
-        recs = _regions.region_boxes(mask, background=background, connectivity=connectivity)
+        if props:
+            recs = _regions.region_props(mask, skeleton_classes=skeleton_classes, background=background,
+                                         connectivity=connectivity)
+        else:
+            recs = _regions.region_boxes(mask, background=background, connectivity=connectivity)
         return (recs, mask) if return_mask else recs
 
     @torch.no_grad()

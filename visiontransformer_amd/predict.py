@@ -70,7 +70,8 @@ def preprocess(image, size: int, device="cuda:0") -> torch.Tensor:
 def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, index_to_color=None,
             return_logits: bool = False, serve_size: Optional[int] = None, return_boxes: bool = False,
             sliding: bool = False, stride: Optional[int] = None, weights: str = "linear", tta=None, tta_sizes=None,
-            tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0):
+            tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0,
+            return_props: bool = False, props_classes=None, pixel_size: float = 1.0):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
@@ -86,7 +87,11 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     [C, S, S] (probabilities for "probs").  With `sliding` it raises ValueError: TTA inside sliding windows is not built.
     `min_area` / `fill_holes` / `max_hole_area` (defaults: off): the mask, its colour rendering and its boxes are those of
     the mask cleaned on the device by clean.clean_mask (regions below `min_area` pixels to class 0, then enclosed holes of
-    at most `max_hole_area` pixels filled), after whichever route made it; the logits are not touched."""
+    at most `max_hole_area` pixels filled), after whichever route made it; the logits are not touched.
+    `return_props`: also, last of all, one dict per region of the (cleaned) mask in `region_boxes`' order -- position, size,
+    axes, orientation, perimeter, frame contact and, for the classes in `props_classes` (None: none; "all"; or label values),
+    the region's own skeleton length and widths (regions.region_props + regions.props_from_records), lengths in units of
+    `pixel_size`."""
     from . import clean as _clean
     _clean.check_options(min_area, fill_holes, max_hole_area)
     seg = model.model if isinstance(model, LightningViTModel) else model
@@ -114,6 +119,10 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     if return_boxes:
         from .regions import boxes_by_class, region_boxes
         boxes = boxes_by_class(region_boxes(mask_dev))
+    props = None
+    if return_props:
+        from .regions import props_from_records, region_props
+        props = props_from_records(region_props(mask_dev, skeleton_classes=props_classes), pixel_size)
     mask = mask_dev.cpu().numpy()
     res = [mask]
     if index_to_color is not None:
@@ -122,4 +131,6 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
         res.append(out[1][0].cpu().numpy())
     if return_boxes:
         res.append(boxes)
+    if return_props:
+        res.append(props)
     return res[0] if len(res) == 1 else tuple(res)

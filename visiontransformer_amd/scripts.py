@@ -15,6 +15,7 @@ import torch
 from . import synth
 from .metrics import (Evaluator, crack_csv_row, csv_row, distance_csv_row, matches_from_stats, pool_region_stats,
                       region_csv_row, write_crack_csv, write_distance_csv, write_metrics_csv, write_region_csv)
+from .regions import props_csv_row, write_props_csv
 
 
 def checkpoint_epoch(path: str) -> Optional[int]:
@@ -178,12 +179,23 @@ def run_validation(model, batches, device) -> dict:
     return {k: float(torch.stack([t.to("cpu") for t in v]).mean()) for k, v in acc.items()}
 
 
+def parse_props_classes(text: Optional[str]):
+    """The value of --region-props: None (flag absent), "all", or a comma-separated list of label values."""
+    if text is None or text == "all":
+        return text
+    try:
+        return [int(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        raise ValueError(f'--region-props takes "all" or comma-separated label values, got {text!r}') from None
+
+
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
                     distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
                     percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None,
                     tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False,
                     max_hole_area: int = 0, region_classes=None, region_csv_path: Optional[str] = None, region_iou=0.5,
-                    region_coverage=0.5, region_connectivity: int = 4) -> List[list]:
+                    region_coverage=0.5, region_connectivity: int = 4, props_classes=None,
+                    props_csv_path: Optional[str] = None, props_pixel_size: float = 1.0) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
@@ -199,12 +211,18 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     the clean-up is part of the time per image.
     region_classes (a list of label values, or True for every class but 0): the region-level detection statistics of every
     image and class (Evaluator.region_metrics at region_iou / region_coverage / region_connectivity) go to region_csv_path
-    (default: ..._region_metrics.csv), followed by one row per class of the integers pooled over all images."""
+    (default: ..._region_metrics.csv), followed by one row per class of the integers pooled over all images.
+    props_classes (None: off; a list of label values, "all", or True for every class but 0 -- the classes whose regions also get
+    their own skeleton length and widths; an empty list measures shape alone): one row per region of the prediction and of the
+    ground truth (Evaluator.region_props at region_connectivity, lengths in units of props_pixel_size) goes to props_csv_path
+    (default: ..._region_props.csv), with a Source column pred / gt."""
     from . import clean as _clean
     min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
     seg = getattr(model, "model", model)
     ev = Evaluator(num_classes, device)
-    rows, drows, crows, rrows, rstats = [], [], [], [], []
+    rows, drows, crows, rrows, rstats, prows = [], [], [], [], [], []
+    if props_classes is True:
+        props_classes = list(range(1, num_classes))
     if crack_classes is True:
         crack_classes = list(range(1, num_classes))
     if region_classes is True:
@@ -240,6 +258,12 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                 rstats.append(m["stats"])
                 for c, r in m["per_class"].items():
                     rrows.append(region_csv_row(model_info, bn, idx, c, region_iou, region_coverage, r))
+        if props_classes is not None:
+            for idx, m in enumerate(ev.region_props(mask, gt, skeleton_classes=props_classes, connectivity=region_connectivity,
+                                                    pixel_size=props_pixel_size)):
+                for source in ("pred", "gt"):
+                    for r, d in enumerate(m[source]):
+                        prows.append(props_csv_row(source, model_info, bn, idx, r, d))
     os.makedirs(os.path.dirname(os.path.abspath(csv_path)), exist_ok=True)
     write_metrics_csv(csv_path, rows)
     stem = csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
@@ -254,4 +278,6 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
             for c, r in zip(region_classes, matches_from_stats(pool_region_stats(rstats))):
                 rrows.append(region_csv_row(model_info, "pooled", "", c, region_iou, region_coverage, r))
         write_region_csv(region_csv_path or stem + "_region_metrics.csv", rrows)
+    if props_classes is not None:
+        write_props_csv(props_csv_path or stem + "_region_props.csv", prows)
     return rows
