@@ -709,6 +709,42 @@ int vitseg_region_props(const uint8_t* mask, int n, int H, int W, int connectivi
                         int32_t* counts /* [n] */, int64_t* props /* [n, max_regions, 20] */, int max_regions,
                         int32_t* labels /* [n, H, W] or NULL */, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- confidence: per-pixel scores of a stated mask, per-region score rows and a calibration histogram, re-generated from
+ *      the low-resolution head output (the full-size logits are never written; the host answer is predict_mask's logits, then
+ *      torch.sigmoid, gather, the rounding and index_add_ / bincount by label) ----
+ * lowres fp32 [n, C, g, g] (vitseg_forward_lowres; g == S is the identity of the taps: full-size logits are scored as they
+ * stand); mask uint8 [n, S, S], the class map whose confidence is asked for -- the decoder tail's, or a cleaned one.
+ * Per pixel, c = mask[pixel] and v_k = the bilinear value of class k with the decoder tail's arithmetic (scale g / S, taps
+ * src = max(scale * (d + 0.5) - 0.5, 0), row = fma(a, wx0, b * wx1), v = fma(top, wy0, bot * wy1)):
+ *   VITSEG_CONF_PROB    p = sigmoid(v_c), the sigmoid as ATen computes it for fp32: on the tail's own mask this is
+ *                       logits.sigmoid().max(dim=1).values;
+ *   VITSEG_CONF_MARGIN  p = min(max(sigmoid(v_c) - sigmoid(max_{k != c} v_k), 0), 1): the lead over the best other class, 0
+ *                       where the stated class did not win (C >= 2);
+ *   c >= C              p = 0, and lowres is not indexed.
+ *   q = (int) rintf(p * 65535.0f): the product rounded once in fp32, then to nearest even; 0 <= q <= 65535.
+ * Every step is a single correctly rounded fp32 operation, so a CPU restatement holds bit for bit (tests/confidence_ref.py).
+ * Outputs, any subset (none: VITSEG_EINVAL):
+ *   conf fp32 [n, S, S] = p;   conf_q uint16 [n, S, S] = q;
+ *   scores int64 [n, max_regions, 4], with labels int32 [n, S, S] = vitseg_regions' label plane of the same mask (negative:
+ *     no region; an index >= max_regions is skipped, nothing is written outside scores): per region the row
+ *     (pixels, sum_q, max_deficit, n_low), max_deficit = the maximum of 65535 - q over the region, n_low = the pixels with
+ *     q < low_q (0..65536).  A zero row means "no pixel": the rows past the count stay zero.
+ *   hist int64 [n, bins, 3], with gt uint8 [n, S, S]: pixels with gt == ignore_label (-1: none, or 0..255) are void; per image
+ *     and bin = (q * bins) >> 16 (bins 1..256) the row (pixels, pixels with mask == gt, sum_q).
+ * scores and hist are cleared by the call (one memset each), then ONE kernel runs on `stream`: no allocation, no scratch, no
+ * host synchronisation.  The accumulators are 64-bit integer atomicAdd / atomicMax, order-independent: the same bits on every
+ * call, and per image the same bits in any batch.
+ * Each with a vitseg_last_error text and nothing launched -- VITSEG_EINVAL: null lowres or mask, no output, scores without
+ * labels, hist without gt, kind not 0 / 1, margin with C < 2, and for the output that reads them: negative max_regions, low_q
+ * outside 0..65536, bins outside 1..256, ignore_label outside -1..255; VITSEG_ESHAPE: C outside 1..255, n outside 1..65535,
+ * S outside 1..16384, g outside 1..S. */
+enum vitseg_conf_kind { VITSEG_CONF_PROB = 0, VITSEG_CONF_MARGIN = 1 };
+int vitseg_confidence(const float* lowres /* [n, C, g, g] */, const uint8_t* mask /* [n, S, S] */, int n, int C, int g, int S,
+                      int kind, float* conf /* [n, S, S] or NULL */, uint16_t* conf_q /* [n, S, S] or NULL */,
+                      const int32_t* labels /* [n, S, S] or NULL */, int64_t* scores /* [n, max_regions, 4] or NULL */,
+                      int max_regions, int low_q, const uint8_t* gt /* [n, S, S] or NULL */, int ignore_label,
+                      int64_t* hist /* [n, bins, 3] or NULL */, int bins, void* stream);
+
 /* one Adam step over a flat fp32 buffer (torch.optim.Adam semantics, weight_decay 0, amsgrad off: torch's L2 weight decay,
  * g += weight_decay * p, is not implemented, and FusedAdam refuses a nonzero weight_decay);
  * step is 1-based; gradients are multiplied by grad_scale first (1/world for summed all-reduce). */

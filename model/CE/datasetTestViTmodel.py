@@ -51,7 +51,9 @@ def main():
     ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
     ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"], help="mean of the views' logits or of their sigmoids")
     clean.add_arguments(ap)
+    scripts.add_confidence_arguments(ap)
     a = ap.parse_args()
+    confidence = scripts.confidence_options(ap, a)
     dev = "cuda:0"
     cwd = os.getcwd()
     for vid in a.ids:
@@ -70,7 +72,7 @@ def main():
                                        region_classes=True if a.region_metrics else None, region_iou=a.region_iou,
                                        region_coverage=a.region_coverage, region_connectivity=a.region_connectivity,
                                        props_classes=scripts.parse_props_classes(a.region_props),
-                                       props_pixel_size=a.pixel_size, **clean.arguments(a))
+                                       props_pixel_size=a.pixel_size, **clean.arguments(a), **confidence)
         acc = sum(r[8] for r in rows) / max(len(rows), 1)
         print(f"{name}: {len(rows)} images, mean accuracy {acc:.2f} %, {rows[0][11] * 1e3:.2f} ms/image")
 

@@ -54,7 +54,9 @@ def main():
     ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
     ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"], help="mean of the views' logits or of their sigmoids")
     clean.add_arguments(ap)
+    scripts.add_confidence_arguments(ap)
     a = ap.parse_args()
+    confidence = scripts.confidence_options(ap, a)
     dev = "cuda:0"
     cwd = os.getcwd()
     for vid in a.ids:
@@ -75,7 +77,7 @@ def main():
                                        region_classes=True if a.region_metrics else None, region_iou=a.region_iou,
                                        region_coverage=a.region_coverage, region_connectivity=a.region_connectivity,
                                        props_classes=scripts.parse_props_classes(a.region_props),
-                                       props_pixel_size=a.pixel_size, **clean.arguments(a))
+                                       props_pixel_size=a.pixel_size, **clean.arguments(a), **confidence)
         print(f"{name}: {len(rows)} images evaluated -> {os.path.join(a.out, name)}")
 
 

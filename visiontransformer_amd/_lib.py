@@ -96,9 +96,13 @@ MATCH_STATS = ("n_gt", "n_pred", "tp", "gt_found", "pred_confirmed", "sum_q", "s
 # bound on first use, the same way
 PROPS_EXPORTS = ["vitseg_region_props_scratch_bytes", "vitseg_region_props"]
 PROPS_FIELDS = 20   # include/vitseg.h VITSEG_PROPS_FIELDS
+# confidence of a stated mask: per-pixel scores, per-region score rows, calibration histogram (confidence.py): bound on first
+# use, the same way
+CONFIDENCE_EXPORTS = ["vitseg_confidence"]
+CONF_PROB, CONF_MARGIN = 0, 1   # enum vitseg_conf_kind
 _LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
                  + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS + CLEAN_EXPORTS + MATCH_EXPORTS
-                 + PROPS_EXPORTS)
+                 + PROPS_EXPORTS + CONFIDENCE_EXPORTS)
 EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
@@ -305,6 +309,8 @@ def lib() -> C.CDLL:
             l.vitseg_region_props_scratch_bytes.restype = sz
             l.vitseg_region_props.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp, i32, vp, vp,
                                               sz, vp]
+        if getattr(l, "vitseg_confidence", None) is not None:
+            l.vitseg_confidence.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp]
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -456,6 +462,15 @@ def props_symbol(name: str):
     fn = getattr(lib(), name, None)
     if fn is None:
         raise RuntimeError(f"{LIB_PATH} has no {name} (built before the per-region measurements): rebuild it "
+                           "(python -m visiontransformer_amd.build)")
+    return fn
+
+
+def confidence_symbol(name: str):
+    """One of CONFIDENCE_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the confidence scores): rebuild it "
                            "(python -m visiontransformer_amd.build)")
     return fn
 

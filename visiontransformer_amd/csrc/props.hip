@@ -29,6 +29,7 @@
 // All sums are 64-bit integer atomicAdd / atomicMax: order-independent, so the bits do not depend on which region a chunk
 // picks, on the schedule, on the route or on the batch.  Products are formed in 64 bits before they are added.
 #include "kernels.hpp"
+#include "run_reduce.hpp"
 
 namespace vitseg {
 namespace {
@@ -39,43 +40,12 @@ constexpr int PROPS_MAX_SIDE = 16384, PROPS_MAX_BATCH = 32767;
 enum { F_CLASS, F_FIRST, F_AREA, F_YMIN, F_XMIN, F_YMAX, F_XMAX, F_SY, F_SX, F_SYY, F_SXX, F_SXY, F_PERIM, F_FRAME, F_MAXD2,
        F_SKEL, F_ENDS, F_SKELMAX, F_WIDTH };
 
-typedef unsigned long long u64;
-typedef long long i64;
-
 struct ClassSet {   // bit c of the 256: class c is measured
     unsigned bits[8];
     __host__ __device__ bool has(int c) const { return (bits[c >> 5] >> (c & 31)) & 1u; }
 };
 
-// The lanes of a wave hold 64 consecutive pixels; key >= 0 is the pixel's region index (-1: none) and y its row.  A run is a
-// maximal stretch of lanes with one key in one row.  head: this lane starts a run; end: the first lane past the run this lane
-// is in (meaningless where key < 0); members: at a head, the lanes of its run.  Whole waves call it.
-struct Run {
-    bool head;
-    int end;
-    u64 members;
-};
-
-__device__ __forceinline__ Run find_run(int key, int y, int lane) {
-    const int key_prev = __shfl_up(key, 1), y_prev = __shfl_up(y, 1);
-    Run r;
-    r.head = key >= 0 && (lane == 0 || key_prev != key || y_prev != y);
-    const u64 upto = (2ull << lane) - 1ull;   // this lane and the ones below it
-    const u64 stops = __ballot(r.head || key < 0) & ~upto;
-    r.end = stops ? __ffsll((long long)stops) - 1 : WAVE;
-    r.members = (r.end == WAVE ? ~0ull : (1ull << r.end) - 1ull) & ~((1ull << lane) - 1ull);
-    return r;
-}
-
-// at every lane of a run: op over the values from this lane to the run's last; the head gets the run's total.  Whole waves.
-template <typename T, typename Op>
-__device__ __forceinline__ T run_reduce(T v, int lane, int end, Op op) {
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const T o = __shfl_down(v, d);
-        if (lane + d < end) v = op(v, o);
-    }
-    return v;
-}
+// (the runs of equal region index within a wave, find_run / run_reduce: run_reduce.hpp, shared with confidence.hip)
 
 // the region whose runs a workgroup collects in LDS: the one at the chunk's first pixel, else at its middle pixel; -1 when
 // neither has one (or its row is not written).  cls >= 0: only a region of that class.

@@ -276,6 +276,23 @@ class Evaluator:
                                                      torch.cuda.current_stream().cuda_stream))
         return out
 
+    def resized_gt(self, gt: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
+        """The ground truth as uint8 [n, H, W] on the device, nearest-resized to the prediction's size as `distance_stats`
+        does (the tensor itself, cast, when the sizes agree)."""
+        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
+            raise ValueError("Number of images and masks must be equal!")
+        gt = gt.to(self.device).to(torch.uint8).contiguous()
+        n, H, W = (int(d) for d in pred.shape)
+        if tuple(gt.shape[1:]) == (H, W):
+            return gt
+        Hg, Wg = (int(d) for d in gt.shape[1:])
+        g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
+                                                           self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
+                                                           torch.cuda.current_stream().cuda_stream))
+        return g2
+
     def distance_stats(self, pred: torch.Tensor, gt: torch.Tensor, classes: Sequence[int], mode: int, pct_num: int,
                        pct_den: int):
         """(stats_i int64 [n, K, 6], stats_f float64 [n, K, 2]) device tensors of vitseg_distance_stats for uint8 predictions

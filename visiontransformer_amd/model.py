@@ -496,10 +496,34 @@ class ViTSegmentationModel(nn.Module):
         logits, mask = self._run(x, return_logits, True, interp=bool(interpolate_pos_encoding))
         return (mask, logits) if return_logits else mask
 
+    def _lowres_and_mask(self, x: torch.Tensor, interp: bool = False):
+        """(lowres fp32 [B, C, g, g], mask uint8 [B, S, S]) of one encoder pass: the forward that stops at the head output
+        (vitseg_forward_lowres) and a one-tile blend, whose single-tile rule returns the bilinear value unchanged -- the
+        mask is `predict_mask`'s bit for bit, and no full-size logits are written."""
+        self._check_input(x, interp)
+        S, B = self._size_in(x, interp), int(x.shape[0])
+        plan = self._window_lowres(x.to(torch.float32), False, S, S, "uniform", B)
+        return plan["lowres"], self._window_blend(plan, False, True)
+
+    @torch.no_grad()
+    def predict_confidence(self, x: torch.Tensor, kind: str = "prob", quantised: bool = False,
+                           interpolate_pos_encoding: bool = False):
+        """(mask uint8 [B, H, W], conf [B, H, W]): `predict_mask`'s mask and every pixel's score (confidence.confidence_map:
+        fp32 p, or uint16 q = rint(p * 65535) with `quantised`).  kind "prob": the sigmoid that won, exactly
+        `logits.sigmoid().max(dim=1).values` of `predict_mask(return_logits=True)`'s logits; "margin": its lead over the best
+        other class.  The encoder runs once and the scores are re-generated from the low-res head output: the full-size
+        logits are never written."""
+        from . import confidence as _conf
+        if kind not in _conf.KINDS:
+            raise ValueError(f"kind must be one of {sorted(_conf.KINDS)}, got {kind!r}")
+        lowres, mask = self._lowres_and_mask(x, bool(interpolate_pos_encoding))
+        return mask, _conf.confidence_map(lowres, mask, kind=kind, quantised=quantised)
+
     @torch.no_grad()
     def predict_regions(self, x: torch.Tensor, *, background: int = 0, connectivity: int = 4, return_mask: bool = False,
                         interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,
-                        max_hole_area: int = 0, props: bool = False, skeleton_classes=None):
+                        max_hole_area: int = 0, props: bool = False, skeleton_classes=None, scores: bool = False,
+                        score_kind: str = "prob", low: float = 0.5):
         """The regions of each image's predicted mask: a list of int32 [k, 7] numpy arrays, rows (class, y_min, x_min,
         y_max, x_max, area, first) in (class, first) order (regions.region_boxes) -- the reference's "Predicted Regions
         with Boxes" (model/CE/testViTModel.py:34-42,171-185).  The forward, the mask and the labelling are enqueued on one
@@ -507,19 +531,37 @@ class ViTSegmentationModel(nn.Module):
         `min_area` / `fill_holes` / `max_hole_area` (defaults: off): the regions, and the mask returned, are those of the
         mask cleaned by clean.clean_mask with this call's `connectivity` and `background`, enqueued on the same stream.
         `props` (default off): the list holds the int64 [k, 20] measurement rows of regions.region_props instead (the same
-        regions in the same order; `skeleton_classes` as there), again of the cleaned mask when the clean-up is on."""
+        regions in the same order; `skeleton_classes` as there), again of the cleaned mask when the clean-up is on.
+        `scores` (default off): the result is (records or props, score_rows[, mask]) -- per image the int64 [k, 4] rows
+        (pixels, sum_q, max_deficit, n_low) of confidence.region_scores for the same regions in the same order (`score_kind`,
+        `low` as there), scored on the cleaned mask when the clean-up is on: a filled hole carries a class that did not win
+        and scores accordingly.  The encoder still runs once; the mask is `predict_mask`'s bit for bit."""
         from . import clean as _clean, regions as _regions
         if skeleton_classes is not None and not props:
             raise ValueError("skeleton_classes needs props=True")
-        mask = self.predict_mask(x, interpolate_pos_encoding=interpolate_pos_encoding)
+        lowres = None
+        if scores:
+            from . import confidence as _conf
+            if score_kind not in _conf.KINDS:
+                raise ValueError(f"score_kind must be one of {sorted(_conf.KINDS)}, got {score_kind!r}")
+            _conf.low_to_q(low)
+            lowres, mask = self._lowres_and_mask(x, bool(interpolate_pos_encoding))
+        else:
+            mask = self.predict_mask(x, interpolate_pos_encoding=interpolate_pos_encoding)
         if min_area or fill_holes or max_hole_area:   # with both steps off clean_mask checks its arguments and launches nothing
             mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area,
                                      connectivity=connectivity, background=background)
         if props:
             recs = _regions.region_props(mask, skeleton_classes=skeleton_classes, background=background,
                                          connectivity=connectivity)
-        else:
+        elif not scores:
             recs = _regions.region_boxes(mask, background=background, connectivity=connectivity)
+        if scores:
+            boxes, rows = _conf.region_scores(lowres, mask, kind=score_kind, low=low, background=background,
+                                              connectivity=connectivity)
+            if not props:
+                recs = boxes
+            return (recs, rows, mask) if return_mask else (recs, rows)
         return (recs, mask) if return_mask else recs
 
     @torch.no_grad()

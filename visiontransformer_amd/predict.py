@@ -71,7 +71,8 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
             return_logits: bool = False, serve_size: Optional[int] = None, return_boxes: bool = False,
             sliding: bool = False, stride: Optional[int] = None, weights: str = "linear", tta=None, tta_sizes=None,
             tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0,
-            return_props: bool = False, props_classes=None, pixel_size: float = 1.0):
+            return_props: bool = False, props_classes=None, pixel_size: float = 1.0, return_scores: bool = False,
+            return_confidence: bool = False, score_kind: str = "prob", low: float = 0.5):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
@@ -91,9 +92,24 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     `return_props`: also, last of all, one dict per region of the (cleaned) mask in `region_boxes`' order -- position, size,
     axes, orientation, perimeter, frame contact and, for the classes in `props_classes` (None: none; "all"; or label values),
     the region's own skeleton length and widths (regions.region_props + regions.props_from_records), lengths in units of
-    `pixel_size`."""
+    `pixel_size`.
+    `return_scores` / `return_confidence` (appended last, in this order): one dict per region of the (cleaned) mask in
+    `region_boxes`' order -- class, first, area, score (the mean of its pixels' p), score_min, low_fraction (the share of its
+    pixels with p below `low`) -- and the fp32 [S, S] map of p (confidence.region_scores / confidence_map; `score_kind`
+    "prob": the sigmoid of the class the mask states, "margin": its lead over the best other class).  The scores are
+    re-generated on the device from the low-res head output of the same forward.  With `sliding` or `tta` they raise
+    ValueError before anything runs: scoring blended views is not built."""
     from . import clean as _clean
     _clean.check_options(min_area, fill_holes, max_hole_area)
+    scoring = bool(return_scores or return_confidence)
+    if scoring:
+        from . import confidence as _conf
+        if sliding or tta is not None:
+            raise ValueError("return_scores / return_confidence with sliding=True or tta= is not supported: the scores are "
+                             "those of one forward of the resized image")
+        if score_kind not in _conf.KINDS:
+            raise ValueError(f"score_kind must be one of {sorted(_conf.KINDS)}, got {score_kind!r}")
+        _conf.low_to_q(low)
     seg = model.model if isinstance(model, LightningViTModel) else model
     S = serve_size if serve_size is not None else getattr(model, "serve_size", None)
     S = seg.cfg.image_size if S is None else int(S)
@@ -109,9 +125,15 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
                              f"{tuple(img.shape[:2])[0]}x{tuple(img.shape[:2])[1]}")
         out = seg.predict_mask_windowed(img[None].to(seg.arena.device), stride=stride, weights=weights, window_size=S,
                                         return_logits=return_logits)
+    elif scoring and not return_logits:   # one encoder pass that keeps the low-res head output; predict_mask's mask
+        x = preprocess(image, S, seg.arena.device)
+        with torch.no_grad():
+            lowres, out = seg._lowres_and_mask(x, S != seg.cfg.image_size)
     else:
         x = preprocess(image, S, seg.arena.device)
         out = seg.predict_mask(x, return_logits=return_logits, interpolate_pos_encoding=S != seg.cfg.image_size)
+        if scoring:
+            lowres = out[1]   # the full-size logits are there already: scored as they stand (g == S)
     mask_dev = (out[0] if return_logits else out)[0]
     if _clean.active(min_area, fill_holes):
         mask_dev = _clean.clean_mask(mask_dev, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area)
@@ -123,6 +145,11 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     if return_props:
         from .regions import props_from_records, region_props
         props = props_from_records(region_props(mask_dev, skeleton_classes=props_classes), pixel_size)
+    region_scores = conf_map = None
+    if return_scores:
+        region_scores = _conf.region_dicts(*_conf.region_scores(lowres[0], mask_dev, kind=score_kind, low=low))
+    if return_confidence:
+        conf_map = _conf.confidence_map(lowres[0], mask_dev, kind=score_kind).cpu().numpy()
     mask = mask_dev.cpu().numpy()
     res = [mask]
     if index_to_color is not None:
@@ -133,4 +160,8 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
         res.append(boxes)
     if return_props:
         res.append(props)
+    if return_scores:
+        res.append(region_scores)
+    if return_confidence:
+        res.append(conf_map)
     return res[0] if len(res) == 1 else tuple(res)

@@ -189,13 +189,42 @@ def parse_props_classes(text: Optional[str]):
         raise ValueError(f'--region-props takes "all" or comma-separated label values, got {text!r}') from None
 
 
+def add_confidence_arguments(ap) -> None:
+    """--region-scores / --score-kind / --score-low / --calibration of the evaluation scripts."""
+    ap.add_argument("--region-scores", action="store_true",
+                    help="also write <model>_region_scores.csv: one row per predicted region with its confidence score (mean, "
+                         "minimum, share of low pixels); with --region-metrics also its matched flag and one pooled AP row per "
+                         "class; regions by --region-connectivity")
+    ap.add_argument("--score-kind", default="prob", choices=["prob", "margin"],
+                    help="a pixel's score: the sigmoid of its class, or its lead over the best other class")
+    ap.add_argument("--score-low", type=float, default=0.5, help="pixels scoring below this count as low (0..1)")
+    ap.add_argument("--calibration", nargs="?", const=16, type=int, metavar="BINS",
+                    help="also write <model>_calibration.csv: the reliability table pooled over all images (default 16 bins, "
+                         "1..256) and the expected calibration error")
+
+
+def confidence_options(ap, a) -> dict:
+    """The keywords of `evaluate_to_csv` from the parsed flags; refused when arguments are parsed (ap.error): a score flag
+    with --tta, --score-low outside 0..1, BINS outside 1..256."""
+    on = a.region_scores or a.calibration is not None
+    if on and getattr(a, "tta", None):
+        ap.error("--region-scores / --calibration cannot be combined with --tta: the scores are those of one forward")
+    if not 0.0 <= a.score_low <= 1.0:
+        ap.error(f"--score-low must lie in 0..1, got {a.score_low}")
+    if a.calibration is not None and not 1 <= a.calibration <= 256:
+        ap.error(f"--calibration takes 1..256 bins, got {a.calibration}")
+    return dict(region_scores=a.region_scores, score_kind=a.score_kind, score_low=a.score_low, calibration_bins=a.calibration)
+
+
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
                     distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
                     percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None,
                     tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False,
                     max_hole_area: int = 0, region_classes=None, region_csv_path: Optional[str] = None, region_iou=0.5,
                     region_coverage=0.5, region_connectivity: int = 4, props_classes=None,
-                    props_csv_path: Optional[str] = None, props_pixel_size: float = 1.0) -> List[list]:
+                    props_csv_path: Optional[str] = None, props_pixel_size: float = 1.0, region_scores: bool = False,
+                    score_kind: str = "prob", score_low: float = 0.5, calibration_bins: Optional[int] = None,
+                    scores_csv_path: Optional[str] = None, calibration_csv_path: Optional[str] = None) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
@@ -215,12 +244,33 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     props_classes (None: off; a list of label values, "all", or True for every class but 0 -- the classes whose regions also get
     their own skeleton length and widths; an empty list measures shape alone): one row per region of the prediction and of the
     ground truth (Evaluator.region_props at region_connectivity, lengths in units of props_pixel_size) goes to props_csv_path
-    (default: ..._region_props.csv), with a Source column pred / gt."""
+    (default: ..._region_props.csv), with a Source column pred / gt.
+    region_scores (default off): one row per predicted region -- class, first, area, score, score_min, low_fraction
+    (confidence.region_scores with score_kind / score_low at region_connectivity, on the cleaned mask when the clean-up is
+    on) -- goes to scores_csv_path (default: ..._region_scores.csv).  With region_classes the row also holds the region's
+    `matched` flag, joined on `first` to Evaluator.region_metrics(return_matches=True), and one pooled AP row per class
+    follows (confidence.average_precision over all images' regions of the class against the pooled n_gt).
+    calibration_bins (None: off): the reliability table pooled over all images (confidence.calibration_hist of the mask against
+    the resized ground truth, the integers added before any ratio) and its ECE go to calibration_csv_path (default:
+    ..._calibration.csv).  Either makes the forward keep its low-res head output (one encoder pass, predict_mask's mask bit
+    for bit); with tta they raise ValueError: scoring merged views is not built."""
     from . import clean as _clean
+    from . import confidence as _conf
     min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
+    scoring = bool(region_scores) or calibration_bins is not None
+    if scoring:
+        if tta is not None:
+            raise ValueError("region_scores / calibration_bins with tta are not supported: the scores are those of one forward")
+        if score_kind not in _conf.KINDS:
+            raise ValueError(f"score_kind must be one of {sorted(_conf.KINDS)}, got {score_kind!r}")
+        _conf.low_to_q(score_low)
+        if calibration_bins is not None and (isinstance(calibration_bins, bool) or not isinstance(calibration_bins, int)
+                                             or not 1 <= calibration_bins <= _conf.MAX_BINS):
+            raise ValueError(f"calibration_bins must be None or an integer in 1..{_conf.MAX_BINS}, got {calibration_bins!r}")
     seg = getattr(model, "model", model)
     ev = Evaluator(num_classes, device)
     rows, drows, crows, rrows, rstats, prows = [], [], [], [], [], []
+    srows, ranked, pooled_hist = [], {}, None
     if props_classes is True:
         props_classes = list(range(1, num_classes))
     if crack_classes is True:
@@ -237,6 +287,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         with torch.no_grad():
             if tta is not None:
                 mask = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge)
+            elif scoring:
+                lowres, mask = seg._lowres_and_mask(x)
             else:
                 mask = seg.predict_mask(x)
             if _clean.active(min_area, fill_holes):
@@ -252,12 +304,29 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         if crack_classes:
             for idx, m in enumerate(ev.crack_metrics(mask, gt, classes=crack_classes)):
                 crows.append(crack_csv_row(model_info, bn, idx, m))
+        matched = None   # per image {(class, first): the predicted region has a partner}
         if region_classes:
-            for idx, m in enumerate(ev.region_metrics(mask, gt, classes=region_classes, iou_threshold=region_iou,
-                                                      coverage=region_coverage, connectivity=region_connectivity)):
+            extra = dict(return_matches=True) if region_scores else {}
+            found = ev.region_metrics(mask, gt, classes=region_classes, iou_threshold=region_iou, coverage=region_coverage,
+                                      connectivity=region_connectivity, **extra)
+            for idx, m in enumerate(found):
                 rstats.append(m["stats"])
                 for c, r in m["per_class"].items():
                     rrows.append(region_csv_row(model_info, bn, idx, c, region_iou, region_coverage, r))
+            if region_scores:
+                matched = [{(int(r[0]), int(r[6])): int(r[7]) >= 0 for r in m["matches"]["pred"]} for m in found]
+        if region_scores:
+            recs, srow = _conf.region_scores(lowres, mask, kind=score_kind, low=score_low, connectivity=region_connectivity)
+            for idx, (rec, row) in enumerate(zip(recs, srow)):
+                for r, d in enumerate(_conf.region_dicts(rec, row)):
+                    flag = "" if matched is None else matched[idx].get((d["class"], d["first"]), "")
+                    if flag != "":
+                        ranked.setdefault(d["class"], []).append((d["score"], flag))
+                    srows.append([model_info[0], model_info[1], bn, idx, r, d["class"], d["first"], d["area"], d["score"],
+                                  d["score_min"], d["low_fraction"], "" if flag == "" else int(flag), "", ""])
+        if calibration_bins is not None:
+            h = _conf.calibration_hist(lowres, mask, ev.resized_gt(gt, mask), bins=calibration_bins, kind=score_kind)
+            pooled_hist = h.sum(axis=0) if pooled_hist is None else pooled_hist + h.sum(axis=0)
         if props_classes is not None:
             for idx, m in enumerate(ev.region_props(mask, gt, skeleton_classes=props_classes, connectivity=region_connectivity,
                                                     pixel_size=props_pixel_size)):
@@ -280,4 +349,15 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         write_region_csv(region_csv_path or stem + "_region_metrics.csv", rrows)
     if props_classes is not None:
         write_props_csv(props_csv_path or stem + "_region_props.csv", prows)
+    if region_scores:
+        if region_classes and rstats:
+            n_gt = pool_region_stats(rstats)[:, 0]
+            for c, k in zip(region_classes, n_gt):
+                det = ranked.get(c, [])
+                ap = _conf.average_precision([s for s, _ in det], [f for _, f in det], int(k))
+                srows.append([model_info[0], model_info[1], "pooled", "", "", c, "", "", "", "", "", "", ap, int(k)])
+        _conf.write_csv(scores_csv_path or stem + "_region_scores.csv", _conf.SCORES_CSV_COLUMNS, srows)
+    if calibration_bins is not None:
+        _conf.write_csv(calibration_csv_path or stem + "_calibration.csv", _conf.CALIBRATION_CSV_COLUMNS,
+                        _conf.calibration_csv_rows(model_info, pooled_hist, calibration_bins))
     return rows
