@@ -61,7 +61,7 @@ def probe(n, S, fmt, iters, dev):
     y = torch.empty((n, S, S), dtype=torch.uint8, device=dev)
     desc = (_lib.CAugmentMask * 1)(_lib.CAugmentMask(mask.data_ptr(), tab.data_ptr() + n * 48, y.data_ptr(), 0, 0, MASK, MASK, S, S))
     fill = (C.c_float * 3)(0, 0, 0)
-    fn = _lib.augment_symbol("vitseg_augment")
+    fn = _lib.symbol("vitseg_augment")
     st = torch.cuda.current_stream().cuda_stream
 
     def kernel(with_mask=True, with_colour=True):

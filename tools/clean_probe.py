@@ -29,8 +29,8 @@ def clean_call(md, min_area, fill_holes):
     n, H, W = md.shape
     out = torch.empty_like(md)
     stats = torch.empty((n, 8), dtype=torch.int32, device=md.device)
-    scratch = torch.empty(_lib.clean_symbol("vitseg_clean_scratch_bytes")(n, H, W), dtype=torch.uint8, device=md.device)
-    f = _lib.clean_symbol("vitseg_clean_mask")
+    scratch = torch.empty(_lib.symbol("vitseg_clean_scratch_bytes")(n, H, W), dtype=torch.uint8, device=md.device)
+    f = _lib.symbol("vitseg_clean_mask")
     stream = torch.cuda.current_stream().cuda_stream
 
     def call():
@@ -43,10 +43,10 @@ def regions_call(md):
     n, H, W = md.shape
     counts, _, _ = regions._launch(md, 0, 4, 0, False)
     cap = int(counts.max())
-    scratch = torch.empty(_lib.region_symbol("vitseg_regions_scratch_bytes")(n, H, W), dtype=torch.uint8, device=md.device)
+    scratch = torch.empty(_lib.symbol("vitseg_regions_scratch_bytes")(n, H, W), dtype=torch.uint8, device=md.device)
     recs = torch.empty((n, cap, 8), dtype=torch.int32, device=md.device)
     labels = torch.empty((n, H, W), dtype=torch.int32, device=md.device)
-    f = _lib.region_symbol("vitseg_regions")
+    f = _lib.symbol("vitseg_regions")
     stream = torch.cuda.current_stream().cuda_stream
 
     def call():

@@ -43,7 +43,7 @@ def make_calls(B, C_, g, S, seed=0):
     def buffers():
         G = torch.empty((B, C_, S, S), dtype=torch.float32, device=DEV)
         scratch = torch.empty(L.vitseg_ce_scratch_bytes(B, S), dtype=torch.uint8, device=DEV)
-        nbytes = int(_lib.ce_opts_symbol("vitseg_ce_options_scratch_bytes")(B, S))
+        nbytes = int(_lib.symbol("vitseg_ce_options_scratch_bytes")(B, S))
         oscr = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
         o = _lib.CCEOptions(1, 0, 255, None, 0.0, oscr.data_ptr(), nbytes)
         out = torch.zeros(3, dtype=torch.float32, device=DEV)   # (vitseg_ce_loss_opts writes the first alone)
@@ -51,17 +51,17 @@ def make_calls(B, C_, g, S, seed=0):
 
     def ce_opts():
         G, scratch, oscr, o, out = buffers()
-        _lib.check(_lib.ce_opts_symbol("vitseg_ce_loss_opts")(z.data_ptr(), t.data_ptr(), 1, G.data_ptr(), scratch.data_ptr(),
-                                                              out.data_ptr(), B, C_, g, S, C.byref(o), 1.0, _stream()))
+        _lib.check(_lib.symbol("vitseg_ce_loss_opts")(z.data_ptr(), t.data_ptr(), 1, G.data_ptr(), scratch.data_ptr(),
+                                                      out.data_ptr(), B, C_, g, S, C.byref(o), 1.0, _stream()))
         state["ce_opts"] = (out, G)
 
     def ce_dice():
         G, scratch, oscr, o, out = buffers()
-        dbytes = int(_lib.dice_symbol("vitseg_dice_options_scratch_bytes")(B, C_, S))
+        dbytes = int(_lib.symbol("vitseg_dice_options_scratch_bytes")(B, C_, S))
         dscr = torch.empty(dbytes, dtype=torch.uint8, device=DEV)
         d = _lib.CDiceOptions(1.0, 1.0, 1e-6, 1, dscr.data_ptr(), dbytes)
-        _lib.check(_lib.dice_symbol("vitseg_ce_dice_loss")(z.data_ptr(), t.data_ptr(), 1, G.data_ptr(), scratch.data_ptr(),
-                                                           out.data_ptr(), B, C_, g, S, C.byref(o), C.byref(d), 1.0, _stream()))
+        _lib.check(_lib.symbol("vitseg_ce_dice_loss")(z.data_ptr(), t.data_ptr(), 1, G.data_ptr(), scratch.data_ptr(),
+                                                      out.data_ptr(), B, C_, g, S, C.byref(o), C.byref(d), 1.0, _stream()))
         state["ce_dice"] = (out, G)
 
     def torch_composition():

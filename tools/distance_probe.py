@@ -35,8 +35,8 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--no-host", action="store_true", help="skip the scipy timing (e.g. under rocprofv3)")
     a = ap.parse_args()
-    fn = _lib.distance_symbol("vitseg_distance_stats")
-    nbytes = _lib.distance_symbol("vitseg_distance_scratch_bytes")(N, S, S)
+    fn = _lib.symbol("vitseg_distance_stats")
+    nbytes = _lib.symbol("vitseg_distance_scratch_bytes")(N, S, S)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     lines = [f"vitseg_distance_stats, {N} x {S}^2, percentile 95; median of {a.iters} hipEvent-timed calls after 2 warm-up calls; "
              f"scratch {nbytes / 2 ** 20:.0f} MiB",

@@ -47,12 +47,12 @@ def match_call(pred, gt, classes):
     n, H, W = pred.shape
     K = len(classes)
     cls = (ctypes.c_int32 * K)(*classes)
-    nbytes = _lib.match_symbol("vitseg_region_match_scratch_bytes")(n, H, W)
+    nbytes = _lib.symbol("vitseg_region_match_scratch_bytes")(n, H, W)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     stats = torch.empty((n, K, 8), dtype=torch.int64, device=pred.device)
     pinfo = torch.empty((n, H, W, 2), dtype=torch.int32, device=pred.device)
     ginfo = torch.empty((n, H, W, 2), dtype=torch.int32, device=pred.device)
-    f = _lib.match_symbol("vitseg_region_match")
+    f = _lib.symbol("vitseg_region_match")
     stream = torch.cuda.current_stream().cuda_stream
 
     def call():
@@ -65,10 +65,10 @@ def regions_call(md):
     n, H, W = md.shape
     counts, _, _ = regions._launch(md, 0, 4, 0, False)
     cap = int(counts.max())
-    scratch = torch.empty(_lib.region_symbol("vitseg_regions_scratch_bytes")(n, H, W), dtype=torch.uint8, device=md.device)
+    scratch = torch.empty(_lib.symbol("vitseg_regions_scratch_bytes")(n, H, W), dtype=torch.uint8, device=md.device)
     recs = torch.empty((n, cap, 8), dtype=torch.int32, device=md.device)
     labels = torch.empty((n, H, W), dtype=torch.int32, device=md.device)
-    f = _lib.region_symbol("vitseg_regions")
+    f = _lib.symbol("vitseg_regions")
     stream = torch.cuda.current_stream().cuda_stream
 
     def call():

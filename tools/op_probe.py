@@ -46,14 +46,14 @@ if a.op == "ce":   # fused upsample + CE with its gradient: the plain kernels, t
     t = t.to(torch.uint8) if a.u8 else t
     G = torch.empty(a.B, a.C, a.S, a.S, device=dev)
     scr = torch.empty(L.vitseg_ce_scratch_bytes(a.B, a.S), dtype=torch.uint8, device=dev)
-    nb = int(_lib.ce_opts_symbol("vitseg_ce_options_scratch_bytes")(a.B, a.S))
+    nb = int(_lib.symbol("vitseg_ce_options_scratch_bytes")(a.B, a.S))
     oscr = torch.empty(nb, dtype=torch.uint8, device=dev)
     w = torch.rand(a.C, device=dev) + 0.5
     loss = torch.empty(1, device=dev)
     o = _lib.CCEOptions(1, 0, 255, w.data_ptr(), 0.1, oscr.data_ptr(), nb)
     args = (z.data_ptr(), t.data_ptr(), int(a.u8), G.data_ptr(), scr.data_ptr(), loss.data_ptr(), a.B, a.C, a.g, a.S)
     plain = lambda: _lib.check(L.vitseg_ce_loss(*args, st))   # (the 255 labels make its loss NaN; the work is the same)
-    run = lambda: _lib.check(_lib.ce_opts_symbol("vitseg_ce_loss_opts")(*args, ctypes.byref(o), 1.0, st))
+    run = lambda: _lib.check(_lib.symbol("vitseg_ce_loss_opts")(*args, ctypes.byref(o), 1.0, st))
     work = float(G.numel() * 4 + t.numel() * t.element_size())   # bytes: the gradient written, the targets read once
     for name, fn in (("plain", plain), ("options", run)):
         fn()

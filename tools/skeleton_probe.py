@@ -60,8 +60,8 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--no-host", action="store_true", help="skip the numpy timing (e.g. under rocprofv3)")
     a = ap.parse_args()
-    fn = _lib.skeleton_symbol("vitseg_skeleton")
-    size = _lib.skeleton_symbol("vitseg_skeleton_scratch_bytes")
+    fn = _lib.symbol("vitseg_skeleton")
+    size = _lib.symbol("vitseg_skeleton_scratch_bytes")
     st = torch.cuda.current_stream().cuda_stream
     lines = [f"vitseg_skeleton; median of {a.iters} hipEvent-timed calls after 1 warm-up call",
              f"{'n x S^2':>12s} {'mask':6s} {'route':9s} {'passes min..max':>16s} {'ms/call':>10s} {'us/image':>10s} {'numpy ms/image':>15s}"]
@@ -92,12 +92,12 @@ def main():
             lines.append(f"{n:4d} x {S:4d}^2 {kind:6s} {ROUTE_NAMES[route]:9s} {f'{p.min()}..{p.max()}':>16s} {ms:10.3f} "
                          f"{ms * 1e3 / n:10.1f} {host:>15s}")
             print(lines[-1], flush=True)
-    fs = _lib.skeleton_symbol("vitseg_skeleton_stats")
+    fs = _lib.symbol("vitseg_skeleton_stats")
     N, S = 32, 512
     lines.append(f"vitseg_skeleton_stats, {N} x {S}^2, classes 0 (background) .. K - 1 (crack bands); automatic route")
     lines.append(f"{'classes':>8s} {'ms/call':>10s} {'us/(image, class)':>18s} {'numpy ms/image':>15s}")
     print("\n".join(lines[-2:]), flush=True)
-    nbytes = _lib.skeleton_symbol("vitseg_skeleton_stats_scratch_bytes")(N, S, S, 0)
+    nbytes = _lib.symbol("vitseg_skeleton_stats_scratch_bytes")(N, S, S, 0)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     for K in (2, 17):
         gt, pred = class_maps(N, S, K, 1000), class_maps(N, S, K, 2000)

@@ -71,7 +71,7 @@ def probe_blend(Cc, K, mode, iters, dev):
     merged = torch.empty((N, Cc, S, S), device=dev)
     mask = torch.empty((N, S, S), dtype=torch.uint8, device=dev)
     descs = (_lib.CTTAView * K)(*[_lib.CTTAView(z.data_ptr(), g, op, 1.0) for z, op in zip(lows, ops)])
-    fn, st = _lib.tta_symbol("vitseg_tta_blend"), torch.cuda.current_stream().cuda_stream
+    fn, st = _lib.symbol("vitseg_tta_blend"), torch.cuda.current_stream().cuda_stream
 
     def blend(want_merged=True):
         _lib.check(fn(descs, K, N, Cc, S, mode, merged.data_ptr() if want_merged else None, mask.data_ptr(), st))
@@ -101,7 +101,7 @@ def probe_forward(Cc, precision, iters, dev):
     low = torch.empty((N, Cc, S // P, S // P), device=dev)
     ws, lp = m.workspace(N, S), m._bf16_arena()
     cfg = C.byref(_lib.CConfig.from_config(m.cfg))
-    fn, st = _lib.window_symbol("vitseg_forward_lowres"), torch.cuda.current_stream().cuda_stream
+    fn, st = _lib.symbol("vitseg_forward_lowres"), torch.cuda.current_stream().cuda_stream
 
     def fwd():
         _lib.check(fn(cfg, S, m.arena.data_ptr(), None if lp is None else lp.data_ptr(), x.data_ptr(), N, m.precision,

@@ -6,6 +6,7 @@ this module's `lib()` raises -- the product path must never silently run elsewhe
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
 from .config import ViTSegConfig
@@ -21,89 +22,14 @@ BUF_TOKENS, BUF_LOWRES = 0, 1
 (T_CLS, T_POS, T_PATCH_W, T_PATCH_B, T_LN1_W, T_LN1_B, T_WQKV, T_BQKV, T_WO, T_BO, T_LN2_W, T_LN2_B,
  T_W1, T_B1, T_W2, T_B2, T_LNF_W, T_LNF_B, T_HEAD0_W, T_HEAD0_B, T_HEAD2_W, T_HEAD2_B, T_COUNT) = range(23)
 
-EXPORTS = [
-    "vitseg_version", "vitseg_last_error", "vitseg_set_option", "vitseg_get_option", "vitseg_param_count", "vitseg_param_offset", "vitseg_cast_params_bf16",
-    "vitseg_query_workspace", "vitseg_workspace_offset", "vitseg_forward", "vitseg_op_layernorm_f32",
-    "vitseg_op_linear_f32", "vitseg_op_attention_f32", "vitseg_op_upsample_argmax", "vitseg_op_upsample_bwd",
-    "vitseg_profile_enable", "vitseg_profile_collect", "vitseg_op_linear_bf16", "vitseg_op_attention_bf16",
-    "vitseg_ce_scratch_bytes", "vitseg_ce_loss",
-    "vitseg_train_workspace", "vitseg_forward_train", "vitseg_backward", "vitseg_adam_step",
-    "vitseg_grad_bucket_count", "vitseg_grad_bucket_range",
-    "vitseg_cast_params_f16", "vitseg_op_linear_f16", "vitseg_op_attention_f16", "vitseg_op_linear_f32x3", "vitseg_op_attention_f32x3", "vitseg_cast_params_split",
-    "vitseg_resize_taps", "vitseg_resize_coeffs", "vitseg_nearest_index", "vitseg_preprocess_u8",
-    "vitseg_resize_nearest_u8", "vitseg_eval_counts", "vitseg_paed_scratch_bytes", "vitseg_paed_multiclass_loss",
-    "vitseg_op_gemm_f32", "vitseg_op_attention_bwd_f32", "vitseg_op_layernorm_bwd_f32", "vitseg_op_linear_h16_ex",
-    "vitseg_op_wgrad_bf16", "vitseg_op_wgrad_bf16_scratch_floats", "vitseg_op_attention_bwd_bf16", "vitseg_attention_dropmask_bytes", "vitseg_attention_bwd_scratch_floats", "vitseg_op_colsum_scratch_floats",
-    "vitseg_paed_binary_scratch_bytes", "vitseg_paed_binary_loss", "vitseg_op_linear_f32_ex", "vitseg_resize_nearest_i64",
-    "vitseg_small_splits", "vitseg_op_linear_f32_small", "vitseg_op_linear_resln_f32_small", "vitseg_op_attention_f32_small", "vitseg_op_attention_bwd_f32_small", "vitseg_op_linear_h16_small", "vitseg_op_attention_h16_small", "vitseg_forward_route", "vitseg_op_layernorm_bwd_f32_small",
-    "vitseg_dbg_linear_f32_small", "vitseg_adamw_step", "vitseg_op_dgrad_f32_small", "vitseg_op_wgrad_f32_small", "vitseg_op_layernorm_bwd_scratch_floats",
-]
-# other input sizes (interpolated position embeddings): bound on first use, so that a library built before them still
-# serves everything else; the new path alone raises a "rebuild" error against it (`at_symbol`)
-AT_EXPORTS = [
-    "vitseg_query_workspace_at", "vitseg_workspace_offset_at", "vitseg_forward_at", "vitseg_train_workspace_at",
-    "vitseg_forward_train_at", "vitseg_backward_at", "vitseg_pos_interp", "vitseg_pos_interp_bwd",
-]
-# connected regions of class masks and their boxes (regions.py): bound on first use, the same way
-REGION_EXPORTS = ["vitseg_regions_scratch_bytes", "vitseg_regions"]
-# exact distance transforms and the signed-distance targets of binary masks (sdf.py): bound on first use, the same way
-SDF_EXPORTS = ["vitseg_sdf_scratch_bytes", "vitseg_sdf"]
-# the K-sliced GEMM paths, one entry each, and the router's slice counts (tests/test_splitk_cpu.py, tests/test_gpu_splitk.py):
-# bound on first use, the same way
-SPLITK_EXPORTS = ["vitseg_op_linear_f32_thin", "vitseg_op_wgrad_f32_scratch_floats", "vitseg_op_wgrad_f32", "vitseg_dbg_gemm_slices"]
-# the fused cross-entropy with ignore_index / class weights / label smoothing (model.ce_loss): bound on first use, the same way
-CE_OPTS_EXPORTS = ["vitseg_ce_options_scratch_bytes", "vitseg_ce_loss_opts", "vitseg_backward_opts"]
-# the embedding, seg-head and training helper kernels, one entry per production launch (csrc/op_helpers.hip,
-# tests/test_gpu_helpers.py): bound on first use, the same way
-HELPER_EXPORTS = [
-    "vitseg_op_patch_embed_f32", "vitseg_op_conv3x3_f32", "vitseg_op_conv3x3_h16", "vitseg_op_head1x1",
-    "vitseg_op_head1x1_bwd_scratch_floats", "vitseg_op_head1x1_bwd", "vitseg_op_colsum", "vitseg_op_embed_bwd",
-    "vitseg_op_im2col3x3", "vitseg_op_im2col3x3_bf16", "vitseg_op_im2col_patch", "vitseg_op_im2col_patch_bf16",
-    "vitseg_op_conv_dgrad_weight", "vitseg_op_transpose_bf16", "vitseg_op_transpose_layers_bf16", "vitseg_op_dropout_rows",
-    "vitseg_op_layernorm_h16",
-]
-# sliding-window inference (model.predict_mask_windowed): the window grid, the tile gather, the forward that stops at the low-res
-# head output and the overlapping-tile blend: bound on first use, the same way
-WINDOW_EXPORTS = ["vitseg_window_count", "vitseg_window_origins", "vitseg_window_gather", "vitseg_forward_lowres",
-                  "vitseg_window_blend"]
-# CE + soft Dice in one fused loss (model.ce_dice_loss): bound on first use, the same way
-DICE_EXPORTS = ["vitseg_dice_options_scratch_bytes", "vitseg_ce_dice_loss", "vitseg_backward_dice"]
-# boundary-distance statistics of class maps: PAED, Hausdorff, HD95, ASSD (metrics.Evaluator.distance_metrics): bound on first
-# use, the same way
-DISTANCE_EXPORTS = ["vitseg_distance_scratch_bytes", "vitseg_distance_stats"]
-# skeletons by Zhang-Suen thinning and the crack statistics on them: clDice, length, width (skeleton.py,
-# metrics.Evaluator.crack_metrics): bound on first use, the same way
-SKELETON_EXPORTS = ["vitseg_skeleton_scratch_bytes", "vitseg_skeleton", "vitseg_skeleton_stats_scratch_bytes",
-                    "vitseg_skeleton_stats"]
 SKELETON_AUTO, SKELETON_RESIDENT, SKELETON_GLOBAL = 0, 1, 2   # the `route` argument
-# training augmentation: the paired affine warp + colour jitter launch and its host-side matrix composer (augment.py): bound on
-# first use, the same way
-AUGMENT_EXPORTS = ["vitseg_augment_matrix", "vitseg_augment"]
 AUGMENT_CONSTANT, AUGMENT_EDGE = 0, 1      # enum vitseg_augment_border
 AUGMENT_U8_NHWC, AUGMENT_F32_NCHW = 0, 1   # enum vitseg_augment_format
-# test-time augmentation (model.predict_mask_tta): the exact affine of a flip / quarter-turn view and the launch that merges the
-# views' low-res maps: bound on first use, the same way
-TTA_EXPORTS = ["vitseg_tta_affine", "vitseg_tta_blend"]
 TTA_LOGITS, TTA_PROBS = 0, 1   # the `mode` argument of vitseg_tta_blend
-# mask clean-up: regions below a minimum area out, enclosed holes filled (clean.py): bound on first use, the same way
-CLEAN_EXPORTS = ["vitseg_clean_scratch_bytes", "vitseg_clean_mask"]
 CLEAN_STATS = ("regions_removed", "pixels_removed", "holes_filled", "pixels_filled", "holes_mixed", "holes_over_area")
-# region-level detection statistics: predicted regions matched against the true ones, PQ (metrics.Evaluator.region_metrics):
-# bound on first use, the same way
-MATCH_EXPORTS = ["vitseg_region_match_scratch_bytes", "vitseg_region_match"]
 MATCH_STATS = ("n_gt", "n_pred", "tp", "gt_found", "pred_confirmed", "sum_q", "sum_i", "sum_u")
-# per-region measurements: moments, perimeter, frame contact, per-region skeleton length and widths (regions.region_props):
-# bound on first use, the same way
-PROPS_EXPORTS = ["vitseg_region_props_scratch_bytes", "vitseg_region_props"]
 PROPS_FIELDS = 20   # include/vitseg.h VITSEG_PROPS_FIELDS
-# confidence of a stated mask: per-pixel scores, per-region score rows, calibration histogram (confidence.py): bound on first
-# use, the same way
-CONFIDENCE_EXPORTS = ["vitseg_confidence"]
 CONF_PROB, CONF_MARGIN = 0, 1   # enum vitseg_conf_kind
-_LATE_EXPORTS = (AT_EXPORTS + REGION_EXPORTS + SDF_EXPORTS + SPLITK_EXPORTS + CE_OPTS_EXPORTS + HELPER_EXPORTS + WINDOW_EXPORTS
-                 + DICE_EXPORTS + DISTANCE_EXPORTS + SKELETON_EXPORTS + AUGMENT_EXPORTS + TTA_EXPORTS + CLEAN_EXPORTS + MATCH_EXPORTS
-                 + PROPS_EXPORTS + CONFIDENCE_EXPORTS)
-EXPORTS += _LATE_EXPORTS   # every symbol include/vitseg.h declares
 # enum vitseg_slices_path
 SLICES_WHOLE_F32, SLICES_WHOLE_H16, SLICES_THIN_F32, SLICES_THIN_H16, SLICES_WGRAD_F32, SLICES_WGRAD_BF16_TT, SLICES_WGRAD_BF16_P8 = range(7)
 VERSION = 110   # include/vitseg.h VITSEG_VERSION this binding was written against
@@ -147,6 +73,205 @@ class CConfig(C.Structure):
                    cfg.layer_norm_eps)
 
 
+# short names, so that a row of SIGNATURES stays on one line
+vp, sz, i32, f32, u32, u64, i64, ll, cstr = (C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint32, C.c_uint64, C.c_int64,
+                                             C.c_longlong, C.c_char_p)
+psz, pint, pi32, pi64, pll, pf32, pdbl = (C.POINTER(t) for t in (sz, i32, C.c_int32, i64, ll, f32, C.c_double))
+pcfg, popt, pdice, pmask, pview = (C.POINTER(t) for t in (CConfig, CCEOptions, CDiceOptions, CAugmentMask, CTTAView))
+
+# Every entry point include/vitseg.h declares, stated once: group -> (required at load, the words after "built before" in
+# `symbol`'s error, [(name, restype, argtypes)]).  `lib()` binds from it, every list of names below is read off it, and
+# tests/test_binding_cpu.py compares it with the header.  A group that is not required is bound where the loaded library has
+# it, so that a library built before a feature still serves everything else; that feature alone raises a "rebuild" error.
+SIGNATURES = {
+    "core": (True, None, [
+        ("vitseg_version", i32, []),
+        ("vitseg_last_error", cstr, []),
+        ("vitseg_set_option", i32, [cstr, ll]),
+        ("vitseg_get_option", i32, [cstr, pll]),
+        ("vitseg_param_count", i32, [pcfg, psz]),
+        ("vitseg_param_offset", i32, [pcfg, i32, i32, psz, psz]),
+        ("vitseg_cast_params_bf16", i32, [vp, vp, sz, vp]),
+        ("vitseg_query_workspace", i32, [pcfg, i32, i32, psz]),
+        ("vitseg_workspace_offset", i32, [pcfg, i32, i32, i32, psz, psz]),
+        ("vitseg_forward", i32, [pcfg, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+        ("vitseg_op_layernorm_f32", i32, [vp, vp, vp, vp, i32, i32, f32, vp]),
+        ("vitseg_op_linear_f32", i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_attention_f32", i32, [vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_upsample_argmax", i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_upsample_bwd", i32, [vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_profile_enable", i32, [i32]),
+        ("vitseg_profile_collect", i32, [i32, pdbl, pi64, pdbl]),
+        ("vitseg_op_linear_bf16", i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_attention_bf16", i32, [vp, vp, i32, i32, i32, vp]),
+        ("vitseg_ce_scratch_bytes", sz, [i32, i32]),
+        ("vitseg_ce_loss", i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_train_workspace", i32, [pcfg, i32, i32, psz]),
+        ("vitseg_forward_train", i32, [pcfg, vp, vp, vp, i32, i32, f32, u64, vp, vp, sz, vp]),
+        ("vitseg_backward", i32, [pcfg, vp, vp, vp, i32, i32, f32, u64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp]),
+        ("vitseg_adam_step", i32, [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, f32, vp]),
+        ("vitseg_grad_bucket_count", i32, [pcfg]),
+        ("vitseg_grad_bucket_range", i32, [pcfg, i32, psz, psz]),
+        ("vitseg_cast_params_f16", i32, [vp, vp, sz, vp]),
+        ("vitseg_op_linear_f16", i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_attention_f16", i32, [vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_linear_f32x3", i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_attention_f32x3", i32, [vp, vp, i32, i32, i32, vp]),
+        ("vitseg_cast_params_split", i32, [vp, vp, sz, vp]),
+        ("vitseg_resize_taps", i32, [i32, i32]),
+        ("vitseg_resize_coeffs", i32, [i32, i32, vp, vp]),
+        ("vitseg_nearest_index", i32, [i32, i32, i32, vp]),
+        ("vitseg_preprocess_u8", i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
+        ("vitseg_resize_nearest_u8", i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp]),
+        ("vitseg_eval_counts", i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+        ("vitseg_paed_scratch_bytes", sz, [i32, i32, i32, i32]),
+        ("vitseg_paed_multiclass_loss", i32, [vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
+        ("vitseg_op_gemm_f32", i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        ("vitseg_op_attention_bwd_f32", i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_layernorm_bwd_f32", i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
+        ("vitseg_op_linear_h16_ex", i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, f32, u32, u32, vp, vp, vp]),
+        ("vitseg_op_wgrad_bf16", i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_wgrad_bf16_scratch_floats", sz, [i32, i32, i32]),
+        ("vitseg_op_attention_bwd_bf16", i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp, vp, vp]),
+        ("vitseg_attention_dropmask_bytes", sz, [i32, i32, i32]),
+        ("vitseg_attention_bwd_scratch_floats", sz, [i32, i32, i32]),
+        ("vitseg_op_colsum_scratch_floats", sz, [i32, i32]),
+        ("vitseg_paed_binary_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_paed_binary_loss", i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+        ("vitseg_op_linear_f32_ex", i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, u32, u32, vp]),
+        ("vitseg_resize_nearest_i64", i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
+        ("vitseg_small_splits", i32, [i32, i32]),
+        ("vitseg_op_linear_f32_small", i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_linear_resln_f32_small", i32, [vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, f32, vp]),
+        ("vitseg_op_attention_f32_small", i32, [vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_attention_bwd_f32_small", i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp]),
+        ("vitseg_op_linear_h16_small", i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+        ("vitseg_op_attention_h16_small", i32, [vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_forward_route", i32, [pcfg, i32, i32]),
+        ("vitseg_op_layernorm_bwd_f32_small", i32, [vp, vp, vp, sz, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, f32, u32, u32, vp]),
+        ("vitseg_dbg_linear_f32_small", i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
+        ("vitseg_adamw_step", i32, [vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, i32, f32, vp]),
+        ("vitseg_op_dgrad_f32_small", i32, [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
+        ("vitseg_op_wgrad_f32_small", i32, [vp, vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_layernorm_bwd_scratch_floats", sz, [i32, i32]),
+    ]),
+    # other input sizes (interpolated position embeddings)
+    "at": (False, "interpolated position embeddings", [
+        ("vitseg_query_workspace_at", i32, [pcfg, i32, i32, i32, psz]),
+        ("vitseg_workspace_offset_at", i32, [pcfg, i32, i32, i32, i32, psz, psz]),
+        ("vitseg_forward_at", i32, [pcfg, i32, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+        ("vitseg_train_workspace_at", i32, [pcfg, i32, i32, i32, psz]),
+        ("vitseg_forward_train_at", i32, [pcfg, i32, vp, vp, vp, i32, i32, f32, u64, vp, vp, sz, vp]),
+        ("vitseg_backward_at", i32, [pcfg, i32, vp, vp, vp, i32, i32, f32, u64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp]),
+        ("vitseg_pos_interp", i32, [vp, vp, i32, i32, i32, vp]),
+        ("vitseg_pos_interp_bwd", i32, [vp, vp, vp, i32, i32, i32, vp]),
+    ]),
+    # connected regions of class masks and their boxes (regions.py)
+    "region": (False, "connected regions", [
+        ("vitseg_regions_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_regions", i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, sz, vp]),
+    ]),
+    # exact distance transforms and the signed-distance targets of binary masks (sdf.py)
+    "sdf": (False, "distance transforms", [
+        ("vitseg_sdf_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_sdf", i32, [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    ]),
+    # the K-sliced GEMM paths, one entry each, and the router's slice counts (tests/test_splitk_cpu.py, tests/test_gpu_splitk.py)
+    "splitk": (False, "the split-K entry points", [
+        ("vitseg_op_linear_f32_thin", i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, f32, u32, u32, vp]),
+        ("vitseg_op_wgrad_f32_scratch_floats", sz, [i32, i32, i32]),
+        ("vitseg_op_wgrad_f32", i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+        ("vitseg_dbg_gemm_slices", i32, [i32, i32, i32, i32]),
+    ]),
+    # the fused cross-entropy with ignore_index / class weights / label smoothing (model.ce_loss)
+    "ce_opts": (False, "the cross-entropy options", [
+        ("vitseg_ce_options_scratch_bytes", sz, [i32, i32]),
+        ("vitseg_ce_loss_opts", i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, popt, f32, vp]),
+        ("vitseg_backward_opts", i32, [pcfg, i32, vp, vp, vp, i32, i32, f32, u64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp, popt]),
+    ]),
+    # the embedding, seg-head and training helper kernels, one entry per production launch (csrc/op_helpers.hip,
+    # tests/test_gpu_helpers.py)
+    "helper": (False, "the helper-kernel entry points", [
+        ("vitseg_op_patch_embed_f32", i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        ("vitseg_op_conv3x3_f32", i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        ("vitseg_op_conv3x3_h16", i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+        ("vitseg_op_head1x1", i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_head1x1_bwd_scratch_floats", sz, [i32, i32, i32]),
+        ("vitseg_op_head1x1_bwd", i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_colsum", i32, [vp, i32, vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_embed_bwd", i32, [vp, vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_im2col3x3", i32, [vp, i32, vp, i32, i32, i32, vp]),
+        ("vitseg_op_im2col3x3_bf16", i32, [vp, vp, i32, i32, i32, vp]),
+        ("vitseg_op_im2col_patch", i32, [vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_im2col_patch_bf16", i32, [vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_conv_dgrad_weight", i32, [vp, vp, i32, vp]),
+        ("vitseg_op_transpose_bf16", i32, [vp, vp, i32, i32, i32, i32, vp]),
+        ("vitseg_op_transpose_layers_bf16", i32, [vp, vp, psz, pint, pint, sz, i32, vp]),
+        ("vitseg_op_dropout_rows", i32, [vp, vp, i32, i32, i32, f32, u32, u32, vp]),
+        ("vitseg_op_layernorm_h16", i32, [vp, vp, vp, vp, i32, i32, f32, i32, vp]),
+    ]),
+    # sliding-window inference (model.predict_mask_windowed): the window grid, the tile gather, the forward that stops at the
+    # low-res head output and the overlapping-tile blend
+    "window": (False, "sliding-window inference", [
+        ("vitseg_window_count", i32, [i32, i32, i32]),
+        ("vitseg_window_origins", i32, [i32, i32, i32, vp]),
+        ("vitseg_window_gather", i32, [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp]),
+        ("vitseg_forward_lowres", i32, [pcfg, i32, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+        ("vitseg_window_blend", i32, [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    ]),
+    # CE + soft Dice in one fused loss (model.ce_dice_loss)
+    "dice": (False, "the CE + Dice loss", [
+        ("vitseg_dice_options_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_ce_dice_loss", i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, popt, pdice, f32, vp]),
+        ("vitseg_backward_dice", i32, [pcfg, i32, vp, vp, vp, i32, i32, f32, u64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp, popt,
+                                       pdice, vp]),
+    ]),
+    # boundary-distance statistics of class maps: PAED, Hausdorff, HD95, ASSD (metrics.Evaluator.distance_metrics)
+    "distance": (False, "the boundary-distance metrics", [
+        ("vitseg_distance_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_distance_stats", i32, [vp, vp, i32, i32, i32, pi32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    ]),
+    # skeletons by Zhang-Suen thinning and the crack statistics on them: clDice, length, width (skeleton.py,
+    # metrics.Evaluator.crack_metrics)
+    "skeleton": (False, "the skeletons", [
+        ("vitseg_skeleton_scratch_bytes", sz, [i32, i32, i32, i32]),
+        ("vitseg_skeleton", i32, [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+        ("vitseg_skeleton_stats_scratch_bytes", sz, [i32, i32, i32, i32]),
+        ("vitseg_skeleton_stats", i32, [vp, vp, i32, i32, i32, pi32, i32, i32, vp, vp, vp, sz, vp]),
+    ]),
+    # training augmentation: the paired affine warp + colour jitter launch and its host-side matrix composer (augment.py)
+    "augment": (False, "the training augmentation", [
+        ("vitseg_augment_matrix", i32, [vp, i32, i32, i32, i32, vp]),   # (double[6] in, int64[6] out)
+        ("vitseg_augment", i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, pmask, i32, i32, pf32, i64, vp]),
+    ]),
+    # test-time augmentation (model.predict_mask_tta): the exact affine of a flip / quarter-turn view and the launch that
+    # merges the views' low-res maps
+    "tta": (False, "test-time augmentation", [
+        ("vitseg_tta_affine", i32, [i32, vp]),   # (double[6] out)
+        ("vitseg_tta_blend", i32, [pview, i32, i32, i32, i32, i32, vp, vp, vp]),
+    ]),
+    # mask clean-up: regions below a minimum area out, enclosed holes filled (clean.py)
+    "clean": (False, "the mask clean-up", [
+        ("vitseg_clean_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_clean_mask", i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    ]),
+    # region-level detection statistics: predicted regions matched against the true ones, PQ (metrics.Evaluator.region_metrics)
+    "match": (False, "the region matching", [
+        ("vitseg_region_match_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_region_match", i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    ]),
+    # per-region measurements: moments, perimeter, frame contact, per-region skeleton length and widths (regions.region_props)
+    "props": (False, "the per-region measurements", [
+        ("vitseg_region_props_scratch_bytes", sz, [i32, i32, i32, i32, i32]),
+        ("vitseg_region_props", i32, [vp, i32, i32, i32, i32, i32, pi32, i32, i32, vp, vp, i32, vp, vp, sz, vp]),
+    ]),
+    # confidence of a stated mask: per-pixel scores, per-region score rows, calibration histogram (confidence.py)
+    "confidence": (False, "the confidence scores", [
+        ("vitseg_confidence", i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp]),
+    ]),
+}
+_WHAT = {name: what for _, what, rows in SIGNATURES.values() for name, _, _ in rows}
+
 _lib = None
 
 
@@ -158,159 +283,12 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m visiontransformer_amd.build` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback for this path.")
         l = C.CDLL(LIB_PATH)
-        vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int
-        pcfg, psz = C.POINTER(CConfig), C.POINTER(C.c_size_t)
-        l.vitseg_version.restype = i32
-        l.vitseg_last_error.restype = C.c_char_p
-        l.vitseg_set_option.argtypes = [C.c_char_p, C.c_longlong]
-        l.vitseg_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_longlong)]
-        l.vitseg_param_count.argtypes = [pcfg, psz]
-        l.vitseg_param_offset.argtypes = [pcfg, i32, i32, psz, psz]
-        l.vitseg_cast_params_bf16.argtypes = [vp, vp, sz, vp]
-        l.vitseg_cast_params_f16.argtypes = [vp, vp, sz, vp]
-        l.vitseg_cast_params_split.argtypes = [vp, vp, sz, vp]
-        l.vitseg_query_workspace.argtypes = [pcfg, i32, i32, psz]
-        l.vitseg_workspace_offset.argtypes = [pcfg, i32, i32, i32, psz, psz]
-        l.vitseg_forward.argtypes = [pcfg, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]
-        l.vitseg_op_layernorm_f32.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp]
-        l.vitseg_op_linear_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        l.vitseg_op_linear_f32_ex.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_uint32, C.c_uint32, vp]
-        l.vitseg_op_attention_f32.argtypes = [vp, vp, i32, i32, i32, vp]
-        l.vitseg_op_attention_f32_small.argtypes = [vp, vp, i32, i32, i32, vp]
-        l.vitseg_small_splits.argtypes = [i32, i32]
-        l.vitseg_op_layernorm_bwd_scratch_floats.argtypes = [i32, i32]
-        l.vitseg_op_layernorm_bwd_scratch_floats.restype = sz
-        l.vitseg_op_wgrad_f32_small.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-        l.vitseg_op_dgrad_f32_small.argtypes = [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]
-        l.vitseg_dbg_linear_f32_small.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]
-        l.vitseg_op_linear_f32_small.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        l.vitseg_op_linear_resln_f32_small.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, C.c_float, vp]
-        l.vitseg_op_linear_bf16.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        l.vitseg_op_attention_bf16.argtypes = [vp, vp, i32, i32, i32, vp]
-        l.vitseg_op_linear_f16.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        l.vitseg_op_linear_f32x3.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        l.vitseg_op_wgrad_bf16_scratch_floats.argtypes = [i32, i32, i32]
-        l.vitseg_op_wgrad_bf16_scratch_floats.restype = sz
-        l.vitseg_op_wgrad_bf16.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
-        l.vitseg_op_linear_h16_ex.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, C.c_float,
-                                              C.c_uint32, C.c_uint32, vp, vp, vp]
-        l.vitseg_op_colsum_scratch_floats.argtypes = [i32, i32]
-        l.vitseg_op_colsum_scratch_floats.restype = sz
-        l.vitseg_op_attention_f16.argtypes = [vp, vp, i32, i32, i32, vp]
-        l.vitseg_op_attention_f32x3.argtypes = [vp, vp, i32, i32, i32, vp]
-        l.vitseg_op_upsample_argmax.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-        l.vitseg_op_upsample_bwd.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-        l.vitseg_ce_scratch_bytes.argtypes = [i32, i32]
-        l.vitseg_ce_scratch_bytes.restype = sz
-        l.vitseg_ce_loss.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]
-        f32 = C.c_float
-        l.vitseg_train_workspace.argtypes = [pcfg, i32, i32, psz]
-        l.vitseg_forward_train.argtypes = [pcfg, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, vp, sz, vp]
-        l.vitseg_backward.argtypes = [pcfg, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp]
-        l.vitseg_grad_bucket_count.argtypes = [pcfg]
-        l.vitseg_resize_taps.argtypes = [i32, i32]
-        l.vitseg_paed_scratch_bytes.argtypes = [i32, i32, i32, i32]
-        l.vitseg_paed_scratch_bytes.restype = sz
-        l.vitseg_paed_multiclass_loss.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]
-        l.vitseg_paed_binary_scratch_bytes.argtypes = [i32, i32, i32]
-        l.vitseg_paed_binary_scratch_bytes.restype = sz
-        l.vitseg_paed_binary_loss.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-        l.vitseg_resize_coeffs.argtypes = [i32, i32, vp, vp]
-        l.vitseg_nearest_index.argtypes = [i32, i32, i32, vp]
-        l.vitseg_preprocess_u8.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]
-        l.vitseg_resize_nearest_u8.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp]
-        l.vitseg_resize_nearest_i64.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]
-        l.vitseg_eval_counts.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-        l.vitseg_grad_bucket_range.argtypes = [pcfg, i32, psz, psz]
-        l.vitseg_adam_step.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, i32, f32, vp]
-        l.vitseg_adamw_step.argtypes = [vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, i32, f32, vp]
-        l.vitseg_op_gemm_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-        l.vitseg_op_attention_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-        l.vitseg_op_layernorm_bwd_f32_small.argtypes = [vp, vp, vp, sz, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, f32, C.c_uint32, C.c_uint32, vp]
-        l.vitseg_forward_route.argtypes = [pcfg, i32, i32]
-        l.vitseg_op_attention_h16_small.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-        l.vitseg_op_linear_h16_small.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]
-        l.vitseg_op_attention_bwd_f32_small.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, C.c_uint32, C.c_uint32, vp]
-        l.vitseg_attention_bwd_scratch_floats.argtypes = [i32, i32, i32]
-        l.vitseg_attention_bwd_scratch_floats.restype = sz
-        l.vitseg_op_attention_bwd_bf16.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp]
-        l.vitseg_attention_dropmask_bytes.argtypes = [i32, i32, i32]
-        l.vitseg_attention_dropmask_bytes.restype = C.c_size_t
-        l.vitseg_op_layernorm_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]
-        l.vitseg_profile_enable.argtypes = [i32]
-        l.vitseg_profile_collect.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
-        for name in EXPORTS:
-            if name not in _LATE_EXPORTS:
-                getattr(l, name)  # raises AttributeError if the build is stale
-        for name, args in _at_argtypes(vp, sz, i32, pcfg, psz).items():
-            fn = getattr(l, name, None)
-            if fn is not None:
-                fn.argtypes = args
-        if getattr(l, "vitseg_regions", None) is not None:
-            l.vitseg_regions_scratch_bytes.argtypes = [i32, i32, i32]
-            l.vitseg_regions_scratch_bytes.restype = sz
-            l.vitseg_regions.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, sz, vp]
-        if getattr(l, "vitseg_sdf", None) is not None:
-            l.vitseg_sdf_scratch_bytes.argtypes = [i32, i32, i32]
-            l.vitseg_sdf_scratch_bytes.restype = sz
-            l.vitseg_sdf.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
-        if getattr(l, "vitseg_distance_stats", None) is not None:
-            l.vitseg_distance_scratch_bytes.argtypes = [i32, i32, i32]
-            l.vitseg_distance_scratch_bytes.restype = sz
-            l.vitseg_distance_stats.argtypes = [vp, vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, i32, vp, vp, vp,
-                                                sz, vp]
-        if getattr(l, "vitseg_skeleton_stats", None) is not None:
-            l.vitseg_skeleton_scratch_bytes.argtypes = [i32, i32, i32, i32]
-            l.vitseg_skeleton_scratch_bytes.restype = sz
-            l.vitseg_skeleton.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
-            l.vitseg_skeleton_stats_scratch_bytes.argtypes = [i32, i32, i32, i32]
-            l.vitseg_skeleton_stats_scratch_bytes.restype = sz
-            l.vitseg_skeleton_stats.argtypes = [vp, vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp, vp, sz, vp]
-        if getattr(l, "vitseg_dbg_gemm_slices", None) is not None:
-            l.vitseg_op_linear_f32_thin.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, C.c_float,
-                                                    C.c_uint32, C.c_uint32, vp]
-            l.vitseg_op_wgrad_f32_scratch_floats.argtypes = [i32, i32, i32]
-            l.vitseg_op_wgrad_f32_scratch_floats.restype = sz
-            l.vitseg_op_wgrad_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
-            l.vitseg_dbg_gemm_slices.argtypes = [i32, i32, i32, i32]
-        if getattr(l, "vitseg_backward_opts", None) is not None:
-            for name, args in _ce_opts_argtypes(vp, sz, i32, pcfg).items():
-                getattr(l, name).argtypes = args
-            l.vitseg_ce_options_scratch_bytes.restype = sz
-        if getattr(l, "vitseg_op_patch_embed_f32", None) is not None:
-            for name, args in _helper_argtypes(vp, sz, i32).items():
-                getattr(l, name).argtypes = args
-            l.vitseg_op_head1x1_bwd_scratch_floats.restype = sz
-        if getattr(l, "vitseg_window_blend", None) is not None:
-            for name, args in _window_argtypes(vp, sz, i32, pcfg).items():
-                getattr(l, name).argtypes = args
-        if getattr(l, "vitseg_backward_dice", None) is not None:
-            for name, args in _dice_argtypes(vp, sz, i32, pcfg).items():
-                getattr(l, name).argtypes = args
-            l.vitseg_dice_options_scratch_bytes.restype = sz
-        if getattr(l, "vitseg_augment", None) is not None:
-            l.vitseg_augment_matrix.argtypes = [vp, i32, i32, i32, i32, vp]   # (double[6] in, int64[6] out)
-            l.vitseg_augment.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(CAugmentMask), i32, i32,
-                                         C.POINTER(C.c_float), C.c_int64, vp]
-        if getattr(l, "vitseg_tta_blend", None) is not None:
-            l.vitseg_tta_affine.argtypes = [i32, vp]   # (double[6] out)
-            l.vitseg_tta_blend.argtypes = [C.POINTER(CTTAView), i32, i32, i32, i32, i32, vp, vp, vp]
-        if getattr(l, "vitseg_clean_mask", None) is not None:
-            l.vitseg_clean_scratch_bytes.argtypes = [i32, i32, i32]
-            l.vitseg_clean_scratch_bytes.restype = sz
-            l.vitseg_clean_mask.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]
-        if getattr(l, "vitseg_region_match", None) is not None:
-            l.vitseg_region_match_scratch_bytes.argtypes = [i32, i32, i32]
-            l.vitseg_region_match_scratch_bytes.restype = sz
-            l.vitseg_region_match.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,
-                                              sz, vp]
-        if getattr(l, "vitseg_region_props", None) is not None:
-            l.vitseg_region_props_scratch_bytes.argtypes = [i32, i32, i32, i32, i32]
-            l.vitseg_region_props_scratch_bytes.restype = sz
-            l.vitseg_region_props.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp, i32, vp, vp,
-                                              sz, vp]
-        if getattr(l, "vitseg_confidence", None) is not None:
-            l.vitseg_confidence.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp]
+        for required, _, rows in SIGNATURES.values():
+            for name, restype, argtypes in rows:
+                fn = getattr(l, name) if required else getattr(l, name, None)   # AttributeError: the build is stale
+                if fn is not None:
+                    fn.restype = restype
+                    fn.argtypes = argtypes
         if l.vitseg_version() != VERSION:   # argument lists changed between versions: a stale .so would misread them
             raise RuntimeError(f"{LIB_PATH} is version {l.vitseg_version()}, this binding expects {VERSION}: rebuild it "
                                "(python -m visiontransformer_amd.build)")
@@ -318,188 +296,40 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def _at_argtypes(vp, sz, i32, pcfg, psz) -> dict:
-    f32 = C.c_float
-    return {
-        "vitseg_query_workspace_at": [pcfg, i32, i32, i32, psz],
-        "vitseg_workspace_offset_at": [pcfg, i32, i32, i32, i32, psz, psz],
-        "vitseg_forward_at": [pcfg, i32, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp],
-        "vitseg_train_workspace_at": [pcfg, i32, i32, i32, psz],
-        "vitseg_forward_train_at": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, vp, sz, vp],
-        "vitseg_backward_at": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp],
-        "vitseg_pos_interp": [vp, vp, i32, i32, i32, vp],
-        "vitseg_pos_interp_bwd": [vp, vp, vp, i32, i32, i32, vp],
-    }
-
-
-def _ce_opts_argtypes(vp, sz, i32, pcfg) -> dict:
-    f32, popt = C.c_float, C.POINTER(CCEOptions)
-    return {
-        "vitseg_ce_options_scratch_bytes": [i32, i32],
-        "vitseg_ce_loss_opts": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, popt, f32, vp],
-        "vitseg_backward_opts": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp,
-                                 popt],
-    }
-
-
-def _dice_argtypes(vp, sz, i32, pcfg) -> dict:
-    f32, popt, pdice = C.c_float, C.POINTER(CCEOptions), C.POINTER(CDiceOptions)
-    return {
-        "vitseg_dice_options_scratch_bytes": [i32, i32, i32],
-        "vitseg_ce_dice_loss": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, popt, pdice, f32, vp],
-        "vitseg_backward_dice": [pcfg, i32, vp, vp, vp, i32, i32, f32, C.c_uint64, vp, i32, vp, vp, vp, f32, vp, vp, sz, vp,
-                                 popt, pdice, vp],
-    }
-
-
-def _window_argtypes(vp, sz, i32, pcfg) -> dict:
-    return {
-        "vitseg_window_count": [i32, i32, i32],
-        "vitseg_window_origins": [i32, i32, i32, vp],
-        "vitseg_window_gather": [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp],
-        "vitseg_forward_lowres": [pcfg, i32, vp, vp, vp, i32, i32, vp, vp, sz, vp],
-        "vitseg_window_blend": [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
-    }
-
-
-def _helper_argtypes(vp, sz, i32) -> dict:
-    f32, u32 = C.c_float, C.c_uint32
-    return {
-        "vitseg_op_patch_embed_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-        "vitseg_op_conv3x3_f32": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-        "vitseg_op_conv3x3_h16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-        "vitseg_op_head1x1": [vp, vp, vp, vp, i32, i32, i32, vp],
-        "vitseg_op_head1x1_bwd_scratch_floats": [i32, i32, i32],
-        "vitseg_op_head1x1_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-        "vitseg_op_colsum": [vp, i32, vp, vp, i32, i32, i32, vp],
-        "vitseg_op_embed_bwd": [vp, vp, vp, i32, i32, i32, vp],
-        "vitseg_op_im2col3x3": [vp, i32, vp, i32, i32, i32, vp],
-        "vitseg_op_im2col3x3_bf16": [vp, vp, i32, i32, i32, vp],
-        "vitseg_op_im2col_patch": [vp, vp, i32, i32, i32, i32, vp],
-        "vitseg_op_im2col_patch_bf16": [vp, vp, i32, i32, i32, i32, vp],
-        "vitseg_op_conv_dgrad_weight": [vp, vp, i32, vp],
-        "vitseg_op_transpose_bf16": [vp, vp, i32, i32, i32, i32, vp],
-        "vitseg_op_transpose_layers_bf16": [vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int), sz, i32, vp],
-        "vitseg_op_dropout_rows": [vp, vp, i32, i32, i32, f32, u32, u32, vp],
-        "vitseg_op_layernorm_h16": [vp, vp, vp, vp, i32, i32, f32, i32, vp],
-    }
-
-
-def helper_symbol(name: str):
-    """One of HELPER_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
+def symbol(name: str, what: str = None):
+    """The bound entry point `name`, or a RuntimeError naming the rebuild when the loaded library predates it.  `what`: the
+    feature to name for a `name` that SIGNATURES does not know."""
     fn = getattr(lib(), name, None)
     if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the helper-kernel entry points): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
+        what = _WHAT.get(name) or what or "this entry point"
+        raise RuntimeError(f"{LIB_PATH} has no {name} (built before {what}): rebuild it (python -m visiontransformer_amd.build)")
     return fn
 
 
-def ce_opts_symbol(name: str):
-    """One of CE_OPTS_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the cross-entropy options): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
+def _public(group: str):
+    """What callers outside the package know a group by: the list of its names and `symbol` carrying the group's words."""
+    _, what, rows = SIGNATURES[group]
+    return [name for name, _, _ in rows], functools.partial(symbol, what=what)
 
 
-def dice_symbol(name: str):
-    """One of DICE_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the CE + Dice loss): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def at_symbol(name: str):
-    """One of AT_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before interpolated position embeddings): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def region_symbol(name: str):
-    """One of REGION_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before connected regions): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def clean_symbol(name: str):
-    """One of CLEAN_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the mask clean-up): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def sdf_symbol(name: str):
-    """One of SDF_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before distance transforms): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def match_symbol(name: str):
-    """One of MATCH_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the region matching): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def props_symbol(name: str):
-    """One of PROPS_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the per-region measurements): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def confidence_symbol(name: str):
-    """One of CONFIDENCE_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the confidence scores): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def distance_symbol(name: str):
-    """One of DISTANCE_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the boundary-distance metrics): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def skeleton_symbol(name: str):
-    """One of SKELETON_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the skeletons): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
-
-
-def augment_symbol(name: str):
-    """One of AUGMENT_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the training augmentation): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
+AT_EXPORTS, at_symbol = _public("at")
+REGION_EXPORTS, region_symbol = _public("region")
+SDF_EXPORTS, sdf_symbol = _public("sdf")
+SPLITK_EXPORTS, splitk_symbol = _public("splitk")
+CE_OPTS_EXPORTS, ce_opts_symbol = _public("ce_opts")
+HELPER_EXPORTS, helper_symbol = _public("helper")
+WINDOW_EXPORTS, window_symbol = _public("window")
+DICE_EXPORTS, dice_symbol = _public("dice")
+DISTANCE_EXPORTS, distance_symbol = _public("distance")
+SKELETON_EXPORTS, skeleton_symbol = _public("skeleton")
+AUGMENT_EXPORTS, augment_symbol = _public("augment")
+TTA_EXPORTS, tta_symbol = _public("tta")
+CLEAN_EXPORTS, clean_symbol = _public("clean")
+MATCH_EXPORTS, match_symbol = _public("match")
+PROPS_EXPORTS, props_symbol = _public("props")
+CONFIDENCE_EXPORTS, confidence_symbol = _public("confidence")
+_LATE_EXPORTS = [name for required, _, rows in SIGNATURES.values() if not required for name, _, _ in rows]
+EXPORTS = list(_WHAT)   # every symbol include/vitseg.h declares
 
 
 def augment_matrix(affine, src_hw, dst_hw) -> list:
@@ -507,60 +337,33 @@ def augment_matrix(affine, src_hw, dst_hw) -> list:
     (vitseg_augment_matrix); ValueError for an extent outside 1..16384 or an entry past the kernel's clamp bounds."""
     a = (C.c_double * 6)(*[float(v) for v in affine])
     out = (C.c_int64 * 6)()
-    check(augment_symbol("vitseg_augment_matrix")(a, int(src_hw[0]), int(src_hw[1]), int(dst_hw[0]), int(dst_hw[1]), out))
+    check(symbol("vitseg_augment_matrix")(a, int(src_hw[0]), int(src_hw[1]), int(dst_hw[0]), int(dst_hw[1]), out))
     return list(out)
-
-
-def tta_symbol(name: str):
-    """One of TTA_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before test-time augmentation): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
 
 
 def tta_affine(op: int) -> list:
     """The normalised 2x3 affine (six doubles) of view(., op) for `augment_matrix` (vitseg_tta_affine); ValueError for an
     op outside 0..7."""
     out = (C.c_double * 6)()
-    if tta_symbol("vitseg_tta_affine")(int(op), out):
+    if symbol("vitseg_tta_affine")(int(op), out):
         raise ValueError(lib().vitseg_last_error().decode(errors="replace"))
     return list(out)
-
-
-def window_symbol(name: str):
-    """One of WINDOW_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before sliding-window inference): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
 
 
 def window_origins(extent: int, S: int, stride: int) -> list:
     """Origins of the windows along one axis (vitseg_window_origins): i * stride, the last one shifted back to end at the edge.
     ValueError for an extent shorter than the window, a stride outside 1..S or an extent above 16384."""
-    n = int(window_symbol("vitseg_window_count")(int(extent), int(S), int(stride)))
+    n = int(symbol("vitseg_window_count")(int(extent), int(S), int(stride)))
     if n < 0:
         check(n)
     out = (C.c_int32 * n)()
-    check(window_symbol("vitseg_window_origins")(int(extent), int(S), int(stride), out))
+    check(symbol("vitseg_window_origins")(int(extent), int(S), int(stride), out))
     return list(out)
-
-
-def splitk_symbol(name: str):
-    """One of SPLITK_EXPORTS, or a RuntimeError naming the rebuild when the loaded library predates it."""
-    fn = getattr(lib(), name, None)
-    if fn is None:
-        raise RuntimeError(f"{LIB_PATH} has no {name} (built before the split-K entry points): rebuild it "
-                           "(python -m visiontransformer_amd.build)")
-    return fn
 
 
 def gemm_slices(path: int, M: int, N: int, K: int) -> int:
     """K slices of a GEMM with a dense [M, N] output on one of the router's sliced paths (SLICES_*); 0: the path does not apply."""
-    return int(splitk_symbol("vitseg_dbg_gemm_slices")(path, M, N, K))
+    return int(symbol("vitseg_dbg_gemm_slices")(path, M, N, K))
 
 
 def _native(cfg: ViTSegConfig, image_size) -> bool:
@@ -623,8 +426,8 @@ def query_workspace(cfg: ViTSegConfig, batch: int, precision: int, image_size=No
     if _native(cfg, image_size):
         check(lib().vitseg_query_workspace(C.byref(CConfig.from_config(cfg)), batch, precision, C.byref(n)))
     else:
-        check(at_symbol("vitseg_query_workspace_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
-                                                     C.byref(n)))
+        check(symbol("vitseg_query_workspace_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
+                                                  C.byref(n)))
     return n.value
 
 
@@ -646,8 +449,8 @@ def workspace_offset(cfg: ViTSegConfig, batch: int, precision: int, buffer: int,
         check(lib().vitseg_workspace_offset(C.byref(CConfig.from_config(cfg)), batch, precision, buffer,
                                             C.byref(off), C.byref(n)))
     else:
-        check(at_symbol("vitseg_workspace_offset_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
-                                                      buffer, C.byref(off), C.byref(n)))
+        check(symbol("vitseg_workspace_offset_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
+                                                   buffer, C.byref(off), C.byref(n)))
     return off.value, n.value
 
 
@@ -656,8 +459,8 @@ def train_workspace(cfg: ViTSegConfig, batch: int, precision: int, image_size=No
     if _native(cfg, image_size):
         check(lib().vitseg_train_workspace(C.byref(CConfig.from_config(cfg)), batch, precision, C.byref(n)))
     else:
-        check(at_symbol("vitseg_train_workspace_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
-                                                     C.byref(n)))
+        check(symbol("vitseg_train_workspace_at")(C.byref(CConfig.from_config(cfg)), int(image_size), batch, precision,
+                                                  C.byref(n)))
     return n.value
 
 

@@ -137,7 +137,7 @@ class Augmenter:
         (sh, sw), (dh, dw) = _pair(src_hw, "src_hw"), _pair(dst_hw, "dst_hw")
         aff = self.affine(params)
         out = np.empty((aff.shape[0], 6), np.int64)
-        fn, pa, po = _lib.augment_symbol("vitseg_augment_matrix"), aff.ctypes.data, out.ctypes.data
+        fn, pa, po = _lib.symbol("vitseg_augment_matrix"), aff.ctypes.data, out.ctypes.data
         for i in range(aff.shape[0]):   # one call per sample: 48 bytes in, 48 bytes out
             rc = fn(pa + 48 * i, sh, sw, dh, dw, po + 48 * i)
             if rc:
@@ -178,7 +178,7 @@ class Augmenter:
         scale = 255.0 if u8 else 1.0   # the kernel takes the fill in the source's units
         fill = (C.c_float * 3)(*[v * scale for v in self.fill])
         with torch.cuda.device(dev):
-            _lib.check(_lib.augment_symbol("vitseg_augment")(
+            _lib.check(_lib.symbol("vitseg_augment")(
                 images.data_ptr(), _lib.AUGMENT_U8_NHWC if u8 else _lib.AUGMENT_F32_NCHW, n, H, W, S, S, tab.data_ptr(),
                 None if ctab is None else ctab.data_ptr(), x.data_ptr(), descs, len(planes), _BORDERS[self.border], fill,
                 self.fill_label if self.fill_label is not None else 0, torch.cuda.current_stream(dev).cuda_stream))

@@ -80,8 +80,8 @@ def clean_mask(mask, *, min_area: int = 0, fill_holes: bool = False, max_hole_ar
     dev = m.device
     out = torch.empty_like(m)
     stats = torch.empty((n, 8), dtype=torch.int32, device=dev) if return_stats else None
-    scratch = torch.empty(_lib.clean_symbol("vitseg_clean_scratch_bytes")(n, H, W), dtype=torch.uint8, device=dev)
-    _lib.check(_lib.clean_symbol("vitseg_clean_mask")(
+    scratch = torch.empty(_lib.symbol("vitseg_clean_scratch_bytes")(n, H, W), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.symbol("vitseg_clean_mask")(
         m.data_ptr(), out.data_ptr(), n, H, W, connectivity, background, min_area, int(fill_holes), max_hole_area,
         stats.data_ptr() if stats is not None else None, scratch.data_ptr(), scratch.numel(),
         torch.cuda.current_stream(dev).cuda_stream))

@@ -76,7 +76,7 @@ def _launch(lowres, mask, kind, conf=None, conf_q=None, labels=None, scores=None
     n, C, g, _ = (int(d) for d in lowres.shape)
     S = int(mask.shape[-1])
     with torch.cuda.device(lowres.device):
-        _lib.check(_lib.confidence_symbol("vitseg_confidence")(
+        _lib.check(_lib.symbol("vitseg_confidence")(
             lowres.data_ptr(), mask.data_ptr(), n, C, g, S, KINDS[kind], _ptr(conf), _ptr(conf_q), _ptr(labels), _ptr(scores),
             0 if scores is None else int(scores.shape[1]), int(low_q), _ptr(gt), int(ignore_label), _ptr(hist),
             0 if hist is None else int(hist.shape[1]), torch.cuda.current_stream().cuda_stream))

@@ -318,15 +318,15 @@ class Evaluator:
                                                                self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
                                                                st))
                 gt = g2
-            nbytes = _lib.distance_symbol("vitseg_distance_scratch_bytes")(n, H, W)
+            nbytes = _lib.symbol("vitseg_distance_scratch_bytes")(n, H, W)
             if nbytes == 0:
                 raise ValueError(f"distance metrics: H and W must lie in 1..16384 and n in 1..32767, got {n} x {H} x {W}")
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             si = torch.empty((n, K, 6), dtype=torch.int64, device=self.device)
             sf = torch.empty((n, K, 2), dtype=torch.float64, device=self.device)
-            _lib.check(_lib.distance_symbol("vitseg_distance_stats")(pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K, int(mode),
-                                                                     int(pct_num), int(pct_den), si.data_ptr(), sf.data_ptr(),
-                                                                     scratch.data_ptr(), nbytes, st))
+            _lib.check(_lib.symbol("vitseg_distance_stats")(pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K, int(mode),
+                                                            int(pct_num), int(pct_den), si.data_ptr(), sf.data_ptr(),
+                                                            scratch.data_ptr(), nbytes, st))
         return si, sf
 
     def distance_metrics(self, pred: torch.Tensor, gt: torch.Tensor, classes: Optional[Sequence[int]] = None,
@@ -376,16 +376,16 @@ class Evaluator:
                                                                self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
                                                                st))
                 gt = g2
-            nbytes = _lib.skeleton_symbol("vitseg_skeleton_stats_scratch_bytes")(n, H, W, int(route))
+            nbytes = _lib.symbol("vitseg_skeleton_stats_scratch_bytes")(n, H, W, int(route))
             if nbytes == 0:
                 raise ValueError(f"crack metrics: H and W must lie in 1..16384 and n in 1..32767 (and the plane must fit the "
                                  f"route asked for), got {n} x {H} x {W}, route {route}")
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             si = torch.empty((n, K, 10), dtype=torch.int64, device=self.device)
             sf = torch.empty((n, K, 2), dtype=torch.float64, device=self.device)
-            _lib.check(_lib.skeleton_symbol("vitseg_skeleton_stats")(pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K,
-                                                                     int(route), si.data_ptr(), sf.data_ptr(),
-                                                                     scratch.data_ptr(), nbytes, st))
+            _lib.check(_lib.symbol("vitseg_skeleton_stats")(pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K,
+                                                            int(route), si.data_ptr(), sf.data_ptr(),
+                                                            scratch.data_ptr(), nbytes, st))
         return si, sf
 
     def crack_metrics(self, pred: torch.Tensor, gt: torch.Tensor, classes: Optional[Sequence[int]] = None) -> List[dict]:
@@ -432,14 +432,14 @@ class Evaluator:
                                                                self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
                                                                st))
                 gt = g2
-            nbytes = _lib.match_symbol("vitseg_region_match_scratch_bytes")(n, H, W)
+            nbytes = _lib.symbol("vitseg_region_match_scratch_bytes")(n, H, W)
             if nbytes == 0:
                 raise ValueError(f"region metrics: H * W must stay below 2^31 and n in 1..32767, got {n} x {H} x {W}")
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             stats = torch.empty((n, K, 8), dtype=torch.int64, device=self.device)
             pinfo = torch.empty((n, H, W, 2), dtype=torch.int32, device=self.device) if return_info else None
             ginfo = torch.empty((n, H, W, 2), dtype=torch.int32, device=self.device) if return_info else None
-            _lib.check(_lib.match_symbol("vitseg_region_match")(
+            _lib.check(_lib.symbol("vitseg_region_match")(
                 pred.data_ptr(), gt.data_ptr(), n, H, W, cls, K, int(connectivity), int(background), int(ignore_label),
                 int(iou[0]), int(iou[1]), int(coverage[0]), int(coverage[1]), stats.data_ptr(),
                 None if pinfo is None else pinfo.data_ptr(), None if ginfo is None else ginfo.data_ptr(), scratch.data_ptr(),

@@ -317,9 +317,9 @@ class ViTSegmentationModel(nn.Module):
                 rc = _lib.lib().vitseg_forward(cfg, self.arena.data_ptr(), _ptr(lp), x.data_ptr(), B, self.precision,
                                                _ptr(logits), _ptr(mask), ws.data_ptr(), ws.numel(), stream)
             else:
-                rc = _lib.at_symbol("vitseg_forward_at")(cfg, S, self.arena.data_ptr(), _ptr(lp), x.data_ptr(), B,
-                                                         self.precision, _ptr(logits), _ptr(mask), ws.data_ptr(),
-                                                         ws.numel(), stream)
+                rc = _lib.symbol("vitseg_forward_at")(cfg, S, self.arena.data_ptr(), _ptr(lp), x.data_ptr(), B,
+                                                      self.precision, _ptr(logits), _ptr(mask), ws.data_ptr(),
+                                                      ws.numel(), stream)
         _lib.check(rc)
         return logits, mask
 
@@ -357,7 +357,7 @@ class ViTSegmentationModel(nn.Module):
             if S == self.cfg.image_size:
                 _lib.check(_lib.lib().vitseg_forward_train(cfg, *args, stream))
             else:
-                _lib.check(_lib.at_symbol("vitseg_forward_train_at")(cfg, S, *args, stream))
+                _lib.check(_lib.symbol("vitseg_forward_train_at")(cfg, S, *args, stream))
         return logits
 
     def no_sync(self):
@@ -454,15 +454,15 @@ class ViTSegmentationModel(nn.Module):
             cfg = C.byref(_lib.CConfig.from_config(self.cfg))
             if dice_opts is not None:
                 terms = torch.zeros(3, dtype=torch.float32, device=x.device)
-                _lib.check(_lib.dice_symbol("vitseg_backward_dice")(
+                _lib.check(_lib.symbol("vitseg_backward_dice")(
                     cfg, S, *args, C.byref(ce_opts) if ce_opts is not None else None, C.byref(dice_opts), terms.data_ptr()))
                 loss = terms
             elif ce_opts is not None:
-                _lib.check(_lib.ce_opts_symbol("vitseg_backward_opts")(cfg, S, *args, C.byref(ce_opts)))
+                _lib.check(_lib.symbol("vitseg_backward_opts")(cfg, S, *args, C.byref(ce_opts)))
             elif S == self.cfg.image_size:
                 _lib.check(_lib.lib().vitseg_backward(cfg, *args))
             else:
-                _lib.check(_lib.at_symbol("vitseg_backward_at")(cfg, S, *args))
+                _lib.check(_lib.symbol("vitseg_backward_at")(cfg, S, *args))
             if overlap:
                 # the whole backward is enqueued by now; each ring starts when its bucket's event fires and the
                 # compute stream only rejoins after the last one (what DDP's finalize does)
@@ -688,7 +688,7 @@ class ViTSegmentationModel(nn.Module):
         lowres = torch.empty((T, Cc, g, g), dtype=torch.float32, device=dev)
         ws, lp = self.workspace(chunk, S), self._bf16_arena()
         ccfg = C.byref(_lib.CConfig.from_config(cfg))
-        gather, fwd = _lib.window_symbol("vitseg_window_gather"), _lib.window_symbol("vitseg_forward_lowres")
+        gather, fwd = _lib.symbol("vitseg_window_gather"), _lib.symbol("vitseg_forward_lowres")
         route = self.forward_route(chunk, S)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
@@ -715,10 +715,10 @@ class ViTSegmentationModel(nn.Module):
         logits = torch.empty((B, Cc, H, W), dtype=torch.float32, device=dev) if want_logits else None
         mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_mask else None
         with torch.cuda.device(dev):
-            _lib.check(_lib.window_symbol("vitseg_window_blend")(p["lowres"].data_ptr(), p["tab"].data_ptr(), p["ny"],
-                                                                 p["tab"][p["ny"]:].data_ptr(), p["nx"], p["wtab"].data_ptr(), B,
-                                                                 Cc, p["g"], p["S"], H, W, _ptr(logits), _ptr(mask),
-                                                                 torch.cuda.current_stream().cuda_stream))
+            _lib.check(_lib.symbol("vitseg_window_blend")(p["lowres"].data_ptr(), p["tab"].data_ptr(), p["ny"],
+                                                          p["tab"][p["ny"]:].data_ptr(), p["nx"], p["wtab"].data_ptr(), B,
+                                                          Cc, p["g"], p["S"], H, W, _ptr(logits), _ptr(mask),
+                                                          torch.cuda.current_stream().cuda_stream))
         return (mask, logits) if want_logits and want_mask else (mask if want_mask else logits)
 
     # ------------------------------------------------------------------ test-time augmentation
@@ -769,7 +769,7 @@ class ViTSegmentationModel(nn.Module):
         tab = self._tta_matrix(op, S, size, B)
         none = (_lib.CAugmentMask * 1)()
         with torch.cuda.device(x.device):
-            _lib.check(_lib.augment_symbol("vitseg_augment")(
+            _lib.check(_lib.symbol("vitseg_augment")(
                 x.data_ptr(), _lib.AUGMENT_U8_NHWC if u8 else _lib.AUGMENT_F32_NCHW, B, S, S, size, size, tab.data_ptr(),
                 None, out.data_ptr(), none, 0, _lib.AUGMENT_EDGE, None, 0, torch.cuda.current_stream().cuda_stream))
         return out
@@ -797,7 +797,7 @@ class ViTSegmentationModel(nn.Module):
         B, Cc, P, dev = int(x.shape[0]), cfg.num_classes, cfg.patch_size, x.device
         lp = self._bf16_arena()
         ccfg = C.byref(_lib.CConfig.from_config(cfg))
-        fwd = _lib.window_symbol("vitseg_forward_lowres")
+        fwd = _lib.symbol("vitseg_forward_lowres")
         bufs, out = {}, []
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
@@ -823,8 +823,8 @@ class ViTSegmentationModel(nn.Module):
         mask = torch.empty((B, S, S), dtype=torch.uint8, device=dev) if want_mask else None
         descs = (_lib.CTTAView * len(views))(*[_lib.CTTAView(low.data_ptr(), g, op, w) for low, g, op, w in views])
         with torch.cuda.device(dev):
-            _lib.check(_lib.tta_symbol("vitseg_tta_blend")(descs, len(views), B, Cc, S, mode, _ptr(merged), _ptr(mask),
-                                                           torch.cuda.current_stream().cuda_stream))
+            _lib.check(_lib.symbol("vitseg_tta_blend")(descs, len(views), B, Cc, S, mode, _ptr(merged), _ptr(mask),
+                                                       torch.cuda.current_stream().cuda_stream))
         return (mask, merged) if want_merged and want_mask else (mask if want_mask else merged)
 
     _CE_CACHE_ENTRIES = 8  # device weight vectors / scratch buffers kept per model, least recently used first out
@@ -856,7 +856,7 @@ class ViTSegmentationModel(nn.Module):
         wdev = None
         if w is not None:
             wdev = self._ce_cached("weight", (w.numpy().tobytes(), dev), lambda: w.to(dev).contiguous())
-        nbytes = int(_lib.ce_opts_symbol("vitseg_ce_options_scratch_bytes")(B, S))
+        nbytes = int(_lib.symbol("vitseg_ce_options_scratch_bytes")(B, S))
         scratch = self._ce_cached("scratch", (B, S, dev), lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
         opts = _lib.CCEOptions(int(ii is not None), 0, 0 if ii is None else ii, _ptr(wdev), eps, scratch.data_ptr(),
                                scratch.numel())
@@ -905,14 +905,14 @@ class ViTSegmentationModel(nn.Module):
             if opts is None:
                 _lib.check(_lib.lib().vitseg_ce_loss(*args, stream))
             else:
-                _lib.check(_lib.ce_opts_symbol("vitseg_ce_loss_opts")(*args, C.byref(opts), 1.0, stream))
+                _lib.check(_lib.symbol("vitseg_ce_loss_opts")(*args, C.byref(opts), 1.0, stream))
         return loss
 
     def _dice_options(self, B: int, S: int, dice_weight, ce_weight, smooth, include_background):
         """The `_lib.CDiceOptions` of a `ce_dice_loss` call (validated on the host); its scratch is cached per (batch, size)."""
         dw, cw, sm, bg = check_dice_options(self.cfg.num_classes, dice_weight, ce_weight, smooth, include_background)
         dev = self.arena.device
-        nbytes = int(_lib.dice_symbol("vitseg_dice_options_scratch_bytes")(B, self.cfg.num_classes, S))
+        nbytes = int(_lib.symbol("vitseg_dice_options_scratch_bytes")(B, self.cfg.num_classes, S))
         scratch = self._ce_cached("dice scratch", (B, S, dev), lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
         opts = _lib.CDiceOptions(cw, dw, sm, int(bg), scratch.data_ptr(), scratch.numel())
         opts._tensors = (scratch,)   # the struct holds a raw address: an eviction must not free it under the struct
@@ -950,7 +950,7 @@ class ViTSegmentationModel(nn.Module):
                 low = self.debug_buffer(B, _lib.BUF_LOWRES, S)
                 scratch = torch.empty(_lib.lib().vitseg_ce_scratch_bytes(B, S), dtype=torch.uint8, device=low.device)
                 terms = torch.empty(3, dtype=torch.float32, device=low.device)
-                _lib.check(_lib.dice_symbol("vitseg_ce_dice_loss")(
+                _lib.check(_lib.symbol("vitseg_ce_dice_loss")(
                     low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8), None, scratch.data_ptr(),
                     terms.data_ptr(), B, self.cfg.num_classes, S // self.cfg.patch_size, S,
                     C.byref(opts) if opts is not None else None, C.byref(dopts), 1.0, torch.cuda.current_stream().cuda_stream))

@@ -57,11 +57,11 @@ def _launch(m: torch.Tensor, background: int, connectivity: int, max_regions: in
     """Enqueues one vitseg_regions call on the current stream (no host sync): (counts, regions, labels or None)."""
     n, H, W = (int(d) for d in m.shape)
     dev = m.device
-    scratch = torch.empty(_lib.region_symbol("vitseg_regions_scratch_bytes")(n, H, W), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(_lib.symbol("vitseg_regions_scratch_bytes")(n, H, W), dtype=torch.uint8, device=dev)
     counts = torch.empty(n, dtype=torch.int32, device=dev)
     regions = torch.empty((n, max_regions, 8), dtype=torch.int32, device=dev)
     labels = torch.empty((n, H, W), dtype=torch.int32, device=dev) if want_labels else None
-    _lib.check(_lib.region_symbol("vitseg_regions")(
+    _lib.check(_lib.symbol("vitseg_regions")(
         m.data_ptr(), n, H, W, connectivity, background, counts.data_ptr(),
         regions.data_ptr() if max_regions > 0 else None, max_regions,
         labels.data_ptr() if labels is not None else None, scratch.data_ptr(), scratch.numel(),
@@ -147,7 +147,7 @@ def _launch_props(m: torch.Tensor, classes, background: int, connectivity: int, 
     K = len(classes)
     cls = (C.c_int32 * K)(*classes) if K else None
     with torch.cuda.device(dev):
-        nbytes = _lib.props_symbol("vitseg_region_props_scratch_bytes")(n, H, W, K, route)
+        nbytes = _lib.symbol("vitseg_region_props_scratch_bytes")(n, H, W, K, route)
         if nbytes == 0:
             raise ValueError(f"region_props: a {H} x {W} plane does not fit the resident route of the skeleton (or the shape "
                              f"{n} x {H} x {W} is out of range)")
@@ -155,7 +155,7 @@ def _launch_props(m: torch.Tensor, classes, background: int, connectivity: int, 
         counts = torch.empty(n, dtype=torch.int32, device=dev)
         props = torch.empty((n, max_regions, _lib.PROPS_FIELDS), dtype=torch.int64, device=dev)
         labels = torch.empty((n, H, W), dtype=torch.int32, device=dev) if want_labels else None
-        _lib.check(_lib.props_symbol("vitseg_region_props")(
+        _lib.check(_lib.symbol("vitseg_region_props")(
             m.data_ptr(), n, H, W, connectivity, background, cls, K, route, counts.data_ptr(),
             props.data_ptr() if max_regions > 0 else None, max_regions,
             labels.data_ptr() if labels is not None else None, scratch.data_ptr(), nbytes,

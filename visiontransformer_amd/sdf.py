@@ -55,12 +55,12 @@ def _launch(m: torch.Tensor, normalize: bool):
     float32 [n, H, W] each."""
     n, H, W = (int(d) for d in m.shape)
     dev = m.device
-    scratch = torch.empty(_lib.sdf_symbol("vitseg_sdf_scratch_bytes")(n, H, W), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(_lib.symbol("vitseg_sdf_scratch_bytes")(n, H, W), dtype=torch.uint8, device=dev)
     e = torch.empty((n, H, W), dtype=torch.float32, device=dev)
     i = torch.empty((n, H, W), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.sdf_symbol("vitseg_sdf")(m.data_ptr(), n, H, W, int(bool(normalize)), e.data_ptr(), i.data_ptr(),
-                                                 scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(_lib.symbol("vitseg_sdf")(m.data_ptr(), n, H, W, int(bool(normalize)), e.data_ptr(), i.data_ptr(),
+                                             scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream))
     return e, i
 
 

@@ -25,17 +25,17 @@ def _launch(m: torch.Tensor, route: int, want_passes: bool):
     n, H, W = (int(d) for d in m.shape)
     dev = m.device
     with torch.cuda.device(dev):
-        nbytes = _lib.skeleton_symbol("vitseg_skeleton_scratch_bytes")(n, H, W, route)
+        nbytes = _lib.symbol("vitseg_skeleton_scratch_bytes")(n, H, W, route)
         if nbytes == 0:
             raise ValueError(f"skeletonize: a {H} x {W} plane does not fit the resident route (or n = {n} is outside "
                              f"1..{MAX_BATCH})")
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         out = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
         passes = torch.empty(n, dtype=torch.int32, device=dev) if want_passes else None
-        _lib.check(_lib.skeleton_symbol("vitseg_skeleton")(m.data_ptr(), n, H, W, route, out.data_ptr(),
-                                                           None if passes is None else passes.data_ptr(),
-                                                           scratch.data_ptr(), nbytes,
-                                                           torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(_lib.symbol("vitseg_skeleton")(m.data_ptr(), n, H, W, route, out.data_ptr(),
+                                                  None if passes is None else passes.data_ptr(),
+                                                  scratch.data_ptr(), nbytes,
+                                                  torch.cuda.current_stream(dev).cuda_stream))
     return out, passes
 
 
