@@ -48,13 +48,15 @@ def main():
                          "(position, size, axes, orientation, perimeter, frame contact) and, for the listed classes (default: "
                          "all present but the background 0), the region's own skeleton length and widths; regions by "
                          "--region-connectivity")
-    ap.add_argument("--pixel-size", type=float, default=1.0, help="side of a pixel: the unit of the lengths in <model>_region_props.csv")
+    ap.add_argument("--pixel-size", type=float, default=1.0, help="side of a pixel: the unit of the lengths in <model>_region_props.csv and of the coordinates in "
+                         "<model>_region_polygons.geojson")
     ap.add_argument("--tta", help='test-time augmentation: "hflip", "flip" or "d4" -- the mask is merged from flipped / '
                                   "quarter-turned views (default: one look)")
     ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
     ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"], help="mean of the views' logits or of their sigmoids")
     clean.add_arguments(ap)
     scripts.add_confidence_arguments(ap)
+    scripts.add_polygon_arguments(ap)
     a = ap.parse_args()
     confidence = scripts.confidence_options(ap, a)
     dev = "cuda:0"
@@ -70,14 +72,16 @@ def main():
             model.load_state_dict(torch.load(ck, map_location="cpu")["state_dict"])
         name = f"ID{vid}P{P}H{D}A{A}"
         batches = scripts.paed_binary_batches(model.model.cfg, a.num_batches * a.batch_size, a.batch_size, a.data, seed=5)
-        rows = scripts.evaluate_to_csv(model, batches, (vid, name, P, D, L, A), os.path.join(cwd, a.out, name, f"{name}_metrics.csv"),
+        csv_path = os.path.join(cwd, a.out, name, f"{name}_metrics.csv")
+        rows = scripts.evaluate_to_csv(model, batches, (vid, name, P, D, L, A), csv_path,
                                        max(a.num_classes, 2), a.num_batches, dev,
                                        distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None,
                                        tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge,
                                        region_classes=True if a.region_metrics else None, region_iou=a.region_iou,
                                        region_coverage=a.region_coverage, region_connectivity=a.region_connectivity,
                                        props_classes=scripts.parse_props_classes(a.region_props),
-                                       props_pixel_size=a.pixel_size, **clean.arguments(a), **confidence)
+                                       props_pixel_size=a.pixel_size, **clean.arguments(a), **confidence,
+                                       **scripts.polygon_options(a, csv_path))
         print(f"{name}: {len(rows)} images evaluated -> {os.path.join(a.out, name)}")
 
 

@@ -1,0 +1,46 @@
+"""Bindings of the family headers: entry points of csrc/libvitseg.so that are declared beside include/vitseg.h.
+
+A feature family has a header of its own (include/vitseg_<family>.h, with its own version) and one entry of EXT_SIGNATURES:
+family -> (header file, the words after "built before" in `ext_symbol`'s error, [(name, restype, argtypes)]).  `_lib.SIGNATURES`
+and include/vitseg.h do not grow with it.  Functions are bound on first use on the handle `_lib.lib()` loaded;
+tests/test_polygons_cpu.py compares the table with the header through the parser of tests/test_binding_cpu.py.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _lib
+from ._lib import i32, i64, sz, vp
+
+POLYGONS_VERSION = 100   # include/vitseg_polygons.h VITSEG_POLYGONS_VERSION this binding was written against
+
+EXT_SIGNATURES = {
+    # region outlines: polygon rings with holes (polygons.py)
+    "polygons": ("vitseg_polygons.h", "the region outlines", [
+        ("vitseg_polygons_version", i32, []),
+        ("vitseg_region_polygons_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_region_polygons", i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, sz, vp]),
+    ]),
+}
+EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION)}
+
+
+
+def ext_symbol(family: str, name: str):
+    """The entry point `name` of `family` on `_lib.lib()`'s handle, restype and argtypes set from EXT_SIGNATURES on first use;
+    a RuntimeError naming the rebuild when the loaded library predates the family (or `name` is not in its table) or was built
+    from another version of its header."""
+    _, what, rows = EXT_SIGNATURES[family]
+    row = {n: (restype, argtypes) for n, restype, argtypes in rows}.get(name)
+    fn = getattr(_lib.lib(), name, None) if row is not None else None
+    if fn is None:
+        raise RuntimeError(f"{_lib.LIB_PATH} has no {name} (built before {what}): rebuild it (python -m visiontransformer_amd.build)")
+    if getattr(fn, "_ext_bound", False):
+        return fn
+    fn.restype, fn.argtypes = row[0], list(row[1])
+    vname, version = EXT_VERSIONS[family]
+    if name != vname and ext_symbol(family, vname)() != version:
+        raise RuntimeError(f"{_lib.LIB_PATH} has {what} at version {ext_symbol(family, vname)()}, this binding expects "
+                           f"{version}: rebuild it (python -m visiontransformer_amd.build)")
+    fn._ext_bound = True
+    return fn

@@ -245,5 +245,10 @@ size_t region_props_scratch_bytes(int n, int H, int W, int K, int route);
 int launch_region_props(const unsigned char* mask, int n, int H, int W, int connectivity, int background, const int* classes,
                         int K, int route, int* counts, long long* props, int max_regions, int* labels, void* scratch,
                         size_t scratch_bytes, hipStream_t s);
+// region outlines (polygons.hip: vitseg_region_polygons, include/vitseg_polygons.h): polygon rings with holes
+size_t region_polygons_scratch_bytes(int n, int H, int W);
+int launch_region_polygons(const unsigned char* mask, int n, int H, int W, int connectivity, int background, int* region_counts,
+                           int* ring_counts, long long* vertex_counts, long long* rings, int max_rings, int* vertices,
+                           long long max_vertices, int* labels, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 }  // namespace vitseg

@@ -565,6 +565,24 @@ class ViTSegmentationModel(nn.Module):
         return (recs, mask) if return_mask else recs
 
     @torch.no_grad()
+    def predict_polygons(self, x: torch.Tensor, *, background: int = 0, connectivity: int = 4,
+                         interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,
+                         max_hole_area: int = 0, return_mask: bool = False):
+        """The outlines of the regions of each image's predicted mask: a list of (records, polygons) pairs, `records` the int32
+        [k, 7] rows of `predict_regions`, `polygons[i]` the rings of region i as int32 [v, 2] arrays of (y, x) pixel corners,
+        the outer ring first, then the holes (polygons.region_polygons).  The forward, the mask and the outlining are enqueued
+        on one stream; the host waits once, for the counts.  `min_area` / `fill_holes` / `max_hole_area` (defaults: off): the
+        outlines, and the mask returned, are those of the mask cleaned by clean.clean_mask with this call's `connectivity` and
+        `background`.  `return_mask`: also the uint8 [B, H, W] device mask."""
+        from . import clean as _clean, polygons as _polygons
+        mask = self.predict_mask(x, interpolate_pos_encoding=interpolate_pos_encoding)
+        if min_area or fill_holes or max_hole_area:
+            mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area,
+                                     connectivity=connectivity, background=background)
+        out = _polygons.region_polygons(mask, background=background, connectivity=connectivity)
+        return (out, mask) if return_mask else out
+
+    @torch.no_grad()
     def predict_mask_graphed(self, x: torch.Tensor, return_logits: bool = False, interpolate_pos_encoding: bool = False):
         """`predict_mask` replayed from a captured hipGraph (one per batch size and output set): the ~110 kernel
         launches of a forward become one graph launch.  Measured (tools/latency_probe.py, ViT-B/16): no gain at batch

@@ -72,7 +72,7 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
             sliding: bool = False, stride: Optional[int] = None, weights: str = "linear", tta=None, tta_sizes=None,
             tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0,
             return_props: bool = False, props_classes=None, pixel_size: float = 1.0, return_scores: bool = False,
-            return_confidence: bool = False, score_kind: str = "prob", low: float = 0.5):
+            return_confidence: bool = False, score_kind: str = "prob", low: float = 0.5, return_polygons: bool = False):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
@@ -98,7 +98,10 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     pixels with p below `low`) -- and the fp32 [S, S] map of p (confidence.region_scores / confidence_map; `score_kind`
     "prob": the sigmoid of the class the mask states, "margin": its lead over the best other class).  The scores are
     re-generated on the device from the low-res head output of the same forward.  With `sliding` or `tta` they raise
-    ValueError before anything runs: scoring blended views is not built."""
+    ValueError before anything runs: scoring blended views is not built.
+    `return_polygons`: also, last of all, the pair (records, polygons) of polygons.region_polygons for the (cleaned) mask: the
+    int32 [k, 7] records of its regions and, per region, its outline as rings of (y, x) pixel corners, the outer ring first,
+    then the holes.  It reads the mask alone, so it goes with `sliding` and `tta`."""
     from . import clean as _clean
     _clean.check_options(min_area, fill_holes, max_hole_area)
     scoring = bool(return_scores or return_confidence)
@@ -150,6 +153,10 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
         region_scores = _conf.region_dicts(*_conf.region_scores(lowres[0], mask_dev, kind=score_kind, low=low))
     if return_confidence:
         conf_map = _conf.confidence_map(lowres[0], mask_dev, kind=score_kind).cpu().numpy()
+    polygons = None
+    if return_polygons:
+        from .polygons import region_polygons
+        polygons = region_polygons(mask_dev)
     mask = mask_dev.cpu().numpy()
     res = [mask]
     if index_to_color is not None:
@@ -164,4 +171,6 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
         res.append(region_scores)
     if return_confidence:
         res.append(conf_map)
+    if return_polygons:
+        res.append(polygons)
     return res[0] if len(res) == 1 else tuple(res)

@@ -4,6 +4,7 @@ torch.save'd dict), checkpoint discovery with the reference's rule, and the per-
 """
 from __future__ import annotations
 
+import json
 import os
 import re
 import time
@@ -216,6 +217,23 @@ def confidence_options(ap, a) -> dict:
     return dict(region_scores=a.region_scores, score_kind=a.score_kind, score_low=a.score_low, calibration_bins=a.calibration)
 
 
+def add_polygon_arguments(ap) -> None:
+    """--region-polygons of the evaluation scripts."""
+    ap.add_argument("--region-polygons", action="store_true",
+                    help="also write <model>_region_polygons.geojson: the outline of every predicted region as a polygon with "
+                         "holes, coordinates in units of --pixel-size; regions by --region-connectivity, on the mask that "
+                         "--min-area, --fill-holes and --tta produce")
+
+
+def polygon_options(a, metrics_csv_path: str) -> dict:
+    """The keywords of `evaluate_to_csv` from the parsed flags: none without --region-polygons, else `polygons_path`, the
+    .geojson file beside the metrics file."""
+    if not a.region_polygons:
+        return {}
+    stem = metrics_csv_path[:-len("_metrics.csv")] if metrics_csv_path.endswith("_metrics.csv") else os.path.splitext(metrics_csv_path)[0]
+    return dict(polygons_path=stem + "_region_polygons.geojson")
+
+
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
                     distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
                     percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None,
@@ -224,7 +242,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                     region_coverage=0.5, region_connectivity: int = 4, props_classes=None,
                     props_csv_path: Optional[str] = None, props_pixel_size: float = 1.0, region_scores: bool = False,
                     score_kind: str = "prob", score_low: float = 0.5, calibration_bins: Optional[int] = None,
-                    scores_csv_path: Optional[str] = None, calibration_csv_path: Optional[str] = None) -> List[list]:
+                    scores_csv_path: Optional[str] = None, calibration_csv_path: Optional[str] = None,
+                    polygons_path: Optional[str] = None) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
@@ -253,7 +272,10 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     calibration_bins (None: off): the reliability table pooled over all images (confidence.calibration_hist of the mask against
     the resized ground truth, the integers added before any ratio) and its ECE go to calibration_csv_path (default:
     ..._calibration.csv).  Either makes the forward keep its low-res head output (one encoder pass, predict_mask's mask bit
-    for bit); with tta they raise ValueError: scoring merged views is not built."""
+    for bit); with tta they raise ValueError: scoring merged views is not built.
+    polygons_path (None: off): the outlines of every predicted region of the (cleaned, merged) mask
+    (polygons.region_polygons at region_connectivity, coordinates in units of props_pixel_size) go to that file as one GeoJSON
+    FeatureCollection, each feature carrying its image as image_id "<batch>/<index>" and its batch_num / image_idx."""
     from . import clean as _clean
     from . import confidence as _conf
     min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
@@ -271,6 +293,7 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     ev = Evaluator(num_classes, device)
     rows, drows, crows, rrows, rstats, prows = [], [], [], [], [], []
     srows, ranked, pooled_hist = [], {}, None
+    features = []
     if props_classes is True:
         props_classes = list(range(1, num_classes))
     if crack_classes is True:
@@ -333,6 +356,12 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                 for source in ("pred", "gt"):
                     for r, d in enumerate(m[source]):
                         prows.append(props_csv_row(source, model_info, bn, idx, r, d))
+        if polygons_path is not None:
+            from . import polygons as _poly
+            for idx, (rec, rings) in enumerate(_poly.region_polygons(mask, connectivity=region_connectivity)):
+                for f in _poly.polygons_to_geojson(rec, rings, pixel_size=props_pixel_size, image_id=f"{bn}/{idx}")["features"]:
+                    f["properties"].update(model_id=model_info[0], model_name=model_info[1], batch_num=bn, image_idx=idx)
+                    features.append(f)
     os.makedirs(os.path.dirname(os.path.abspath(csv_path)), exist_ok=True)
     write_metrics_csv(csv_path, rows)
     stem = csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
@@ -360,4 +389,7 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     if calibration_bins is not None:
         _conf.write_csv(calibration_csv_path or stem + "_calibration.csv", _conf.CALIBRATION_CSV_COLUMNS,
                         _conf.calibration_csv_rows(model_info, pooled_hist, calibration_bins))
+    if polygons_path is not None:
+        with open(polygons_path, "w") as f:
+            json.dump({"type": "FeatureCollection", "features": features}, f)
     return rows
