@@ -45,8 +45,8 @@ def main():
                          "(position, size, axes, orientation, perimeter, frame contact) and, for the listed classes (default: "
                          "all present but the background 0), the region's own skeleton length and widths; regions by "
                          "--region-connectivity")
-    ap.add_argument("--pixel-size", type=float, default=1.0, help="side of a pixel: the unit of the lengths in <model>_region_props.csv and of the coordinates in "
-                         "<model>_region_polygons.geojson")
+    ap.add_argument("--pixel-size", type=float, default=1.0, help="side of a pixel: the unit of the lengths in <model>_region_props.csv and <model>_crack_branches.csv and of the "
+                         "coordinates in <model>_region_polygons.geojson and <model>_crack_graph.geojson")
     ap.add_argument("--tta", help='test-time augmentation: "hflip", "flip" or "d4" -- the mask is merged from flipped / '
                                   "quarter-turned views (default: one look)")
     ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
@@ -54,6 +54,7 @@ def main():
     clean.add_arguments(ap)
     scripts.add_confidence_arguments(ap)
     scripts.add_polygon_arguments(ap)
+    scripts.add_crack_graph_arguments(ap)
     a = ap.parse_args()
     confidence = scripts.confidence_options(ap, a)
     dev = "cuda:0"
@@ -76,7 +77,7 @@ def main():
                                        region_coverage=a.region_coverage, region_connectivity=a.region_connectivity,
                                        props_classes=scripts.parse_props_classes(a.region_props),
                                        props_pixel_size=a.pixel_size, **clean.arguments(a), **confidence,
-                                       **scripts.polygon_options(a, csv_path))
+                                       **scripts.polygon_options(a, csv_path), **scripts.crack_graph_options(a, csv_path))
         acc = sum(r[8] for r in rows) / max(len(rows), 1)
         print(f"{name}: {len(rows)} images, mean accuracy {acc:.2f} %, {rows[0][11] * 1e3:.2f} ms/image")
 

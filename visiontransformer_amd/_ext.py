@@ -4,6 +4,8 @@ A feature family has a header of its own (include/vitseg_<family>.h, with its ow
 family -> (header file, the words after "built before" in `ext_symbol`'s error, [(name, restype, argtypes)]).  `_lib.SIGNATURES`
 and include/vitseg.h do not grow with it.  Functions are bound on first use on the handle `_lib.lib()` loaded;
 tests/test_polygons_cpu.py compares the table with the header through the parser of tests/test_binding_cpu.py.
+EXT_SIGNATURES is pinned to the polygons family by that test; later families have the same kind of entry in EXT_FAMILIES
+(tests/test_centerlines_cpu.py), which `ext_symbol` consults after EXT_SIGNATURES.
 """
 from __future__ import annotations
 
@@ -13,6 +15,7 @@ from . import _lib
 from ._lib import i32, i64, sz, vp
 
 POLYGONS_VERSION = 100   # include/vitseg_polygons.h VITSEG_POLYGONS_VERSION this binding was written against
+CENTERLINES_VERSION = 100   # include/vitseg_centerlines.h VITSEG_CENTERLINES_VERSION
 
 EXT_SIGNATURES = {
     # region outlines: polygon rings with holes (polygons.py)
@@ -22,15 +25,24 @@ EXT_SIGNATURES = {
         ("vitseg_region_polygons", i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, sz, vp]),
     ]),
 }
-EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION)}
-
+EXT_FAMILIES = {
+    # crack centre-lines as a graph: nodes, branches, polylines (centerlines.py)
+    "centerlines": ("vitseg_centerlines.h", "the crack centre-lines", [
+        ("vitseg_centerlines_version", i32, []),
+        ("vitseg_centerlines_scratch_bytes", sz, [i32, i32, i32, i32]),
+        ("vitseg_centerlines", i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i64, vp, sz, vp]),
+    ]),
+}
+EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
+                "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION)}
 
 
 def ext_symbol(family: str, name: str):
-    """The entry point `name` of `family` on `_lib.lib()`'s handle, restype and argtypes set from EXT_SIGNATURES on first use;
+    """The entry point `name` of `family` on `_lib.lib()`'s handle, restype and argtypes set from EXT_SIGNATURES / EXT_FAMILIES on first
+    use;
     a RuntimeError naming the rebuild when the loaded library predates the family (or `name` is not in its table) or was built
     from another version of its header."""
-    _, what, rows = EXT_SIGNATURES[family]
+    _, what, rows = EXT_SIGNATURES[family] if family in EXT_SIGNATURES else EXT_FAMILIES[family]
     row = {n: (restype, argtypes) for n, restype, argtypes in rows}.get(name)
     fn = getattr(_lib.lib(), name, None) if row is not None else None
     if fn is None:

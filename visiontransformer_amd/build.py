@@ -31,7 +31,8 @@ def _stale(target, deps):
 def build(force: bool = False, verbose: bool = False) -> str:
     srcs = sources()
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "vitseg.h"))
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    hdrs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]   # vitseg.h and every family header
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
 

@@ -250,5 +250,10 @@ size_t region_polygons_scratch_bytes(int n, int H, int W);
 int launch_region_polygons(const unsigned char* mask, int n, int H, int W, int connectivity, int background, int* region_counts,
                            int* ring_counts, long long* vertex_counts, long long* rings, int max_rings, int* vertices,
                            long long max_vertices, int* labels, void* scratch, size_t scratch_bytes, hipStream_t s);
+// crack centre-lines as a graph (centerlines.hip: vitseg_centerlines, include/vitseg_centerlines.h): nodes, branches, polylines
+size_t centerlines_scratch_bytes(int n, int H, int W, int route);
+int launch_centerlines(const unsigned char* mask, int n, int H, int W, int value, int thin, int route, int* node_counts,
+                       int* branch_counts, long long* point_counts, int* nodes, int max_nodes, long long* branches,
+                       int max_branches, int* points, long long max_points, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 }  // namespace vitseg

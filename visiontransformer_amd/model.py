@@ -583,6 +583,27 @@ class ViTSegmentationModel(nn.Module):
         return (out, mask) if return_mask else out
 
     @torch.no_grad()
+    def predict_centerlines(self, x: torch.Tensor, classes, *, route: str = "auto", background: int = 0, connectivity: int = 4,
+                            interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,
+                            max_hole_area: int = 0, return_mask: bool = False):
+        """The centre-line graph of the label values `classes` in each image's predicted mask: a list of dicts class ->
+        (nodes, branches, points), the rows of centerlines.trace on the skeleton of {mask == class}.  `min_area` /
+        `fill_holes` / `max_hole_area` (defaults: off): the graph, and the mask returned, are those of the mask cleaned by
+        clean.clean_mask with this call's `connectivity` and `background`.  `return_mask`: also the uint8 [B, H, W] device
+        mask."""
+        from . import centerlines as _centerlines, clean as _clean
+        if classes is None:
+            raise ValueError("classes must be a sequence of label values")
+        _centerlines.check_options(classes, True, route)   # before the forward
+        _clean.check_options(min_area, fill_holes, max_hole_area)
+        mask = self.predict_mask(x, interpolate_pos_encoding=interpolate_pos_encoding)
+        if min_area or fill_holes or max_hole_area:
+            mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area,
+                                     connectivity=connectivity, background=background)
+        out = _centerlines.trace(mask, classes=classes, route=route)
+        return (out, mask) if return_mask else out
+
+    @torch.no_grad()
     def predict_mask_graphed(self, x: torch.Tensor, return_logits: bool = False, interpolate_pos_encoding: bool = False):
         """`predict_mask` replayed from a captured hipGraph (one per batch size and output set): the ~110 kernel
         launches of a forward become one graph launch.  Measured (tools/latency_probe.py, ViT-B/16): no gain at batch

@@ -72,7 +72,8 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
             sliding: bool = False, stride: Optional[int] = None, weights: str = "linear", tta=None, tta_sizes=None,
             tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0,
             return_props: bool = False, props_classes=None, pixel_size: float = 1.0, return_scores: bool = False,
-            return_confidence: bool = False, score_kind: str = "prob", low: float = 0.5, return_polygons: bool = False):
+            return_confidence: bool = False, score_kind: str = "prob", low: float = 0.5, return_polygons: bool = False,
+            return_centerlines: bool = False, centerline_classes=None):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
@@ -101,9 +102,17 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     ValueError before anything runs: scoring blended views is not built.
     `return_polygons`: also, last of all, the pair (records, polygons) of polygons.region_polygons for the (cleaned) mask: the
     int32 [k, 7] records of its regions and, per region, its outline as rings of (y, x) pixel corners, the outer ring first,
-    then the holes.  It reads the mask alone, so it goes with `sliding` and `tta`."""
+    then the holes.  It reads the mask alone, so it goes with `sliding` and `tta`.
+    `return_centerlines`: also, last of all, the dict class -> (nodes, branches, points) of centerlines.trace for the label
+    values `centerline_classes` (required) of the (cleaned) mask: the centre-line graph of each class's skeleton.  It reads the
+    mask alone as well."""
     from . import clean as _clean
     _clean.check_options(min_area, fill_holes, max_hole_area)
+    if return_centerlines:
+        from . import centerlines as _centerlines
+        if centerline_classes is None:
+            raise ValueError("return_centerlines needs centerline_classes, a sequence of label values")
+        _centerlines.check_options(centerline_classes)
     scoring = bool(return_scores or return_confidence)
     if scoring:
         from . import confidence as _conf
@@ -157,6 +166,9 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     if return_polygons:
         from .polygons import region_polygons
         polygons = region_polygons(mask_dev)
+    graph = None
+    if return_centerlines:
+        graph = _centerlines.trace(mask_dev, classes=centerline_classes)
     mask = mask_dev.cpu().numpy()
     res = [mask]
     if index_to_color is not None:
@@ -173,4 +185,6 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
         res.append(conf_map)
     if return_polygons:
         res.append(polygons)
+    if return_centerlines:
+        res.append(graph)
     return res[0] if len(res) == 1 else tuple(res)

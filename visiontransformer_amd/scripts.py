@@ -234,6 +234,33 @@ def polygon_options(a, metrics_csv_path: str) -> dict:
     return dict(polygons_path=stem + "_region_polygons.geojson")
 
 
+def add_crack_graph_arguments(ap) -> None:
+    """--crack-graph of the evaluation scripts."""
+    ap.add_argument("--crack-graph", nargs="?", const="all", metavar="CLASSES",
+                    help="also write <model>_crack_graph.geojson and <model>_crack_branches.csv: the centre-lines of the listed "
+                         'classes (comma-separated label values, or "all": every class but the background 0) as a graph -- one '
+                         "LineString / one row per branch with its length, widths and ends, then a summary row per image and "
+                         "class; lengths and coordinates in units of --pixel-size, on the mask that --min-area, --fill-holes and "
+                         "--tta produce")
+
+
+def crack_graph_options(a, metrics_csv_path: str) -> dict:
+    """The keywords of `evaluate_to_csv` from the parsed flags: none without --crack-graph, else the classes (True for "all")
+    and the two files beside the metrics file."""
+    if a.crack_graph is None:
+        return {}
+    if a.crack_graph == "all":
+        classes = True
+    else:
+        try:
+            classes = [int(t) for t in a.crack_graph.split(",") if t.strip()]
+        except ValueError:
+            raise ValueError(f'--crack-graph takes "all" or comma-separated label values, got {a.crack_graph!r}') from None
+    stem = metrics_csv_path[:-len("_metrics.csv")] if metrics_csv_path.endswith("_metrics.csv") else os.path.splitext(metrics_csv_path)[0]
+    return dict(crack_graph_classes=classes, crack_graph_path=stem + "_crack_graph.geojson",
+                crack_branches_csv_path=stem + "_crack_branches.csv")
+
+
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
                     distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
                     percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None,
@@ -243,7 +270,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                     props_csv_path: Optional[str] = None, props_pixel_size: float = 1.0, region_scores: bool = False,
                     score_kind: str = "prob", score_low: float = 0.5, calibration_bins: Optional[int] = None,
                     scores_csv_path: Optional[str] = None, calibration_csv_path: Optional[str] = None,
-                    polygons_path: Optional[str] = None) -> List[list]:
+                    polygons_path: Optional[str] = None, crack_graph_classes=None, crack_graph_path: Optional[str] = None,
+                    crack_branches_csv_path: Optional[str] = None) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
@@ -275,7 +303,11 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     for bit); with tta they raise ValueError: scoring merged views is not built.
     polygons_path (None: off): the outlines of every predicted region of the (cleaned, merged) mask
     (polygons.region_polygons at region_connectivity, coordinates in units of props_pixel_size) go to that file as one GeoJSON
-    FeatureCollection, each feature carrying its image as image_id "<batch>/<index>" and its batch_num / image_idx."""
+    FeatureCollection, each feature carrying its image as image_id "<batch>/<index>" and its batch_num / image_idx.
+    crack_graph_classes (None: off; a list of label values, or True for every class but 0): the centre-line graph of each class
+    of the (cleaned, merged) mask (Evaluator.crack_graph, lengths and coordinates in units of props_pixel_size) goes to
+    crack_graph_path (default: ..._crack_graph.geojson) as one FeatureCollection of LineStrings, tagged like the outlines, and
+    to crack_branches_csv_path (default: ..._crack_branches.csv): one row per branch, then a summary row per image and class."""
     from . import clean as _clean
     from . import confidence as _conf
     min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
@@ -300,6 +332,12 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         crack_classes = list(range(1, num_classes))
     if region_classes is True:
         region_classes = list(range(1, num_classes))
+    if crack_graph_classes is True:
+        crack_graph_classes = list(range(1, num_classes))
+    if crack_graph_classes is not None:
+        from . import centerlines as _cl
+        crack_graph_classes = _cl.check_options(crack_graph_classes)
+        lines, brows = [], []
     model.eval()
     for bn, batch in enumerate(batches):
         if bn >= num_batches:
@@ -362,6 +400,15 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                 for f in _poly.polygons_to_geojson(rec, rings, pixel_size=props_pixel_size, image_id=f"{bn}/{idx}")["features"]:
                     f["properties"].update(model_id=model_info[0], model_name=model_info[1], batch_num=bn, image_idx=idx)
                     features.append(f)
+        if crack_graph_classes is not None:
+            for idx, per_class in enumerate(ev.crack_graph(mask, crack_graph_classes, pixel_size=props_pixel_size)):
+                for c, g in per_class.items():
+                    found = _cl.centerlines_to_geojson(g["branches"], g["points"], pixel_size=props_pixel_size,
+                                                       image_id=f"{bn}/{idx}", class_id=c)["features"]
+                    for f in found:
+                        f["properties"].update(model_id=model_info[0], model_name=model_info[1], batch_num=bn, image_idx=idx)
+                    lines += found
+                    brows += _cl.csv_rows(model_info, bn, idx, c, g["table"], g["summary"])
     os.makedirs(os.path.dirname(os.path.abspath(csv_path)), exist_ok=True)
     write_metrics_csv(csv_path, rows)
     stem = csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
@@ -392,4 +439,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     if polygons_path is not None:
         with open(polygons_path, "w") as f:
             json.dump({"type": "FeatureCollection", "features": features}, f)
+    if crack_graph_classes is not None:
+        with open(crack_graph_path or stem + "_crack_graph.geojson", "w") as f:
+            json.dump({"type": "FeatureCollection", "features": lines}, f)
+        _cl.write_csv(crack_branches_csv_path or stem + "_crack_branches.csv", brows)
     return rows
