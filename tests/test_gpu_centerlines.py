@@ -143,6 +143,24 @@ def test_nested_rings_are_closed_branches():
     _assert_equal(_both_fills(_dev(m), **_caps(exp)), exp, "rings")
 
 
+def test_more_than_256_pixel_chunks():
+    """262 x 1030: 264 pixel chunks and 1055 half-link chunks, so both chunk scans carry over more than one block of 256
+    chunk totals and every chunk base past the first block is used.  Row 254 is one open branch across pixel 262144, the
+    first pixel of chunk 256; the ring is a closed branch in chunk 259."""
+    H, W = 262, 1030
+    m = np.zeros((1, H, W), np.uint8)
+    lollipop, ring = CR.HAND["lollipop"], CR.HAND["ring_4x4"]
+    m[0, :lollipop.shape[0], :lollipop.shape[1]] = lollipop
+    m[0, 254, :] = 1
+    m[0, 257:257 + ring.shape[0], 1020:1020 + ring.shape[1]] = ring
+    exp = _ref("chunks", m)
+    nodes, branches, points = exp[0]
+    assert (len(nodes), len(branches), len(points)) == (4, 4, 1055)
+    assert branches[:, [0, 1, 3, 4]].tolist() == [[2063, 2063, 9, 0], [2063, 2066, 4, 0], [261620, 262649, 1030, 0],
+                                                  [265730, 265730, 12, 1]]
+    _assert_equal(_both_fills(_dev(m), **_caps(exp)), exp, "chunks")
+
+
 # ---- thin = 1: the skeleton of the plane ----
 
 def _thin_mask(kind, H, W):

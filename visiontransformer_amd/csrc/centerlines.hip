@@ -13,12 +13,13 @@
 //   (d2)         launch_sdf_d2 on the complement
 //   count        per pixel: its link mask (one byte, from the 3 x 3 pixels of S round it); half-links and nodes per chunk of
 //                1024 pixels
-//   scan         one workgroup per image and field: exclusive scan of the chunk totals; the half-link and node counts
+//   (scan)       chunk scan of chains.hip, one workgroup per image and field: exclusive scan of the chunk totals; the
+//                half-link and node counts
 //   build        per pixel: the index of its first half-link, every half-link's key (so half-links are numbered in key order)
 //                and the node rows
 //   link         per half-link: its successor and its word: its own index, bit 31 set unless it is terminal
-//   jump x R     pointer jumping, R = ceil(log2(4 H W)) rounds: after round j a half-link knows the smallest word among the
-//                2^(j+1) from itself on and the hops to it.  A terminal's word is below every other's on its walk, so a walk
+//   (jump x R)   chain jumps of chains.hip, R = ceil(log2(4 H W)) rounds: after round j a half-link knows the smallest word among
+//                the 2^(j+1) from itself on and the hops to it.  A terminal's word is below every other's on its walk, so a walk
 //                ends with (terminal, hops to it) and a cycle with (its smallest half-link, hops to it).  A round that
 //                changed nothing leaves a zero in its word of `changed`; the rounds after it return at once (the host never
 //                reads that word)
@@ -26,47 +27,21 @@
 //                walk through h starts at rev(terminal(rev(h))); a half-link leaving a node leads its branch when it is
 //                below the start of the walk from the other end, rev(terminal(h)); a cycle's smallest half-link leads a closed
 //                branch when it is the first half-link of its pixel (the other direction's smallest leaves the same pixel)
-//   scan         exclusive scan of both over the chunks: branch numbers and point offsets in key order
+//   (scan)       exclusive scan of both over the chunks: branch numbers and point offsets in key order
 //   place        per leader: the branch row's first five fields and, in `info`, what its half-links need
 //   emit         per half-link of a canonical walk: its head pixel to offset + rank + 1 (the leader also its tail to offset);
 //                of a canonical cycle: its tail pixel to offset + rank.  The link's kind, the points' q16 widths and d2
 //                go to the branch row with integer atomics, the lanes of a wave that share a row adding once
 // Every value is an integer; the only atomics are those sums and maxima (order-independent) and the `changed` flags.
+#include "chains.hpp"
 #include "kernels.hpp"
 #include "../../include/vitseg_centerlines.h"
 
 namespace vitseg {
 namespace {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
 constexpr int CL_MAX_SIDE = 16384, CL_MAX_BATCH = 32767;
-constexpr int CHUNK = 1024;         // pixels (count, build) or half-links (leaders, place) per workgroup: 4 per thread
-constexpr int JUMP_BLOCKS = 1024;   // workgroups per image of the half-link-strided launches (link, jump, emit)
 constexpr u32 LIVE = 0x80000000u;   // in a half-link's word: it is not terminal
-
-// exclusive scan of one int per thread over a 256-thread workgroup; total: the sum of all.  Whole workgroups call it.
-// (polygons.hip keeps its own copy: that family is not touched.)
-__device__ __forceinline__ int block_scan(int v, int* wsum /* shared [4] */, int& total) {
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    int inc = v;
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();   // the words may still be read from the call before
-    if (lane == WAVE - 1) wsum[wave] = inc;
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int w = 0; w < 4; ++w) {
-        const int s = wsum[w];
-        if (w < wave) before += s;
-        tot += s;
-    }
-    total = tot;
-    return before + inc - v;
-}
 
 __device__ __forceinline__ int dir_dy(int d) { return (d + (d >= 4)) / 3 - 1; }
 __device__ __forceinline__ int dir_dx(int d) { return (d + (d >= 4)) % 3 - 1; }
@@ -126,31 +101,6 @@ __global__ __launch_bounds__(256) void cl_count_kernel(const unsigned char* __re
     }
 }
 
-struct ScanOut {   // where the totals of the two fields go, [image]; any may be null
-    int* t32[2];
-    long long* t64[2];
-};
-
-// grid (n, 2): tot[image][chunk][field] becomes its exclusive scan over the chunks; the sums go to `out`
-__global__ __launch_bounds__(256) void cl_scan_kernel(int* __restrict__ tot, int nchunks, ScanOut out) {
-    __shared__ int wsum[4];
-    const int f = blockIdx.y;
-    int* t = tot + (size_t)blockIdx.x * nchunks * 2 + f;
-    int carry = 0;
-    for (int b0 = 0; b0 < nchunks; b0 += 256) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nchunks ? t[(size_t)b * 2] : 0;
-        int total;
-        const int ex = block_scan(v, wsum, total);
-        if (b < nchunks) t[(size_t)b * 2] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        if (out.t32[f]) out.t32[f][blockIdx.x] = carry;
-        if (out.t64[f]) out.t64[f][blockIdx.x] = carry;
-    }
-}
-
 // grid (ceil(P / 1024), n): hbase[pixel] = index of the pixel's first half-link; hkey[half-link] = 8 * pixel + direction; the
 // node rows (y, x, degree, d2) below max_nodes
 __global__ __launch_bounds__(256) void cl_build_kernel(const unsigned char* __restrict__ skel,
@@ -191,11 +141,6 @@ __global__ __launch_bounds__(256) void cl_build_kernel(const unsigned char* __re
     }
 }
 
-struct LinkBuf {   // one side of the pointer jumping: where the half-link's window ends, (smallest word in it) << 32 | hops to it
-    int* nxt;
-    u64* mh;
-};
-
 struct Graph {   // one image's arrays
     const unsigned char* lmask;
     const int* hbase;
@@ -217,7 +162,7 @@ struct Graph {   // one image's arrays
 // grid (JUMP_BLOCKS or fewer, n), half-link-strided: the successor and the word of every half-link
 __global__ __launch_bounds__(256) void cl_link_kernel(const unsigned char* __restrict__ lmask, const int* __restrict__ hbase,
                                                       const u32* __restrict__ hkey, const int* __restrict__ hcount,
-                                                      int* __restrict__ nxt0, LinkBuf out, int W, int P, size_t hcap) {
+                                                      int* __restrict__ nxt0, ChainBuf out, int W, int P, size_t hcap) {
     const Graph g{lmask + (size_t)blockIdx.y * P, hbase + (size_t)blockIdx.y * P, hkey + (size_t)blockIdx.y * hcap, W};
     const size_t hb = (size_t)blockIdx.y * hcap;
     const int cnt = hcount[blockIdx.y];
@@ -235,28 +180,6 @@ __global__ __launch_bounds__(256) void cl_link_kernel(const unsigned char* __res
         out.nxt[hb + v] = nx;
         out.mh[hb + v] = (u64)word << 32;
     }
-}
-
-// grid as link: one round of pointer jumping, in -> out
-__global__ __launch_bounds__(256) void cl_jump_kernel(LinkBuf in, LinkBuf out, const int* __restrict__ hcount,
-                                                      int* __restrict__ changed, size_t hcap, int round, int rounds) {
-    int* flags = changed + (size_t)blockIdx.y * rounds;
-    if (round > 0 && flags[round - 1] == 0) return;   // the whole launch: the word was written by the launch before
-    const size_t hb = (size_t)blockIdx.y * hcap;
-    const int cnt = hcount[blockIdx.y];
-    bool any = false;
-    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < cnt; v += (long long)gridDim.x * 256) {
-        const int j = in.nxt[hb + v];
-        u64 mine = in.mh[hb + v];
-        const u64 theirs = in.mh[hb + j];
-        if ((theirs >> 32) < (mine >> 32)) {
-            mine = (theirs & 0xffffffff00000000ull) | ((theirs & 0xffffffffull) + (1ull << round));
-            any = true;
-        }
-        out.nxt[hb + v] = in.nxt[hb + j];
-        out.mh[hb + v] = mine;
-    }
-    if (__syncthreads_or(any) && threadIdx.x == 0) atomicOr(&flags[round], 1);
 }
 
 struct Lead {   // what half-link v leads: points == 0: nothing
@@ -315,7 +238,7 @@ __global__ __launch_bounds__(256) void cl_leaders_kernel(const unsigned char* __
 __global__ __launch_bounds__(256) void cl_place_kernel(const unsigned char* __restrict__ lmask, const int* __restrict__ hbase,
                                                        const u32* __restrict__ hkey, const u64* __restrict__ mh,
                                                        const int* __restrict__ nxt0, const int* __restrict__ hcount,
-                                                       const int* __restrict__ ltot, LinkBuf info, long long* __restrict__ branches,
+                                                       const int* __restrict__ ltot, ChainBuf info, long long* __restrict__ branches,
                                                        int max_branches, int W, int P, size_t hcap, int nhc) {
     __shared__ int wsum[4];
     const Graph g{lmask + (size_t)blockIdx.y * P, hbase + (size_t)blockIdx.y * P, hkey + (size_t)blockIdx.y * hcap, W};
@@ -354,7 +277,7 @@ __global__ __launch_bounds__(256) void cl_place_kernel(const unsigned char* __re
 // grid as link: every point to its place; the link kinds, the widths and the largest d2 to the branch rows
 __global__ __launch_bounds__(256) void cl_emit_kernel(const unsigned char* __restrict__ lmask, const int* __restrict__ hbase,
                                                       const u32* __restrict__ hkey, const u64* __restrict__ mh,
-                                                      const int* __restrict__ d2, const int* __restrict__ hcount, LinkBuf info,
+                                                      const int* __restrict__ d2, const int* __restrict__ hcount, ChainBuf info,
                                                       long long* __restrict__ branches, int max_branches, int* __restrict__ points,
                                                       long long max_points, int W, int P, size_t hcap) {
     const Graph g{lmask + (size_t)blockIdx.y * P, hbase + (size_t)blockIdx.y * P, hkey + (size_t)blockIdx.y * hcap, W};
@@ -448,29 +371,22 @@ __global__ __launch_bounds__(256) void cl_emit_kernel(const unsigned char* __res
     }
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool shape_ok(int n, int H, int W) {
     return n >= 1 && n <= CL_MAX_BATCH && H >= 1 && H <= CL_MAX_SIDE && W >= 1 && W <= CL_MAX_SIDE && (long long)H * W < (1ll << 29);
 }
 
-struct Layout {   // the thinning's scratch, then the byte planes, the pixel words and the half-link arrays
-    size_t X, comp, skel, lmask, d2, maxw, hbase, hcount, changed, ptot, ltot, hkey, nxt0, nxt[2], mh[2], total;
-    size_t thin_bytes;
-    size_t hcap;   // half-links an image can have: four per pixel
-    int ncp, nhc, rounds;
+struct Layout {   // the thinning's scratch, then the byte planes, the pixel words, the half-link keys and the chain scratch
+    size_t X, comp, skel, lmask, d2, maxw, hbase, hcount, ptot, ltot, hkey, chain_at, total;
+    ChainLayout chain;   // of the half-links: an image can have four per pixel
+    int ncp;
 };
 
 // thin_bytes: skeleton_scratch_bytes(n, H, W, route), not 0
 Layout layout(int n, int H, int W, size_t thin_bytes) {
     Layout l{};
     const size_t P = (size_t)H * W;
-    l.thin_bytes = thin_bytes;
-    l.hcap = 4 * P;
+    l.chain = chain_layout(n, 4 * P);
     l.ncp = (int)((P + CHUNK - 1) / CHUNK);
-    l.nhc = (int)((l.hcap + CHUNK - 1) / CHUNK);
-    l.rounds = 1;
-    while (((size_t)1 << l.rounds) < l.hcap) ++l.rounds;
     size_t o = up256(thin_bytes);
     l.X = o;        o += up256((size_t)n * P);
     l.comp = o;     o += up256((size_t)n * P);
@@ -480,15 +396,10 @@ Layout layout(int n, int H, int W, size_t thin_bytes) {
     l.maxw = o;     o += up256((size_t)n * 2 * sizeof(int));
     l.hbase = o;    o += up256((size_t)n * P * sizeof(int));
     l.hcount = o;   o += up256((size_t)n * sizeof(int));
-    l.changed = o;  o += up256((size_t)n * l.rounds * sizeof(int));
     l.ptot = o;     o += up256((size_t)n * l.ncp * 2 * sizeof(int));
-    l.ltot = o;     o += up256((size_t)n * l.nhc * 2 * sizeof(int));
-    l.hkey = o;     o += up256((size_t)n * l.hcap * sizeof(u32));
-    l.nxt0 = o;     o += up256((size_t)n * l.hcap * sizeof(int));
-    for (int i = 0; i < 2; ++i) {
-        l.nxt[i] = o;  o += up256((size_t)n * l.hcap * sizeof(int));
-        l.mh[i] = o;   o += up256((size_t)n * l.hcap * sizeof(u64));
-    }
+    l.ltot = o;     o += up256((size_t)n * l.chain.nchunks * 2 * sizeof(int));
+    l.hkey = o;     o += up256((size_t)n * l.chain.cap * sizeof(u32));
+    l.chain_at = o; o += l.chain.bytes;
     l.total = o;
     return l;
 }
@@ -532,20 +443,18 @@ int launch_centerlines(const unsigned char* mask, int n, int H, int W, int value
     int* maxw = (int*)(base + l.maxw);
     int* hbase = (int*)(base + l.hbase);
     int* hcount = (int*)(base + l.hcount);
-    int* changed = (int*)(base + l.changed);
     int* ptot = (int*)(base + l.ptot);
     int* ltot = (int*)(base + l.ltot);
     u32* hkey = (u32*)(base + l.hkey);
-    int* nxt0 = (int*)(base + l.nxt0);
-    const LinkBuf buf[2] = {{(int*)(base + l.nxt[0]), (u64*)(base + l.mh[0])}, {(int*)(base + l.nxt[1]), (u64*)(base + l.mh[1])}};
-    const int P = H * W;
-    hipError_t e = hipMemsetAsync(changed, 0, (size_t)n * l.rounds * sizeof(int), s);
-    if (e == hipSuccess) e = hipMemsetAsync(maxw, 0, (size_t)n * 2 * sizeof(int), s);
+    const ChainScratch c = chain_scratch(base + l.chain_at, l.chain);
+    const size_t hcap = l.chain.cap;
+    const int P = H * W, nhc = l.chain.nchunks;
+    hipError_t e = hipMemsetAsync(maxw, 0, (size_t)n * 2 * sizeof(int), s);
     if (e == hipSuccess && max_nodes > 0) e = hipMemsetAsync(nodes, 0, (size_t)n * max_nodes * 4 * sizeof(int), s);
     if (e == hipSuccess && max_branches > 0) e = hipMemsetAsync(branches, 0, (size_t)n * max_branches * 9 * sizeof(long long), s);
     if (e == hipSuccess && max_points > 0) e = hipMemsetAsync(points, 0, (size_t)n * (size_t)max_points * 3 * sizeof(int), s);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(centerlines)");
-    const dim3 pgrid(l.ncp, n), hgrid(l.nhc, n), sgrid((unsigned)(l.nhc < JUMP_BLOCKS ? l.nhc : JUMP_BLOCKS), n);
+    const dim3 pgrid(l.ncp, n), hgrid(nhc, n), sgrid = chain_grid(l.chain);
     hipLaunchKernelGGL(cl_planes_kernel, pgrid, dim3(256), 0, s, mask, X, comp, P, value);
     VITSEG_LAUNCH_CHECK("centerlines planes");
     if (thin)
@@ -553,32 +462,22 @@ int launch_centerlines(const unsigned char* mask, int n, int H, int W, int value
     if (const int rc = launch_sdf_d2(comp, n, H, W, d2, maxw, s)) return rc;
     hipLaunchKernelGGL(cl_count_kernel, pgrid, dim3(256), 0, s, skel, lmask, ptot, H, W, P, l.ncp);
     VITSEG_LAUNCH_CHECK("centerlines count");
-    hipLaunchKernelGGL(cl_scan_kernel, dim3(n, 2), dim3(256), 0, s, ptot, l.ncp,
-                       ScanOut{{hcount, node_counts}, {nullptr, nullptr}});
-    VITSEG_LAUNCH_CHECK("centerlines scan");
+    if (const int rc = launch_chunk_scan(ptot, n, l.ncp, 2, ScanOut{{hcount, node_counts}, {nullptr, nullptr}}, s)) return rc;
     hipLaunchKernelGGL(cl_build_kernel, pgrid, dim3(256), 0, s, skel, lmask, d2, ptot, hbase, hkey, nodes, max_nodes, W, P, l.ncp,
-                       l.hcap);
+                       hcap);
     VITSEG_LAUNCH_CHECK("centerlines build");
-    hipLaunchKernelGGL(cl_link_kernel, sgrid, dim3(256), 0, s, lmask, hbase, hkey, hcount, nxt0, buf[0], W, P, l.hcap);
+    hipLaunchKernelGGL(cl_link_kernel, sgrid, dim3(256), 0, s, lmask, hbase, hkey, hcount, c.nxt0, c.buf[0], W, P, hcap);
     VITSEG_LAUNCH_CHECK("centerlines link");
-    for (int r = 0; r < l.rounds; ++r) {
-        hipLaunchKernelGGL(cl_jump_kernel, sgrid, dim3(256), 0, s, buf[r & 1], buf[(r + 1) & 1], hcount, changed, l.hcap, r,
-                           l.rounds);
-        VITSEG_LAUNCH_CHECK("centerlines jump");
-    }
-    // after a round that changed nothing both sides hold the same (word, hops); the other side's words are free
-    const LinkBuf fin = buf[l.rounds & 1], info = buf[(l.rounds + 1) & 1];
-    hipLaunchKernelGGL(cl_leaders_kernel, hgrid, dim3(256), 0, s, lmask, hbase, hkey, fin.mh, nxt0, hcount, ltot, W, P, l.hcap,
-                       l.nhc);
+    ChainBuf fin, info;   // (word, hops) of every half-link; the other side, free for what place tells emit
+    if (const int rc = launch_chain_jumps(l.chain, c, hcount, &fin, &info, s)) return rc;
+    hipLaunchKernelGGL(cl_leaders_kernel, hgrid, dim3(256), 0, s, lmask, hbase, hkey, fin.mh, c.nxt0, hcount, ltot, W, P, hcap, nhc);
     VITSEG_LAUNCH_CHECK("centerlines leaders");
-    hipLaunchKernelGGL(cl_scan_kernel, dim3(n, 2), dim3(256), 0, s, ltot, l.nhc,
-                       ScanOut{{branch_counts, nullptr}, {nullptr, point_counts}});
-    VITSEG_LAUNCH_CHECK("centerlines branch scan");
-    hipLaunchKernelGGL(cl_place_kernel, hgrid, dim3(256), 0, s, lmask, hbase, hkey, fin.mh, nxt0, hcount, ltot, info, branches,
-                       max_branches, W, P, l.hcap, l.nhc);
+    if (const int rc = launch_chunk_scan(ltot, n, nhc, 2, ScanOut{{branch_counts, nullptr}, {nullptr, point_counts}}, s)) return rc;
+    hipLaunchKernelGGL(cl_place_kernel, hgrid, dim3(256), 0, s, lmask, hbase, hkey, fin.mh, c.nxt0, hcount, ltot, info, branches,
+                       max_branches, W, P, hcap, nhc);
     VITSEG_LAUNCH_CHECK("centerlines place");
     hipLaunchKernelGGL(cl_emit_kernel, sgrid, dim3(256), 0, s, lmask, hbase, hkey, fin.mh, d2, hcount, info, branches,
-                       max_branches, points, max_points, W, P, l.hcap);
+                       max_branches, points, max_points, W, P, hcap);
     VITSEG_LAUNCH_CHECK("centerlines emit");
     return VITSEG_OK;
 }

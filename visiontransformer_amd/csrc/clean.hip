@@ -27,11 +27,6 @@ constexpr int CHUNK = 4096;   // pixels per block of the two passes that count
 
 enum { REGIONS_REMOVED, PIXELS_REMOVED, HOLES_FILLED, PIXELS_FILLED, HOLES_MIXED, HOLES_OVER_AREA, NSTATS = 8 };
 
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // the block's sum of v goes to one counter of its image by a single integer atomicAdd (integer sums: any order gives the
 // same bits; one atomic per block and counter keeps thousands of waves off the same few words)
 __device__ __forceinline__ void add_stat(int* stats, int which, int v, int* part /* LDS, one int per wave */) {
@@ -153,14 +148,12 @@ __global__ __launch_bounds__(256) void fill_kernel(unsigned char* out, Holes h, 
     add_stat(stats, HOLES_OVER_AREA, over, part);
 }
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // the labelling's scratch, then one more int32 per pixel (the `hi` words)
 size_t clean_scratch_bytes(int n, int H, int W) {
     if (!regions_shape_ok(n, H, W)) return 0;
-    return align_up(regions_scratch_bytes(n, H, W)) + align_up((size_t)n * H * W * sizeof(int));
+    return up256(regions_scratch_bytes(n, H, W)) + up256((size_t)n * H * W * sizeof(int));
 }
 
 int launch_clean_mask(const unsigned char* mask, unsigned char* out, int n, int H, int W, int connectivity, int background,
@@ -179,7 +172,7 @@ int launch_clean_mask(const unsigned char* mask, unsigned char* out, int n, int 
     const size_t need = clean_scratch_bytes(n, H, W);
     VITSEG_CHECK_ARG(scratch_bytes >= need, VITSEG_EWORKSPACE, "clean_mask: scratch of %zu bytes, %zu needed", scratch_bytes, need);
     const RegionWords w = region_words(scratch, n, H, W);
-    int* hi = (int*)((char*)scratch + align_up(regions_scratch_bytes(n, H, W)));
+    int* hi = (int*)((char*)scratch + up256(regions_scratch_bytes(n, H, W)));
     const int P = H * W;
     const size_t N = (size_t)n * P;
     const dim3 grid((unsigned)(((long long)P + 255) / 256), n), chunks((unsigned)(((long long)P + CHUNK - 1) / CHUNK), n);

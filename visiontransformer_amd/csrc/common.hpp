@@ -55,6 +55,9 @@ long opt(int id);
         if (e__ != hipSuccess) return ::vitseg::hip_fail(e__, what); \
     } while (0)
 
+// every array of a scratch layout starts on a multiple of 256 bytes
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
 // Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Give each
 // XCD a contiguous run of the logical tile list so neighbouring tiles (which share
 // operand panels) hit the same L2.  Bijective for any grid size.
@@ -226,6 +229,11 @@ __device__ __forceinline__ float wave_sum(float v) { return v; }
 __device__ __forceinline__ float row16_sum(float v) { return v; }
 __device__ __forceinline__ float wave_max(float v) { return v; }
 #endif
+// integer sum over the 64 lanes of a wave, on every lane (the post-processing kernels' counts: a few calls per workgroup)
+__device__ __forceinline__ int wave_sum(int v) {
+    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
 
 // exact (erf) GELU, activations.py:78-83:  gelu(u) = u Phi(u),  Phi(u) = (1 + erf(u / sqrt 2)) / 2.
 // Evaluated through the COMPLEMENTARY error function of a = |u| / sqrt 2,  erfc(a) = 2^(-a Q(a)):

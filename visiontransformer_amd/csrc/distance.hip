@@ -33,8 +33,6 @@ struct Layout {
     int NB;
 };
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 Layout layout(int n, int H, int W) {
     Layout l;
     const size_t P = (size_t)H * W, M = 2 * (size_t)n;
@@ -53,11 +51,6 @@ Layout layout(int n, int H, int W) {
 
 bool shape_ok(int n, int H, int W) {
     return n >= 1 && n <= DIST_MAX_BATCH && H >= 1 && H <= DIST_MAX_SIDE && W >= 1 && W <= DIST_MAX_SIDE;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 __device__ __forceinline__ bool is_border(const unsigned char* m, int c, int y, int x, int H, int W) {

@@ -190,8 +190,6 @@ __global__ __launch_bounds__(256) void roots_kernel(const unsigned char* __restr
     flush_sums(acc, stats, K, N_GT, N_PRED, GT_FOUND, PRED_CONFIRMED);
 }
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool shape_ok(int n, int H, int W) { return n > 0 && n <= 32767 && regions_shape_ok(2 * n, H, W); }
 
 struct Layout {   // the labelling's scratch for 2n planes, the staged planes, the pair table
@@ -201,10 +199,10 @@ struct Layout {   // the labelling's scratch for 2n planes, the staged planes, t
 Layout layout(int n, int H, int W) {
     Layout l{};
     const size_t N = (size_t)n * H * W;
-    l.planes = align_up(regions_scratch_bytes(2 * n, H, W));
-    l.keys = l.planes + align_up(2 * N);
-    l.counts = l.keys + align_up(2 * N * sizeof(u64));
-    l.total = l.counts + align_up(2 * N * sizeof(int));
+    l.planes = up256(regions_scratch_bytes(2 * n, H, W));
+    l.keys = l.planes + up256(2 * N);
+    l.counts = l.keys + up256(2 * N * sizeof(u64));
+    l.total = l.counts + up256(2 * N * sizeof(int));
     return l;
 }
 

@@ -9,52 +9,27 @@
 // corner alone (corner_mask), so nothing but the label plane is kept per pixel.
 //   (labels)     tile_label, seam_merge, resolve, class_scan, emit, labels of regions.hip
 //   count        one thread per corner: the number of vertex edges leaving it; totals per chunk of 1024 corners
-//   scan         one workgroup per image: exclusive scan of the chunk totals; the image's vertex count
+//   (scan)       chunk scan of chains.hip, one workgroup per image: exclusive scan of the chunk totals; the image's vertex count
 //   build        per corner: the index of its first node (scan within the chunk + the chunk's base); every node's key.
 //                Nodes are therefore numbered in key order, and a ring's start edge is its smallest node
 //   link         per node: walks the straight run to its end, takes the turn there and looks the next node up
-//   jump x R     pointer jumping over the cyclic lists, R = ceil(log2(4 H W)) rounds: after round j a node knows the smallest
-//                node among the 2^(j+1) from itself on and how many hops ahead it lies.  A round that changed nothing leaves
-//                a zero in its word of `changed`; the rounds after it return at once (the host never reads that word)
+//   (jump x R)   chain jumps of chains.hip over the cyclic lists, R = ceil(log2(4 H W)) rounds: after round j a node knows the
+//                smallest node among the 2^(j+1) from itself on and how many hops ahead it lies.  A round that changed nothing
+//                leaves a zero in its word of `changed`; the rounds after it return at once (the host never reads that word)
 //   rings        per node chunk: the number of leaders (nodes that are their ring's smallest) and of their rings' vertices
-//   scan         exclusive scan of both over the chunks: ring numbers and vertex offsets in key order; the ring count
+//   (scan)       exclusive scan of both over the chunks: ring numbers and vertex offsets in key order; the ring count
 //   place        per leader: its ring's row (region, offset, count) and, for its ring's nodes, the ring number and offset
 //   emit         per node: rank = hops from the leader; the vertex goes to offset + rank; a node going S or N adds
 //                x * (y_next - y) to its ring's area (the shoelace sum, taken over the vertical sides: each term an integer)
 // Every value is an integer; the only atomics are the area sums (order-independent) and the `changed` flags.
+#include "chains.hpp"
 #include "kernels.hpp"
 #include "../../include/vitseg_polygons.h"
 
 namespace vitseg {
 namespace {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
 constexpr int POLY_MAX_SIDE = 16384;
-constexpr int CCHUNK = 1024;     // corners (count, build) or nodes (rings, place) per workgroup: 4 per thread
-constexpr int JUMP_BLOCKS = 1024;   // workgroups per image of the node-strided launches (link, jump, emit)
-
-// exclusive scan of one int per thread over a 256-thread workgroup; total: the sum of all.  Whole workgroups call it.
-__device__ __forceinline__ int block_scan(int v, int* wsum /* shared [4] */, int& total) {
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    int inc = v;
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();   // the words may still be read from the call before
-    if (lane == WAVE - 1) wsum[wave] = inc;
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int w = 0; w < 4; ++w) {
-        const int s = wsum[w];
-        if (w < wave) before += s;
-        tot += s;
-    }
-    total = tot;
-    return before + inc - v;
-}
 
 __device__ __forceinline__ int label_at(const int* __restrict__ lab, int y, int x, int H, int W) {
     return (y >= 0 && y < H && x >= 0 && x < W) ? lab[y * W + x] : -1;
@@ -81,8 +56,8 @@ __global__ __launch_bounds__(256) void poly_count_kernel(const int* __restrict__
     __shared__ int wsum[4];
     const int* lab = labels + (size_t)blockIdx.y * H * W;
     int cnt = 0;
-    for (int k = 0; k < CCHUNK / 256; ++k) {
-        const long long i = (long long)blockIdx.x * CCHUNK + k * 256 + threadIdx.x;
+    for (int k = 0; k < CHUNK / 256; ++k) {
+        const long long i = (long long)blockIdx.x * CHUNK + k * 256 + threadIdx.x;
         if (i < C) {
             const int y = (int)(i / (W + 1)), x = (int)(i - (long long)y * (W + 1));
             cnt += __popc(corner_mask(lab, y, x, H, W));
@@ -91,28 +66,6 @@ __global__ __launch_bounds__(256) void poly_count_kernel(const int* __restrict__
     int total;
     block_scan(cnt, wsum, total);
     if (threadIdx.x == 0) ctot[(size_t)blockIdx.y * ncc + blockIdx.x] = total;
-}
-
-// grid (n, fields): tot[image][chunk][field] becomes its exclusive scan over the chunks; the sum goes to total32 / total64
-// (either may be null) at [image] for field `out_field`
-__global__ __launch_bounds__(256) void poly_scan_kernel(int* __restrict__ tot, int nchunks, int fields, int out_field,
-                                                        int* __restrict__ total32, long long* __restrict__ total64) {
-    __shared__ int wsum[4];
-    const int f = blockIdx.y;
-    int* t = tot + (size_t)blockIdx.x * nchunks * fields + f;
-    int carry = 0;
-    for (int b0 = 0; b0 < nchunks; b0 += 256) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nchunks ? t[(size_t)b * fields] : 0;
-        int total;
-        const int ex = block_scan(v, wsum, total);
-        if (b < nchunks) t[(size_t)b * fields] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0 && f == out_field) {
-        if (total32) total32[blockIdx.x] = carry;
-        if (total64) total64[blockIdx.x] = carry;
-    }
 }
 
 // grid (ceil(C / 1024), n): cbase[corner] = index of the corner's first node; nkey[node] = 4 * corner + direction
@@ -124,8 +77,8 @@ __global__ __launch_bounds__(256) void poly_build_kernel(const int* __restrict__
     int* cb = cbase + (size_t)blockIdx.y * C;
     u32* nk = nkey + (size_t)blockIdx.y * ncap;
     int carry = ctot[(size_t)blockIdx.y * ncc + blockIdx.x];
-    for (int k = 0; k < CCHUNK / 256; ++k) {
-        const long long i = (long long)blockIdx.x * CCHUNK + k * 256 + threadIdx.x;
+    for (int k = 0; k < CHUNK / 256; ++k) {
+        const long long i = (long long)blockIdx.x * CHUNK + k * 256 + threadIdx.x;
         int m = 0;
         if (i < C) {
             const int y = (int)(i / (W + 1)), x = (int)(i - (long long)y * (W + 1));
@@ -145,15 +98,10 @@ __global__ __launch_bounds__(256) void poly_build_kernel(const int* __restrict__
 __device__ __forceinline__ int dir_y(int d) { return (d == 1) - (d == 3); }   // the step of E, S, W, N
 __device__ __forceinline__ int dir_x(int d) { return (d == 0) - (d == 2); }
 
-struct NodeBuf {   // one side of the pointer jumping: where the node's window ends, (smallest node in it) << 32 | hops to it
-    int* nxt;
-    u64* mh;
-};
-
 // grid (JUMP_BLOCKS or fewer, n), node-strided: the node after this one on its ring
 __global__ __launch_bounds__(256) void poly_link_kernel(const int* __restrict__ labels, const int* __restrict__ cbase,
                                                         const u32* __restrict__ nkey, const int* __restrict__ ncount,
-                                                        int* __restrict__ nxt0, NodeBuf out, int H, int W, int C, size_t ncap,
+                                                        int* __restrict__ nxt0, ChainBuf out, int H, int W, int C, size_t ncap,
                                                         int conn8) {
     const int* lab = labels + (size_t)blockIdx.y * H * W;
     const int* cb = cbase + (size_t)blockIdx.y * C;
@@ -192,28 +140,6 @@ __global__ __launch_bounds__(256) void poly_link_kernel(const int* __restrict__ 
     }
 }
 
-// grid as link: one round of pointer jumping, in -> out
-__global__ __launch_bounds__(256) void poly_jump_kernel(NodeBuf in, NodeBuf out, const int* __restrict__ ncount,
-                                                        int* __restrict__ changed, size_t ncap, int round, int rounds) {
-    int* flags = changed + (size_t)blockIdx.y * rounds;
-    if (round > 0 && flags[round - 1] == 0) return;   // the whole launch: the word was written by the launch before
-    const size_t nb = (size_t)blockIdx.y * ncap;
-    const int cnt = ncount[blockIdx.y];
-    bool any = false;
-    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < cnt; v += (long long)gridDim.x * 256) {
-        const int j = in.nxt[nb + v];
-        u64 mine = in.mh[nb + v];
-        const u64 theirs = in.mh[nb + j];
-        if ((theirs >> 32) < (mine >> 32)) {
-            mine = (theirs & 0xffffffff00000000ull) | ((theirs & 0xffffffffull) + (1ull << round));
-            any = true;
-        }
-        out.nxt[nb + v] = in.nxt[nb + j];
-        out.mh[nb + v] = mine;
-    }
-    if (__syncthreads_or(any) && threadIdx.x == 0) atomicOr(&flags[round], 1);
-}
-
 // leader test and ring length of node v (length: hops from the node after the leader back to it, plus one)
 __device__ __forceinline__ int ring_len(const u64* __restrict__ mh, const int* __restrict__ nxt0, long long v) {
     if ((long long)(mh[v] >> 32) != v) return 0;
@@ -229,7 +155,7 @@ __global__ __launch_bounds__(256) void poly_rings_kernel(const u64* __restrict__
     const int cnt = ncount[blockIdx.y];
     int leaders = 0, verts = 0;
     for (int k = 0; k < 4; ++k) {
-        const long long v = (long long)blockIdx.x * CCHUNK + threadIdx.x * 4 + k;
+        const long long v = (long long)blockIdx.x * CHUNK + threadIdx.x * 4 + k;
         if (v < cnt) {
             const int len = ring_len(mh + nb, nxt0 + nb, v);
             leaders += len > 0;
@@ -251,7 +177,7 @@ __global__ __launch_bounds__(256) void poly_rings_kernel(const u64* __restrict__
 __global__ __launch_bounds__(256) void poly_place_kernel(const int* __restrict__ labels, const u32* __restrict__ nkey,
                                                          const u64* __restrict__ mh, const int* __restrict__ nxt0,
                                                          const int* __restrict__ ncount, const int* __restrict__ ntot,
-                                                         NodeBuf info, long long* __restrict__ rings, int max_rings, int H, int W,
+                                                         ChainBuf info, long long* __restrict__ rings, int max_rings, int H, int W,
                                                          size_t ncap, int nnc) {
     __shared__ int wsum[4];
     const size_t nb = (size_t)blockIdx.y * ncap;
@@ -259,7 +185,7 @@ __global__ __launch_bounds__(256) void poly_place_kernel(const int* __restrict__
     const int cnt = ncount[blockIdx.y];
     int len[4], leaders = 0, verts = 0;
     for (int k = 0; k < 4; ++k) {
-        const long long v = (long long)blockIdx.x * CCHUNK + threadIdx.x * 4 + k;
+        const long long v = (long long)blockIdx.x * CHUNK + threadIdx.x * 4 + k;
         len[k] = v < cnt ? ring_len(mh + nb, nxt0 + nb, v) : 0;
         leaders += len[k] > 0;
         verts += len[k];
@@ -270,7 +196,7 @@ __global__ __launch_bounds__(256) void poly_place_kernel(const int* __restrict__
     int off = t[1] + block_scan(verts, wsum, total);
     for (int k = 0; k < 4; ++k) {
         if (len[k] == 0) continue;
-        const long long v = (long long)blockIdx.x * CCHUNK + threadIdx.x * 4 + k;
+        const long long v = (long long)blockIdx.x * CHUNK + threadIdx.x * 4 + k;
         const u32 key = nkey[nb + v];   // a ring starts going E or S: at the top side of pixel (y, x) or the right side of (y, x - 1)
         const int corner = (int)(key >> 2), y = corner / (W + 1), x = corner - y * (W + 1);
         info.nxt[nb + v] = off;
@@ -288,7 +214,7 @@ __global__ __launch_bounds__(256) void poly_place_kernel(const int* __restrict__
 
 // grid as link: every node's vertex to its place, the vertical sides' terms to their ring's area
 __global__ __launch_bounds__(256) void poly_emit_kernel(const u32* __restrict__ nkey, const u64* __restrict__ mh,
-                                                        const int* __restrict__ nxt0, const int* __restrict__ ncount, NodeBuf info,
+                                                        const int* __restrict__ nxt0, const int* __restrict__ ncount, ChainBuf info,
                                                         long long* __restrict__ rings, int max_rings, int* __restrict__ vertices,
                                                         long long max_vertices, int W, size_t ncap) {
     const size_t nb = (size_t)blockIdx.y * ncap;
@@ -314,40 +240,30 @@ __global__ __launch_bounds__(256) void poly_emit_kernel(const u32* __restrict__ 
     }
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool shape_ok(int n, int H, int W) {
     return n >= 1 && n <= 65535 && H >= 1 && H <= POLY_MAX_SIDE && W >= 1 && W <= POLY_MAX_SIDE && (long long)H * W < (1ll << 29);
 }
 
-struct Layout {   // the labelling's scratch, then the label plane, the corner words and the node arrays
-    size_t labels, ncount, changed, ctot, ntot, cbase, nkey, nxt0, nxt[2], mh[2], total;
-    size_t ncap;   // nodes an image can have: every side of every pixel
-    int C, ncc, nnc, rounds;
+struct Layout {   // the labelling's scratch, then the label plane, the corner words, the node keys and the chain scratch
+    size_t labels, ncount, ctot, ntot, cbase, nkey, chain_at, total;
+    ChainLayout chain;   // of the nodes: an image can have 4 H W, every side of every pixel
+    int C, ncc;
 };
 
 Layout layout(int n, int H, int W) {
     Layout l{};
     const size_t P = (size_t)H * W;
-    l.ncap = 4 * P;
+    l.chain = chain_layout(n, 4 * P);
     l.C = (H + 1) * (W + 1);
-    l.ncc = (l.C + CCHUNK - 1) / CCHUNK;
-    l.nnc = (int)((l.ncap + CCHUNK - 1) / CCHUNK);
-    l.rounds = 1;
-    while (((size_t)1 << l.rounds) < l.ncap) ++l.rounds;
+    l.ncc = (l.C + CHUNK - 1) / CHUNK;
     size_t o = up256(regions_scratch_bytes(n, H, W));
-    l.labels = o;   o += up256((size_t)n * P * sizeof(int));
-    l.ncount = o;   o += up256((size_t)n * sizeof(int));
-    l.changed = o;  o += up256((size_t)n * l.rounds * sizeof(int));
-    l.ctot = o;     o += up256((size_t)n * l.ncc * sizeof(int));
-    l.ntot = o;     o += up256((size_t)n * l.nnc * 2 * sizeof(int));
-    l.cbase = o;    o += up256((size_t)n * l.C * sizeof(int));
-    l.nkey = o;     o += up256((size_t)n * l.ncap * sizeof(u32));
-    l.nxt0 = o;     o += up256((size_t)n * l.ncap * sizeof(int));
-    for (int i = 0; i < 2; ++i) {
-        l.nxt[i] = o;  o += up256((size_t)n * l.ncap * sizeof(int));
-        l.mh[i] = o;   o += up256((size_t)n * l.ncap * sizeof(u64));
-    }
+    l.labels = o;    o += up256((size_t)n * P * sizeof(int));
+    l.ncount = o;    o += up256((size_t)n * sizeof(int));
+    l.ctot = o;      o += up256((size_t)n * l.ncc * sizeof(int));
+    l.ntot = o;      o += up256((size_t)n * l.chain.nchunks * 2 * sizeof(int));
+    l.cbase = o;     o += up256((size_t)n * l.C * sizeof(int));
+    l.nkey = o;      o += up256((size_t)n * l.chain.cap * sizeof(u32));
+    l.chain_at = o;  o += l.chain.bytes;
     l.total = o;
     return l;
 }
@@ -378,51 +294,42 @@ int launch_region_polygons(const unsigned char* mask, int n, int H, int W, int c
     const RegionWords w = region_words(scratch, n, H, W);
     int* lab = labels ? labels : (int*)(base + l.labels);
     int* ncount = (int*)(base + l.ncount);
-    int* changed = (int*)(base + l.changed);
     int* ctot = (int*)(base + l.ctot);
     int* ntot = (int*)(base + l.ntot);
     int* cbase = (int*)(base + l.cbase);
     u32* nkey = (u32*)(base + l.nkey);
-    int* nxt0 = (int*)(base + l.nxt0);
-    const NodeBuf buf[2] = {{(int*)(base + l.nxt[0]), (u64*)(base + l.mh[0])}, {(int*)(base + l.nxt[1]), (u64*)(base + l.mh[1])}};
-    hipError_t e = hipMemsetAsync(changed, 0, (size_t)n * l.rounds * sizeof(int), s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(region_polygons flags)");
+    const ChainScratch c = chain_scratch(base + l.chain_at, l.chain);
+    const size_t ncap = l.chain.cap;
+    const int nnc = l.chain.nchunks;
     if (max_rings > 0) {
-        e = hipMemsetAsync(rings, 0, (size_t)n * max_rings * 4 * sizeof(long long), s);
+        const hipError_t e = hipMemsetAsync(rings, 0, (size_t)n * max_rings * 4 * sizeof(long long), s);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(region_polygons rings)");
     }
     if (max_vertices > 0) {
-        e = hipMemsetAsync(vertices, 0, (size_t)n * (size_t)max_vertices * 2 * sizeof(int), s);
+        const hipError_t e = hipMemsetAsync(vertices, 0, (size_t)n * (size_t)max_vertices * 2 * sizeof(int), s);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(region_polygons vertices)");
     }
     if (const int rc = launch_region_labels(mask, n, H, W, connectivity, background, w, s)) return rc;
     if (const int rc = launch_region_index(mask, n, H, W, w, region_counts, nullptr, 0, lab, s)) return rc;
-    const dim3 cgrid(l.ncc, n), ngrid(l.nnc, n), sgrid((unsigned)(l.nnc < JUMP_BLOCKS ? l.nnc : JUMP_BLOCKS), n);
+    const dim3 cgrid(l.ncc, n), ngrid(nnc, n), sgrid = chain_grid(l.chain);
     hipLaunchKernelGGL(poly_count_kernel, cgrid, dim3(256), 0, s, lab, ctot, H, W, l.C, l.ncc);
     VITSEG_LAUNCH_CHECK("region_polygons count");
-    hipLaunchKernelGGL(poly_scan_kernel, dim3(n, 1), dim3(256), 0, s, ctot, l.ncc, 1, 0, ncount, vertex_counts);
-    VITSEG_LAUNCH_CHECK("region_polygons scan");
-    hipLaunchKernelGGL(poly_build_kernel, cgrid, dim3(256), 0, s, lab, ctot, cbase, nkey, H, W, l.C, l.ncc, l.ncap);
+    if (const int rc = launch_chunk_scan(ctot, n, l.ncc, 1, ScanOut{{ncount, nullptr}, {vertex_counts, nullptr}}, s)) return rc;
+    hipLaunchKernelGGL(poly_build_kernel, cgrid, dim3(256), 0, s, lab, ctot, cbase, nkey, H, W, l.C, l.ncc, ncap);
     VITSEG_LAUNCH_CHECK("region_polygons build");
-    hipLaunchKernelGGL(poly_link_kernel, sgrid, dim3(256), 0, s, lab, cbase, nkey, ncount, nxt0, buf[0], H, W, l.C, l.ncap,
+    hipLaunchKernelGGL(poly_link_kernel, sgrid, dim3(256), 0, s, lab, cbase, nkey, ncount, c.nxt0, c.buf[0], H, W, l.C, ncap,
                        connectivity == 8);
     VITSEG_LAUNCH_CHECK("region_polygons link");
-    for (int r = 0; r < l.rounds; ++r) {
-        hipLaunchKernelGGL(poly_jump_kernel, sgrid, dim3(256), 0, s, buf[r & 1], buf[(r + 1) & 1], ncount, changed, l.ncap, r,
-                           l.rounds);
-        VITSEG_LAUNCH_CHECK("region_polygons jump");
-    }
-    // after a round that changed nothing both sides hold the same (smallest node, hops); the other side's words are free
-    const NodeBuf fin = buf[l.rounds & 1], info = buf[(l.rounds + 1) & 1];
-    hipLaunchKernelGGL(poly_rings_kernel, ngrid, dim3(256), 0, s, fin.mh, nxt0, ncount, ntot, l.ncap, l.nnc);
+    ChainBuf fin, info;   // (smallest node, hops) of every node; the other side, free for what place tells emit
+    if (const int rc = launch_chain_jumps(l.chain, c, ncount, &fin, &info, s)) return rc;
+    hipLaunchKernelGGL(poly_rings_kernel, ngrid, dim3(256), 0, s, fin.mh, c.nxt0, ncount, ntot, ncap, nnc);
     VITSEG_LAUNCH_CHECK("region_polygons rings");
-    hipLaunchKernelGGL(poly_scan_kernel, dim3(n, 2), dim3(256), 0, s, ntot, l.nnc, 2, 0, ring_counts, (long long*)nullptr);
-    VITSEG_LAUNCH_CHECK("region_polygons ring scan");
-    hipLaunchKernelGGL(poly_place_kernel, ngrid, dim3(256), 0, s, lab, nkey, fin.mh, nxt0, ncount, ntot, info, rings, max_rings, H,
-                       W, l.ncap, l.nnc);
+    if (const int rc = launch_chunk_scan(ntot, n, nnc, 2, ScanOut{{ring_counts, nullptr}, {nullptr, nullptr}}, s)) return rc;
+    hipLaunchKernelGGL(poly_place_kernel, ngrid, dim3(256), 0, s, lab, nkey, fin.mh, c.nxt0, ncount, ntot, info, rings, max_rings,
+                       H, W, ncap, nnc);
     VITSEG_LAUNCH_CHECK("region_polygons place");
-    hipLaunchKernelGGL(poly_emit_kernel, sgrid, dim3(256), 0, s, nkey, fin.mh, nxt0, ncount, info, rings, max_rings, vertices,
-                       max_vertices, W, l.ncap);
+    hipLaunchKernelGGL(poly_emit_kernel, sgrid, dim3(256), 0, s, nkey, fin.mh, c.nxt0, ncount, info, rings, max_rings, vertices,
+                       max_vertices, W, ncap);
     VITSEG_LAUNCH_CHECK("region_polygons emit");
     return VITSEG_OK;
 }

@@ -221,8 +221,6 @@ __global__ __launch_bounds__(256) void props_class_kernel(const unsigned char* _
     }
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool shape_ok(int n, int H, int W, int K) {
     return n >= 1 && n <= PROPS_MAX_BATCH && H >= 1 && H <= PROPS_MAX_SIDE && W >= 1 && W <= PROPS_MAX_SIDE && K >= 0 && K <= 256;
 }

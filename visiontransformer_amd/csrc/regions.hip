@@ -307,8 +307,6 @@ __global__ __launch_bounds__(256) void labels_kernel(const int* __restrict__ roo
     labels[base + p] = r < 0 ? -1 : link[base + r];
 }
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Layout {
     size_t link, root, xmin, xmax, ymax, area, counts, offsets, total;
     int nchunks;
@@ -318,7 +316,7 @@ Layout layout(int n, int H, int W) {
     Layout l{};
     const size_t N = (size_t)n * H * W;
     l.nchunks = (int)(((size_t)H * W + CHUNK - 1) / CHUNK);
-    const size_t px = align_up(N * sizeof(int)), cc = align_up((size_t)n * l.nchunks * NCLS * sizeof(int));
+    const size_t px = up256(N * sizeof(int)), cc = up256((size_t)n * l.nchunks * NCLS * sizeof(int));
     l.link = 0;
     l.root = l.link + px;
     l.xmin = l.root + px;

@@ -159,7 +159,7 @@ bool shape_ok(int n, int H, int W) {
     return n >= 1 && n <= 65535 && H >= 1 && H <= SDF_MAX_SIDE && W >= 1 && W <= SDF_MAX_SIDE;
 }
 
-size_t scratch_bytes(int n) { return ((size_t)n * 2 * sizeof(int) + 255) & ~(size_t)255; }
+size_t scratch_bytes(int n) { return up256((size_t)n * 2 * sizeof(int)); }
 
 struct RowPlan {
     int R, Wp;

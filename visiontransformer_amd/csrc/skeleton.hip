@@ -253,8 +253,6 @@ __global__ __launch_bounds__(256) void skel_unpack_kernel(const unsigned* __rest
     }
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool shape_ok(int n, int H, int W) {
     return n >= 1 && n <= SKEL_MAX_BATCH && H >= 1 && H <= SKEL_MAX_SIDE && W >= 1 && W <= SKEL_MAX_SIDE;
 }
