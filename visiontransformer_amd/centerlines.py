@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _ext, _lib
+from . import _common, _ext, _lib
 from .skeleton import MAX_BATCH, MAX_SIDE, ROUTES
 
 MAX_PIXELS = 1 << 29
@@ -38,13 +38,7 @@ def check_options(classes, thin=True, route: str = "auto"):
         return None
     if isinstance(classes, (str, bytes)):
         raise ValueError(f"classes must be None or a sequence of label values, got {classes!r}")
-    classes = list(classes)
-    if not classes or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) <= 255 for c in classes):
-        raise ValueError(f"classes must be label values in 0..255, got {classes}")
-    classes = [int(c) for c in classes]
-    if len(set(classes)) != len(classes):
-        raise ValueError(f"classes must be distinct, got {classes}")
-    return classes
+    return _common.label_values("classes", classes)
 
 
 def _checked(mask, classes, thin, route):
@@ -143,13 +137,6 @@ def trace(mask, classes=None, thin: bool = True, route: str = "auto", device=Non
     return res[0] if single else res
 
 
-def _pixel_size(pixel_size) -> float:
-    ps = float(pixel_size)
-    if not ps > 0 or math.isinf(ps):
-        raise ValueError(f"pixel_size must be a positive finite number, got {pixel_size!r}")
-    return ps
-
-
 def _rows(branches) -> np.ndarray:
     rec = np.asarray(branches)
     if rec.ndim != 2 or rec.shape[1] != len(BRANCH_FIELDS):
@@ -167,7 +154,7 @@ def branch_table(branches, pixel_size: float = 1.0, points=None) -> List[dict]:
                               regions.props_from_records;
       closed, start, end, points   kind == 1, the raster indices of the two ends, the number of points."""
     rec = _rows(branches)
-    ps = _pixel_size(pixel_size)
+    ps = _common.pixel_size(pixel_size)
     if points is not None and len(points) != len(rec):
         raise ValueError(f"{len(rec)} branches for {len(points)} point lists")
     nan = float("nan")
@@ -196,7 +183,7 @@ def summary(nodes, branches, pixel_size: float = 1.0) -> dict:
     if nd.ndim != 2 or nd.shape[1] != len(NODE_FIELDS):
         raise ValueError(f"nodes must be [k, {len(NODE_FIELDS)}], got {nd.shape}")
     rec = _rows(branches)
-    ps = _pixel_size(pixel_size)
+    ps = _common.pixel_size(pixel_size)
     deg = nd[:, 2]
     return {"end_points": int((deg == 1).sum()), "junctions": int((deg >= 3).sum()), "isolated": int((deg == 0).sum()),
             "branches": len(rec), "total_length": (int(rec[:, 5].sum()) + int(rec[:, 6].sum()) * math.sqrt(2.0)) * ps}
@@ -222,7 +209,7 @@ def centerlines_to_geojson(branches, points, *, pixel_size: float = 1.0, image_i
     length, width_mean, width_max (`branch_table`, in units of pixel_size), points, image_id and, with `class_names` and a
     `class_id`, class_name."""
     table = branch_table(branches, pixel_size, points)
-    ps = _pixel_size(pixel_size)
+    ps = _common.pixel_size(pixel_size)
     features = []
     for d, pts in zip(table, points):
         p = np.asarray(pts).reshape(-1, 3)
@@ -254,14 +241,6 @@ def csv_rows(model_info, batch_num, image_idx, class_id, table, summ) -> List[li
     rows.append(head + ["summary"] + [""] * 9 + [summ["end_points"], summ["junctions"], summ["isolated"], summ["branches"],
                                                 summ["total_length"]])
     return rows
-
-
-def write_csv(path: str, rows) -> None:
-    import csv
-    with open(path, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(CSV_COLUMNS)
-        w.writerows(rows)
 
 
 __all__ = ["trace", "branch_table", "summary", "centerlines_to_geojson", "NODE_FIELDS", "BRANCH_FIELDS"]

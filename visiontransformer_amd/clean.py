@@ -21,16 +21,14 @@ import argparse
 import numpy as np
 import torch
 
-from . import _lib
+from . import _common, _lib
 from .regions import _checked
 
 STATS = _lib.CLEAN_STATS
 
 
 def _count(name: str, v) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << 31:
-        raise ValueError(f"{name} must be an integer in 0..2^31 - 1, got {v!r}")
-    return int(v)
+    return _common.integer(name, v, 0, (1 << 31) - 1, "0..2^31 - 1")
 
 
 def check_options(min_area=0, fill_holes=False, max_hole_area=0, connectivity: int = 4, background: int = 0):
@@ -39,10 +37,8 @@ def check_options(min_area=0, fill_holes=False, max_hole_area=0, connectivity: i
     min_area, max_hole_area = _count("min_area", min_area), _count("max_hole_area", max_hole_area)
     if not isinstance(fill_holes, (bool, np.bool_)):
         raise ValueError(f"fill_holes must be a bool, got {fill_holes!r}")
-    if connectivity not in (4, 8):
-        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
-    if isinstance(background, bool) or not isinstance(background, (int, np.integer)) or not 0 <= int(background) <= 255:
-        raise ValueError(f"background must be an integer in 0..255 (clean-up needs a background), got {background!r}")
+    _common.connectivity(connectivity)
+    _common.integer("background", background, 0, 255, "0..255 (clean-up needs a background)")
     return min_area, bool(fill_holes), max_hole_area
 
 

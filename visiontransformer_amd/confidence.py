@@ -13,14 +13,13 @@ host arithmetic on the integers: `scores_from_rows`, `calibration_from_hist`, `a
 """
 from __future__ import annotations
 
-import csv
 import math
 from typing import List, Optional
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _common, _lib
 from . import regions as _regions
 
 KINDS = {"prob": _lib.CONF_PROB, "margin": _lib.CONF_MARGIN}
@@ -131,10 +130,8 @@ def calibration_hist(lowres, mask, gt, bins: int = 16, ignore_label: Optional[in
     3] for a single image), per image and confidence bin (q * bins) >> 16 the (pixels, pixels with mask == gt, sum_q).
     Pixels with gt == ignore_label are void.  Pool images by adding the arrays, then `calibration_from_hist`."""
     lowres, mask, single = _checked(lowres, mask, kind)
-    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= MAX_BINS:
-        raise ValueError(f"bins must be an integer in 1..{MAX_BINS}, got {bins!r}")
-    if ignore_label is not None and (isinstance(ignore_label, bool) or not isinstance(ignore_label, (int, np.integer))
-                                     or not 0 <= int(ignore_label) <= 255):
+    _common.integer("bins", bins, 1, MAX_BINS)
+    if ignore_label is not None and not _common.is_integer(ignore_label, 0, 255):
         raise ValueError(f"ignore_label must be None or an integer in 0..255, got {ignore_label!r}")
     if isinstance(gt, np.ndarray):
         gt = torch.from_numpy(gt)
@@ -236,10 +233,3 @@ def region_dicts(records, rows) -> List[dict]:
     """One dict per region of one image from `region_scores`' pair: class, first, area, score, score_min, low_fraction."""
     return [{"class": int(r[0]), "first": int(r[6]), "area": int(r[5]), "score": d["score"], "score_min": d["score_min"],
              "low_fraction": d["low_fraction"]} for r, d in zip(np.asarray(records), scores_from_rows(rows))]
-
-
-def write_csv(path: str, columns, rows) -> None:
-    with open(path, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(columns)
-        w.writerows(rows)

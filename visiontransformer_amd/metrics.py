@@ -27,7 +27,6 @@ integers, and `pool_region_stats` sums them over a data set first, which is the 
 """
 from __future__ import annotations
 
-import csv
 import ctypes
 import math
 import warnings
@@ -37,7 +36,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _common, _lib
 from .preprocess import NEAREST_PIL, nearest_table
 
 # header of <model>_metrics.csv (datasetTestViTmodel.py:166-171); compareModels.py:27-47 reads these columns
@@ -241,6 +240,13 @@ def pool_region_stats(list_of_stats) -> np.ndarray:
     return sum(p.reshape(-1, *p.shape[-2:]).sum(axis=0) for p in parts)
 
 
+def _class_means(row: Sequence[dict], keys: Sequence[str]) -> Dict[str, float]:
+    """The nan-aware mean over one image's per-class dicts, for every key."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)   # all-nan -> nan, as the overlap means
+        return {key: float(np.nanmean([float(r[key]) for r in row])) for key in keys}
+
+
 class Evaluator:
     """Per-image metrics of uint8 predictions [n, S, S] against label maps of any size, counted on the GPU."""
 
@@ -276,48 +282,53 @@ class Evaluator:
                                                      torch.cuda.current_stream().cuda_stream))
         return out
 
+    @staticmethod
+    def _label_values(classes) -> List[int]:
+        classes = [int(c) for c in classes]
+        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
+            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
+        return classes
+
+    def _device_pair(self, pred: torch.Tensor, gt: torch.Tensor, classes=None, size_only: bool = False):
+        """(pred, gt, classes): the uint8 prediction [n, H, W] and the ground truth validated (then `classes`, when given) and
+        contiguous on the device, the ground truth as uint8 and nearest-resized to the prediction's size when the sizes
+        differ -- one enqueue on the current stream of the device.  size_only: `pred` only states the size and is passed
+        through as it is."""
+        if not size_only and (pred.dtype != torch.uint8 or pred.dim() != 3):
+            raise ValueError(f"pred must be uint8 [n, H, W], got {pred.dtype} {tuple(pred.shape)}")
+        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
+            raise ValueError("Number of images and masks must be equal!")   # the reference's dataset check, classes.py:34-35
+        if classes is not None:
+            classes = self._label_values(classes)
+        if not size_only:
+            pred = pred.to(self.device).contiguous()
+        gt = gt.to(self.device).to(torch.uint8).contiguous()
+        n, H, W = (int(d) for d in pred.shape)
+        if tuple(gt.shape[1:]) != (H, W):
+            Hg, Wg = (int(d) for d in gt.shape[1:])
+            g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
+                                                               self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
+                                                               torch.cuda.current_stream().cuda_stream))
+            gt = g2
+        return pred, gt, classes
+
     def resized_gt(self, gt: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
         """The ground truth as uint8 [n, H, W] on the device, nearest-resized to the prediction's size as `distance_stats`
         does (the tensor itself, cast, when the sizes agree)."""
-        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
-            raise ValueError("Number of images and masks must be equal!")
-        gt = gt.to(self.device).to(torch.uint8).contiguous()
-        n, H, W = (int(d) for d in pred.shape)
-        if tuple(gt.shape[1:]) == (H, W):
-            return gt
-        Hg, Wg = (int(d) for d in gt.shape[1:])
-        g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
-                                                           self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
-                                                           torch.cuda.current_stream().cuda_stream))
-        return g2
+        return self._device_pair(pred, gt, size_only=True)[1]
 
     def distance_stats(self, pred: torch.Tensor, gt: torch.Tensor, classes: Sequence[int], mode: int, pct_num: int,
                        pct_den: int):
         """(stats_i int64 [n, K, 6], stats_f float64 [n, K, 2]) device tensors of vitseg_distance_stats for uint8 predictions
         [n, H, W]; a ground truth of another size is nearest-resized first, as `counts` does on the fly."""
-        if pred.dtype != torch.uint8 or pred.dim() != 3:
-            raise ValueError(f"pred must be uint8 [n, H, W], got {pred.dtype} {tuple(pred.shape)}")
-        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
-            raise ValueError("Number of images and masks must be equal!")
-        classes = [int(c) for c in classes]
-        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
-            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
-        pred = pred.to(self.device).contiguous()
-        gt = gt.to(self.device).to(torch.uint8).contiguous()
+        pred, gt, classes = self._device_pair(pred, gt, classes)
         n, H, W = (int(d) for d in pred.shape)
         K = len(classes)
         cls = (ctypes.c_int32 * K)(*classes)
         with torch.cuda.device(self.device):
             st = torch.cuda.current_stream().cuda_stream
-            if tuple(gt.shape[1:]) != (H, W):
-                Hg, Wg = (int(d) for d in gt.shape[1:])
-                g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
-                _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
-                                                               self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
-                                                               st))
-                gt = g2
             nbytes = _lib.symbol("vitseg_distance_scratch_bytes")(n, H, W)
             if nbytes == 0:
                 raise ValueError(f"distance metrics: H and W must lie in 1..16384 and n in 1..32767, got {n} x {H} x {W}")
@@ -341,41 +352,18 @@ class Evaluator:
         classes = list(range(self.num_classes)) if classes is None else [int(c) for c in classes]
         si, sf = self.distance_stats(pred, gt, classes, DISTANCE_MODES[mode], num, den)
         rows = distances_from_stats(si.cpu().numpy(), sf.cpu().numpy(), num, den)
-        out = []
-        for row in rows:
-            d = dict(per_class=dict(zip(classes, row)))
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore", RuntimeWarning)   # all-nan -> nan, as the overlap means
-                for key in DISTANCE_KEYS:
-                    d[key] = float(np.nanmean([r[key] for r in row]))
-            out.append(d)
-        return out
+        return [dict(per_class=dict(zip(classes, row)), **_class_means(row, DISTANCE_KEYS)) for row in rows]
 
     def skeleton_stats(self, pred: torch.Tensor, gt: torch.Tensor, classes: Sequence[int], route: int = 0):
         """(stats_i int64 [n, K, 10], stats_f float64 [n, K, 2]) device tensors of vitseg_skeleton_stats for uint8 predictions
         [n, H, W]; a ground truth of another size is nearest-resized first, as `distance_stats` does.  One enqueue on the
         current stream; planes too large for the resident route (see skeleton.py) synchronise it."""
-        if pred.dtype != torch.uint8 or pred.dim() != 3:
-            raise ValueError(f"pred must be uint8 [n, H, W], got {pred.dtype} {tuple(pred.shape)}")
-        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
-            raise ValueError("Number of images and masks must be equal!")
-        classes = [int(c) for c in classes]
-        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
-            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
-        pred = pred.to(self.device).contiguous()
-        gt = gt.to(self.device).to(torch.uint8).contiguous()
+        pred, gt, classes = self._device_pair(pred, gt, classes)
         n, H, W = (int(d) for d in pred.shape)
         K = len(classes)
         cls = (ctypes.c_int32 * K)(*classes)
         with torch.cuda.device(self.device):
             st = torch.cuda.current_stream().cuda_stream
-            if tuple(gt.shape[1:]) != (H, W):
-                Hg, Wg = (int(d) for d in gt.shape[1:])
-                g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
-                _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
-                                                               self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
-                                                               st))
-                gt = g2
             nbytes = _lib.symbol("vitseg_skeleton_stats_scratch_bytes")(n, H, W, int(route))
             if nbytes == 0:
                 raise ValueError(f"crack metrics: H and W must lie in 1..16384 and n in 1..32767 (and the plane must fit the "
@@ -395,15 +383,7 @@ class Evaluator:
         classes = list(range(self.num_classes)) if classes is None else [int(c) for c in classes]
         si, sf = self.skeleton_stats(pred, gt, classes)
         rows = crack_from_stats(si.cpu().numpy(), sf.cpu().numpy())
-        out = []
-        for row in rows:
-            d = dict(per_class=dict(zip(classes, row)))
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore", RuntimeWarning)   # all-nan -> nan, as the overlap means
-                for key in CRACK_KEYS:
-                    d[key] = float(np.nanmean([float(r[key]) for r in row]))
-            out.append(d)
-        return out
+        return [dict(per_class=dict(zip(classes, row)), **_class_means(row, CRACK_KEYS)) for row in rows]
 
     def region_match_stats(self, pred: torch.Tensor, gt: torch.Tensor, classes: Sequence[int], iou=(1, 2), coverage=(1, 2),
                            connectivity: int = 4, background: int = 0, ignore_label: int = -1, return_info: bool = False):
@@ -411,27 +391,12 @@ class Evaluator:
         another size is nearest-resized first, exactly as `distance_stats` does.  iou and coverage are (num, den) pairs.
         return_info: (stats, pred_info, gt_info, gt as compared), the int32 [n, H, W, 2] planes of include/vitseg.h.  One
         enqueue on the current stream."""
-        if pred.dtype != torch.uint8 or pred.dim() != 3:
-            raise ValueError(f"pred must be uint8 [n, H, W], got {pred.dtype} {tuple(pred.shape)}")
-        if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
-            raise ValueError("Number of images and masks must be equal!")
-        classes = [int(c) for c in classes]
-        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
-            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
-        pred = pred.to(self.device).contiguous()
-        gt = gt.to(self.device).to(torch.uint8).contiguous()
+        pred, gt, classes = self._device_pair(pred, gt, classes)
         n, H, W = (int(d) for d in pred.shape)
         K = len(classes)
         cls = (ctypes.c_int32 * K)(*classes)
         with torch.cuda.device(self.device):
             st = torch.cuda.current_stream().cuda_stream
-            if tuple(gt.shape[1:]) != (H, W):
-                Hg, Wg = (int(d) for d in gt.shape[1:])
-                g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
-                _lib.check(_lib.lib().vitseg_resize_nearest_u8(gt.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
-                                                               self._nearest(Wg, W).data_ptr(), H, W, None, 0, g2.data_ptr(),
-                                                               st))
-                gt = g2
             nbytes = _lib.symbol("vitseg_region_match_scratch_bytes")(n, H, W)
             if nbytes == 0:
                 raise ValueError(f"region metrics: H * W must stay below 2^31 and n in 1..32767, got {n} x {H} x {W}")
@@ -449,22 +414,16 @@ class Evaluator:
     def _region_arguments(self, classes, iou_threshold, coverage, connectivity, background, ignore_label):
         """The arguments of `region_metrics`, checked before anything reaches the library."""
         thr, cov = iou_threshold_fraction(iou_threshold), coverage_fraction(coverage)
-        if connectivity not in (4, 8):
-            raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
-        if isinstance(background, bool) or not isinstance(background, (int, np.integer)) or not 0 <= int(background) <= 255:
-            raise ValueError(f"background must be an integer in 0..255, got {background!r}")
-        background = int(background)
+        _common.connectivity(connectivity)
+        background = _common.integer("background", background, 0, 255)
         if ignore_label is None:
             ignore_label = -1
-        elif (isinstance(ignore_label, bool) or not isinstance(ignore_label, (int, np.integer))
-              or not 0 <= int(ignore_label) <= 255 or int(ignore_label) == background):
+        elif not _common.is_integer(ignore_label, 0, 255) or int(ignore_label) == background:
             raise ValueError(f"ignore_label must be None or an integer in 0..255 other than the background, got {ignore_label!r}")
         ignore_label = int(ignore_label)
         if classes is None:
             classes = [c for c in range(self.num_classes) if c not in (background, ignore_label)]
-        classes = [int(c) for c in classes]
-        if not classes or len(classes) > 256 or any(not 0 <= c <= 255 for c in classes):
-            raise ValueError(f"classes must be 1..256 label values in 0..255, got {classes}")
+        classes = self._label_values(classes)
         if len(set(classes)) != len(classes) or background in classes or ignore_label in classes:
             raise ValueError(f"classes must be distinct and hold neither the background {background} nor the ignore label, "
                              f"got {classes}")
@@ -489,14 +448,8 @@ class Evaluator:
         res = self.region_match_stats(pred, gt, classes, thr, cov, connectivity, background, ignore_label,
                                       return_info=return_matches)
         stats = (res[0] if return_matches else res).cpu().numpy()
-        out = []
-        for i, row in enumerate(matches_from_stats(stats)):
-            d = dict(per_class=dict(zip(classes, row)), stats=stats[i])
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore", RuntimeWarning)   # all-nan -> nan, as the overlap means
-                for key in REGION_KEYS:
-                    d[key] = float(np.nanmean([r[key] for r in row]))
-            out.append(d)
+        out = [dict(per_class=dict(zip(classes, row)), stats=stats[i], **_class_means(row, REGION_KEYS))
+               for i, row in enumerate(matches_from_stats(stats))]
         if return_matches:
             from .regions import region_boxes
             _, pinfo, ginfo, g = res
@@ -529,21 +482,8 @@ class Evaluator:
         from . import regions as _regions
         if not isinstance(pred, torch.Tensor) or pred.dtype != torch.uint8 or pred.dim() != 3:
             raise ValueError(f"pred must be a uint8 tensor [n, H, W], got {getattr(pred, 'dtype', type(pred).__name__)}")
-        maps = {"pred": pred.to(self.device).contiguous()}
-        if gt is not None:
-            if gt.dim() != 3 or gt.shape[0] != pred.shape[0]:
-                raise ValueError("Number of images and masks must be equal!")
-            g = gt.to(self.device).to(torch.uint8).contiguous()
-            n, H, W = (int(d) for d in pred.shape)
-            if tuple(g.shape[1:]) != (H, W):
-                Hg, Wg = (int(d) for d in g.shape[1:])
-                g2 = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
-                with torch.cuda.device(self.device):
-                    _lib.check(_lib.lib().vitseg_resize_nearest_u8(g.data_ptr(), n, Hg, Wg, self._nearest(Hg, H).data_ptr(),
-                                                                   self._nearest(Wg, W).data_ptr(), H, W, None, 0,
-                                                                   g2.data_ptr(), torch.cuda.current_stream().cuda_stream))
-                g = g2
-            maps["gt"] = g
+        maps = {"pred": pred.to(self.device).contiguous()} if gt is None else \
+            dict(zip(("pred", "gt"), self._device_pair(pred, gt)))
         out = [dict() for _ in range(pred.shape[0])]
         for name, m in maps.items():
             recs = _regions.region_props(m, skeleton_classes=skeleton_classes, background=background,
@@ -562,7 +502,7 @@ class Evaluator:
             raise ValueError(f"pred must be a uint8 tensor [n, H, W], got {getattr(pred, 'dtype', type(pred).__name__)}")
         if classes is None:
             raise ValueError("classes must be a sequence of label values")
-        _cl.branch_table(np.zeros((0, len(_cl.BRANCH_FIELDS)), np.int64), pixel_size)   # validates pixel_size
+        _common.pixel_size(pixel_size)
         out = []
         for per_class in _cl.trace(pred.to(self.device), classes=classes, route=route):
             out.append({c: dict(nodes=nd, branches=br, points=pts, table=_cl.branch_table(br, pixel_size, pts),
@@ -584,10 +524,7 @@ def csv_row(model_info: Sequence, batch_num: int, image_idx: int, m: dict, infer
 
 
 def write_metrics_csv(path: str, rows: Sequence[Sequence]) -> None:
-    with open(path, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(CSV_COLUMNS)
-        w.writerows(rows)
+    _common.write_csv(path, CSV_COLUMNS, rows)
 
 
 def distance_csv_row(model_info: Sequence, batch_num: int, image_idx: int, mode: str, percentile, m: dict) -> list:
@@ -599,13 +536,6 @@ def distance_csv_row(model_info: Sequence, batch_num: int, image_idx: int, mode:
             m["hd_percentile"], m["assd"], per]
 
 
-def write_distance_csv(path: str, rows: Sequence[Sequence]) -> None:
-    with open(path, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(DISTANCE_CSV_COLUMNS)
-        w.writerows(rows)
-
-
 def crack_csv_row(model_info: Sequence, batch_num: int, image_idx: int, m: dict) -> list:
     """One row of <model>_crack_metrics.csv from one image's dict of `Evaluator.crack_metrics`; Per_Class holds
     class:cldice:length_gt:length_pred:mean_width_gt:mean_width_pred for every class present in either map, joined by "|"."""
@@ -615,23 +545,9 @@ def crack_csv_row(model_info: Sequence, batch_num: int, image_idx: int, m: dict)
             m["length_gt"], m["length_pred"], m["mean_width_gt"], m["mean_width_pred"], per]
 
 
-def write_crack_csv(path: str, rows: Sequence[Sequence]) -> None:
-    with open(path, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(CRACK_CSV_COLUMNS)
-        w.writerows(rows)
-
-
 def region_csv_row(model_info: Sequence, batch_num, image_idx, cls: int, iou_threshold, coverage, m: dict) -> list:
     """One row of <model>_region_metrics.csv from one class's dict of `matches_from_stats`; batch_num "pooled" and an empty
     image_idx mark a row of the integers summed over all images."""
     return [model_info[0], model_info[1], batch_num, image_idx, cls, iou_threshold, coverage, m["n_gt"], m["n_pred"], m["tp"],
             m["fp"], m["fn"], m["gt_found"], m["pred_confirmed"], m["sum_q"], m["sum_i"], m["sum_u"], m["pq"], m["sq"], m["rq"],
             m["precision"], m["recall"], m["f1"], m["found_rate"], m["confirmed_rate"], m["mean_matched_iou"]]
-
-
-def write_region_csv(path: str, rows: Sequence[Sequence]) -> None:
-    with open(path, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(REGION_CSV_COLUMNS)
-        w.writerows(rows)

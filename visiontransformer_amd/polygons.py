@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _ext, _lib
+from . import _common, _ext, _lib
 from .regions import _checked
 
 DEFAULT_MAX_RINGS = 1024       # ring rows per image on the first call
@@ -125,9 +125,7 @@ def polygons_to_geojson(records, polygons, *, pixel_size: float = 1.0, image_id=
     geometry a Polygon whose first ring is the outline and whose others are the holes, each closed by repeating its first
     point, coordinates [x * pixel_size, y * pixel_size] (x to the right, y down, the image's top left corner at the origin).
     Properties: class, first, area (pixels times pixel_size squared), holes, image_id and, with `class_names`, class_name."""
-    ps = float(pixel_size)
-    if not ps > 0 or ps == float("inf"):
-        raise ValueError(f"pixel_size must be a positive finite number, got {pixel_size!r}")
+    ps = _common.pixel_size(pixel_size)
     rec = np.asarray(records).reshape(-1, 7)
     if len(rec) != len(polygons):
         raise ValueError(f"{len(rec)} records for {len(polygons)} polygons")

@@ -10,7 +10,6 @@ pixel, in (class, first) order -- exactly the order in which the reference's loo
 """
 from __future__ import annotations
 
-import csv
 import ctypes as C
 import math
 from typing import Dict, List, Tuple
@@ -18,7 +17,7 @@ from typing import Dict, List, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _common, _lib
 
 FIELDS = ("class", "y_min", "x_min", "y_max", "x_max", "area", "first")
 DEFAULT_MAX_REGIONS = 1024   # records per image on the first call; an image with more triggers one call at its count
@@ -36,10 +35,8 @@ def _checked(mask, background: int, connectivity: int) -> Tuple[torch.Tensor, bo
         raise ValueError(f"mask must be [n, H, W] or [H, W], got shape {tuple(mask.shape)}")
     if mask.numel() == 0:
         raise ValueError(f"mask must not be empty, got shape {tuple(mask.shape)}")
-    if connectivity not in (4, 8):
-        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
-    if isinstance(background, bool) or not isinstance(background, (int, np.integer)) or not -1 <= int(background) <= 255:
-        raise ValueError(f"background must be an integer in 0..255 or -1 (none), got {background!r}")
+    _common.connectivity(connectivity)
+    _common.integer("background", background, -1, 255, "0..255 or -1 (none)")
     single = mask.dim() == 2
     if single:
         mask = mask[None]
@@ -129,13 +126,7 @@ def _checked_props(mask, skeleton_classes, background: int, connectivity: int, r
         if skeleton_classes != "all":
             raise ValueError(f'skeleton_classes must be None, "all" or a sequence of label values, got {skeleton_classes!r}')
         return m, single, "all"
-    classes = list(skeleton_classes)
-    if any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) <= 255 for c in classes):
-        raise ValueError(f"skeleton_classes must be label values in 0..255, got {classes}")
-    classes = [int(c) for c in classes]
-    if len(set(classes)) != len(classes) or int(background) in classes:
-        raise ValueError(f"skeleton_classes must be distinct and must not hold the background {background}, got {classes}")
-    return m, single, classes
+    return m, single, _common.label_values("skeleton_classes", skeleton_classes, empty_ok=True, background=int(background))
 
 
 def _launch_props(m: torch.Tensor, classes, background: int, connectivity: int, route: int, max_regions: int,
@@ -217,9 +208,7 @@ def props_from_records(records, pixel_size: float = 1.0) -> List[dict]:
     rec = np.asarray(records)
     if rec.ndim != 2 or rec.shape[1] != len(PROPS_FIELDS):
         raise ValueError(f"records must be [k, {len(PROPS_FIELDS)}], got {rec.shape}")
-    ps = float(pixel_size)
-    if not ps > 0 or math.isinf(ps):
-        raise ValueError(f"pixel_size must be a positive finite number, got {pixel_size!r}")
+    ps = _common.pixel_size(pixel_size)
     nan = float("nan")
     out = []
     for row in rec:
@@ -261,7 +250,4 @@ def props_csv_row(source: str, model_info, batch_num, image_idx, region: int, d:
 
 
 def write_props_csv(path: str, rows) -> None:
-    with open(path, mode="w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(PROPS_CSV_COLUMNS)
-        w.writerows(rows)
+    _common.write_csv(path, PROPS_CSV_COLUMNS, rows)

@@ -4,19 +4,16 @@ torch.save'd dict), checkpoint discovery with the reference's rule, and the per-
 """
 from __future__ import annotations
 
-import json
 import os
 import re
 import time
 from typing import List, Optional
 
-import numpy as np
 import torch
 
-from . import synth
-from .metrics import (Evaluator, crack_csv_row, csv_row, distance_csv_row, matches_from_stats, pool_region_stats,
-                      region_csv_row, write_crack_csv, write_distance_csv, write_metrics_csv, write_region_csv)
-from .regions import props_csv_row, write_props_csv
+from . import clean, reports, synth
+from .metrics import Evaluator, csv_row, write_metrics_csv
+from .tta import parse_sizes
 
 
 def checkpoint_epoch(path: str) -> Optional[int]:
@@ -180,14 +177,23 @@ def run_validation(model, batches, device) -> dict:
     return {k: float(torch.stack([t.to("cpu") for t in v]).mean()) for k, v in acc.items()}
 
 
-def parse_props_classes(text: Optional[str]):
-    """The value of --region-props: None (flag absent), "all", or a comma-separated list of label values."""
+def _stem(csv_path: str) -> str:
+    """What every file of one evaluation starts with: the metrics file's path without "_metrics.csv" (or its extension)."""
+    return csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
+
+
+def _parse_classes(flag: str, text: Optional[str]):
+    """The value of a class-list flag: None (flag absent), "all", or a comma-separated list of label values."""
     if text is None or text == "all":
         return text
     try:
         return [int(t) for t in text.split(",") if t.strip()]
     except ValueError:
-        raise ValueError(f'--region-props takes "all" or comma-separated label values, got {text!r}') from None
+        raise ValueError(f'{flag} takes "all" or comma-separated label values, got {text!r}') from None
+
+
+def parse_props_classes(text: Optional[str]):
+    return _parse_classes("--region-props", text)
 
 
 def add_confidence_arguments(ap) -> None:
@@ -228,10 +234,7 @@ def add_polygon_arguments(ap) -> None:
 def polygon_options(a, metrics_csv_path: str) -> dict:
     """The keywords of `evaluate_to_csv` from the parsed flags: none without --region-polygons, else `polygons_path`, the
     .geojson file beside the metrics file."""
-    if not a.region_polygons:
-        return {}
-    stem = metrics_csv_path[:-len("_metrics.csv")] if metrics_csv_path.endswith("_metrics.csv") else os.path.splitext(metrics_csv_path)[0]
-    return dict(polygons_path=stem + "_region_polygons.geojson")
+    return dict(polygons_path=_stem(metrics_csv_path) + "_region_polygons.geojson") if a.region_polygons else {}
 
 
 def add_crack_graph_arguments(ap) -> None:
@@ -249,198 +252,130 @@ def crack_graph_options(a, metrics_csv_path: str) -> dict:
     and the two files beside the metrics file."""
     if a.crack_graph is None:
         return {}
-    if a.crack_graph == "all":
-        classes = True
-    else:
-        try:
-            classes = [int(t) for t in a.crack_graph.split(",") if t.strip()]
-        except ValueError:
-            raise ValueError(f'--crack-graph takes "all" or comma-separated label values, got {a.crack_graph!r}') from None
-    stem = metrics_csv_path[:-len("_metrics.csv")] if metrics_csv_path.endswith("_metrics.csv") else os.path.splitext(metrics_csv_path)[0]
-    return dict(crack_graph_classes=classes, crack_graph_path=stem + "_crack_graph.geojson",
+    classes = _parse_classes("--crack-graph", a.crack_graph)
+    stem = _stem(metrics_csv_path)
+    return dict(crack_graph_classes=True if classes == "all" else classes, crack_graph_path=stem + "_crack_graph.geojson",
                 crack_branches_csv_path=stem + "_crack_branches.csv")
 
 
+def add_evaluation_arguments(ap) -> None:
+    """Every flag the two evaluation scripts (model/CE/datasetTestViTmodel.py, model/PAED/ViTscriptTest.py) share."""
+    ap.add_argument("--distance-metrics", nargs="?", const="sets", choices=["sets", "borders"],
+                    help="also write <model>_distance_metrics.csv: PAED, Hausdorff, HD95 and ASSD per image, between the "
+                         "pixel sets of each class (sets, the default) or between their borders")
+    ap.add_argument("--crack-metrics", action="store_true",
+                    help="also write <model>_crack_metrics.csv: centre-line Dice, crack length and width per image, from the "
+                         "Zhang-Suen skeletons of every class but the background 0")
+    ap.add_argument("--region-metrics", action="store_true",
+                    help="also write <model>_region_metrics.csv: regions found, missed and raised falsely, PQ / SQ / RQ and the "
+                         "coverage hit rates per image and class but the background 0, then pooled over all images")
+    ap.add_argument("--region-iou", type=float, default=0.5, help="a predicted and a true region match above this IoU (0.5 <= t < 1)")
+    ap.add_argument("--region-coverage", type=float, default=0.5, help="a region is found / confirmed from this covered fraction on")
+    ap.add_argument("--region-connectivity", type=int, default=4, choices=[4, 8])
+    ap.add_argument("--region-props", nargs="?", const="all", metavar="C0,C1,...|all",
+                    help="also write <model>_region_props.csv: one row per region of the prediction and of the ground truth "
+                         "(position, size, axes, orientation, perimeter, frame contact) and, for the listed classes (default: "
+                         "all present but the background 0), the region's own skeleton length and widths; regions by "
+                         "--region-connectivity")
+    ap.add_argument("--pixel-size", type=float, default=1.0, help="side of a pixel: the unit of the lengths in <model>_region_props.csv and <model>_crack_branches.csv and of the "
+                         "coordinates in <model>_region_polygons.geojson and <model>_crack_graph.geojson")
+    ap.add_argument("--tta", help='test-time augmentation: "hflip", "flip" or "d4" -- the mask is merged from flipped / '
+                                  "quarter-turned views (default: one look)")
+    ap.add_argument("--tta-sizes", help="comma-separated sides the views are resampled to, e.g. 160,224 (default: the image size)")
+    ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"], help="mean of the views' logits or of their sigmoids")
+    clean.add_arguments(ap)
+    add_confidence_arguments(ap)
+    add_polygon_arguments(ap)
+    add_crack_graph_arguments(ap)
+
+
+def evaluation_options(ap, a, csv_path: str) -> dict:
+    """The keywords of `evaluate_to_csv` from the flags of `add_evaluation_arguments`, for the metrics file `csv_path`;
+    `confidence_options`' refusals go through ap.error."""
+    return dict(distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None,
+                tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge,
+                region_classes=True if a.region_metrics else None, region_iou=a.region_iou, region_coverage=a.region_coverage,
+                region_connectivity=a.region_connectivity, props_classes=parse_props_classes(a.region_props),
+                props_pixel_size=a.pixel_size, **clean.arguments(a), **confidence_options(ap, a),
+                **polygon_options(a, csv_path), **crack_graph_options(a, csv_path))
+
+
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
-                    distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None,
-                    percentile=95, crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None,
-                    tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False,
-                    max_hole_area: int = 0, region_classes=None, region_csv_path: Optional[str] = None, region_iou=0.5,
-                    region_coverage=0.5, region_connectivity: int = 4, props_classes=None,
-                    props_csv_path: Optional[str] = None, props_pixel_size: float = 1.0, region_scores: bool = False,
-                    score_kind: str = "prob", score_low: float = 0.5, calibration_bins: Optional[int] = None,
-                    scores_csv_path: Optional[str] = None, calibration_csv_path: Optional[str] = None,
-                    polygons_path: Optional[str] = None, crack_graph_classes=None, crack_graph_path: Optional[str] = None,
-                    crack_branches_csv_path: Optional[str] = None) -> List[list]:
+                    distance_mode: Optional[str] = None, distance_csv_path: Optional[str] = None, percentile=95,
+                    crack_classes=None, crack_csv_path: Optional[str] = None, tta=None, tta_sizes=None, tta_merge: str = "logits",
+                    min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0, region_classes=None,
+                    region_csv_path: Optional[str] = None, region_iou=0.5, region_coverage=0.5, region_connectivity: int = 4,
+                    props_classes=None, props_csv_path: Optional[str] = None, props_pixel_size: float = 1.0,
+                    region_scores: bool = False, score_kind: str = "prob", score_low: float = 0.5,
+                    calibration_bins: Optional[int] = None, scores_csv_path: Optional[str] = None,
+                    calibration_csv_path: Optional[str] = None, polygons_path: Optional[str] = None, crack_graph_classes=None,
+                    crack_graph_path: Optional[str] = None, crack_branches_csv_path: Optional[str] = None) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
-    sets per image, one CSV row each with the batch's average time per image.  Predictions and class statistics stay on
-    the GPU (fused sigmoid -> argmax mask, vitseg_eval_counts).  distance_mode "sets" / "borders": the boundary distances of
-    every image (Evaluator.distance_metrics: PAED, Hausdorff, its percentile, ASSD) go to a second file, distance_csv_path
-    (default: <csv_path minus "_metrics.csv">_distance_metrics.csv); the first file is the same with and without it.
-    crack_classes (a list of label values, or True for every class but 0): clDice, crack length and width of every image
-    (Evaluator.crack_metrics) go to crack_csv_path (default: ..._crack_metrics.csv), again beside the unchanged first file.
-    tta (default None: one look): a test-time-augmentation preset or op sequence; every file then scores the merged mask of
-    `predict_mask_tta` (views at tta_sizes, default the batch's own size, merged by tta_merge).
-    min_area / fill_holes / max_hole_area (defaults: off): every file scores the mask cleaned on the device by
-    clean.clean_mask (regions below min_area pixels to class 0, then enclosed holes of at most max_hole_area pixels filled);
-    the clean-up is part of the time per image.
-    region_classes (a list of label values, or True for every class but 0): the region-level detection statistics of every
-    image and class (Evaluator.region_metrics at region_iou / region_coverage / region_connectivity) go to region_csv_path
-    (default: ..._region_metrics.csv), followed by one row per class of the integers pooled over all images.
-    props_classes (None: off; a list of label values, "all", or True for every class but 0 -- the classes whose regions also get
-    their own skeleton length and widths; an empty list measures shape alone): one row per region of the prediction and of the
-    ground truth (Evaluator.region_props at region_connectivity, lengths in units of props_pixel_size) goes to props_csv_path
-    (default: ..._region_props.csv), with a Source column pred / gt.
-    region_scores (default off): one row per predicted region -- class, first, area, score, score_min, low_fraction
-    (confidence.region_scores with score_kind / score_low at region_connectivity, on the cleaned mask when the clean-up is
-    on) -- goes to scores_csv_path (default: ..._region_scores.csv).  With region_classes the row also holds the region's
-    `matched` flag, joined on `first` to Evaluator.region_metrics(return_matches=True), and one pooled AP row per class
-    follows (confidence.average_precision over all images' regions of the class against the pooled n_gt).
-    calibration_bins (None: off): the reliability table pooled over all images (confidence.calibration_hist of the mask against
-    the resized ground truth, the integers added before any ratio) and its ECE go to calibration_csv_path (default:
-    ..._calibration.csv).  Either makes the forward keep its low-res head output (one encoder pass, predict_mask's mask bit
-    for bit); with tta they raise ValueError: scoring merged views is not built.
-    polygons_path (None: off): the outlines of every predicted region of the (cleaned, merged) mask
-    (polygons.region_polygons at region_connectivity, coordinates in units of props_pixel_size) go to that file as one GeoJSON
-    FeatureCollection, each feature carrying its image as image_id "<batch>/<index>" and its batch_num / image_idx.
-    crack_graph_classes (None: off; a list of label values, or True for every class but 0): the centre-line graph of each class
-    of the (cleaned, merged) mask (Evaluator.crack_graph, lengths and coordinates in units of props_pixel_size) goes to
-    crack_graph_path (default: ..._crack_graph.geojson) as one FeatureCollection of LineStrings, tagged like the outlines, and
-    to crack_branches_csv_path (default: ..._crack_branches.csv): one row per branch, then a summary row per image and class."""
-    from . import clean as _clean
-    from . import confidence as _conf
-    min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
-    scoring = bool(region_scores) or calibration_bins is not None
-    if scoring:
-        if tta is not None:
-            raise ValueError("region_scores / calibration_bins with tta are not supported: the scores are those of one forward")
-        if score_kind not in _conf.KINDS:
-            raise ValueError(f"score_kind must be one of {sorted(_conf.KINDS)}, got {score_kind!r}")
-        _conf.low_to_q(score_low)
-        if calibration_bins is not None and (isinstance(calibration_bins, bool) or not isinstance(calibration_bins, int)
-                                             or not 1 <= calibration_bins <= _conf.MAX_BINS):
-            raise ValueError(f"calibration_bins must be None or an integer in 1..{_conf.MAX_BINS}, got {calibration_bins!r}")
+    sets per image, one CSV row each with the batch's average time per image; returns those rows.  Predictions and class
+    statistics stay on the GPU (fused sigmoid -> argmax mask, vitseg_eval_counts).  Every option is validated before the
+    model is touched.  The other keywords add files beside the first, which stays as it is; its class in `reports` describes
+    each group, a *_path defaults to <csv_path minus "_metrics.csv"> + the report's suffix, a class list may be True (all but 0):
+      tta, tta_sizes, tta_merge               every file scores the merged mask of `predict_mask_tta` (default: one look)
+      min_area, fill_holes, max_hole_area     every file scores the mask cleaned by clean.clean_mask, inside the time per image
+      region_connectivity, props_pixel_size   the regions, and the unit of length, of every report below that has them
+      distance_mode, percentile               reports.Distance
+      crack_classes                           reports.Crack
+      region_classes, region_iou, region_coverage   reports.RegionMetrics
+      region_scores, score_kind, score_low    reports.RegionScores (ValueError with tta)
+      calibration_bins, score_kind            reports.Calibration (ValueError with tta)
+      props_classes (also "all")              reports.RegionProps
+      polygons_path                           reports.Outlines
+      crack_graph_classes                     reports.CrackGraph"""
+    min_area, fill_holes, max_hole_area = clean.check_options(min_area, fill_holes, max_hole_area)
+    if region_scores or calibration_bins is not None:
+        reports.check_scoring(tta, score_kind, score_low)
+    crack_classes, region_classes, props_classes, crack_graph_classes = (
+        reports.every_class_but_0(c, num_classes) for c in (crack_classes, region_classes, props_classes, crack_graph_classes))
+    regions = reports.RegionMetrics(model_info, region_classes, region_iou, region_coverage, bool(region_scores),
+                                    region_csv_path) if region_classes else None
+    active = [   # in the order of their device calls per batch
+        reports.Distance(distance_mode, percentile, distance_csv_path) if distance_mode is not None else None,
+        reports.Crack(crack_csv_path, crack_classes) if crack_classes else None,
+        regions,
+        reports.RegionScores(model_info, score_kind, score_low, regions, scores_csv_path) if region_scores else None,
+        reports.Calibration(model_info, calibration_bins, score_kind, calibration_csv_path) if calibration_bins is not None else None,
+        reports.RegionProps(props_csv_path, props_classes) if props_classes is not None else None,
+        reports.Outlines(polygons_path) if polygons_path is not None else None,
+        reports.CrackGraph(crack_graph_classes, crack_graph_path, crack_branches_csv_path) if crack_graph_classes is not None else None,
+    ]
+    active = [r for r in active if r is not None]
     seg = getattr(model, "model", model)
     ev = Evaluator(num_classes, device)
-    rows, drows, crows, rrows, rstats, prows = [], [], [], [], [], []
-    srows, ranked, pooled_hist = [], {}, None
-    features = []
-    if props_classes is True:
-        props_classes = list(range(1, num_classes))
-    if crack_classes is True:
-        crack_classes = list(range(1, num_classes))
-    if region_classes is True:
-        region_classes = list(range(1, num_classes))
-    if crack_graph_classes is True:
-        crack_graph_classes = list(range(1, num_classes))
-    if crack_graph_classes is not None:
-        from . import centerlines as _cl
-        crack_graph_classes = _cl.check_options(crack_graph_classes)
-        lines, brows = [], []
+    rows = []
     model.eval()
     for bn, batch in enumerate(batches):
         if bn >= num_batches:
             break
         x, gt = batch[0].to(device), batch[1]
+        lowres = None
         torch.cuda.synchronize()
         t0 = time.time()
         with torch.no_grad():
             if tta is not None:
                 mask = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge)
-            elif scoring:
+            elif any(r.needs_lowres for r in active):
                 lowres, mask = seg._lowres_and_mask(x)
             else:
                 mask = seg.predict_mask(x)
-            if _clean.active(min_area, fill_holes):
-                mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area)
+            if clean.active(min_area, fill_holes):
+                mask = clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area)
         torch.cuda.synchronize()
         per_image = (time.time() - t0) / len(x)
         gt = gt.reshape(gt.shape[0], gt.shape[-2], gt.shape[-1])
         for idx, m in enumerate(ev.evaluate(mask, gt)):
             rows.append(csv_row(model_info, bn, idx, m, per_image))
-        if distance_mode is not None:
-            for idx, m in enumerate(ev.distance_metrics(mask, gt, mode=distance_mode, percentile=percentile)):
-                drows.append(distance_csv_row(model_info, bn, idx, distance_mode, percentile, m))
-        if crack_classes:
-            for idx, m in enumerate(ev.crack_metrics(mask, gt, classes=crack_classes)):
-                crows.append(crack_csv_row(model_info, bn, idx, m))
-        matched = None   # per image {(class, first): the predicted region has a partner}
-        if region_classes:
-            extra = dict(return_matches=True) if region_scores else {}
-            found = ev.region_metrics(mask, gt, classes=region_classes, iou_threshold=region_iou, coverage=region_coverage,
-                                      connectivity=region_connectivity, **extra)
-            for idx, m in enumerate(found):
-                rstats.append(m["stats"])
-                for c, r in m["per_class"].items():
-                    rrows.append(region_csv_row(model_info, bn, idx, c, region_iou, region_coverage, r))
-            if region_scores:
-                matched = [{(int(r[0]), int(r[6])): int(r[7]) >= 0 for r in m["matches"]["pred"]} for m in found]
-        if region_scores:
-            recs, srow = _conf.region_scores(lowres, mask, kind=score_kind, low=score_low, connectivity=region_connectivity)
-            for idx, (rec, row) in enumerate(zip(recs, srow)):
-                for r, d in enumerate(_conf.region_dicts(rec, row)):
-                    flag = "" if matched is None else matched[idx].get((d["class"], d["first"]), "")
-                    if flag != "":
-                        ranked.setdefault(d["class"], []).append((d["score"], flag))
-                    srows.append([model_info[0], model_info[1], bn, idx, r, d["class"], d["first"], d["area"], d["score"],
-                                  d["score_min"], d["low_fraction"], "" if flag == "" else int(flag), "", ""])
-        if calibration_bins is not None:
-            h = _conf.calibration_hist(lowres, mask, ev.resized_gt(gt, mask), bins=calibration_bins, kind=score_kind)
-            pooled_hist = h.sum(axis=0) if pooled_hist is None else pooled_hist + h.sum(axis=0)
-        if props_classes is not None:
-            for idx, m in enumerate(ev.region_props(mask, gt, skeleton_classes=props_classes, connectivity=region_connectivity,
-                                                    pixel_size=props_pixel_size)):
-                for source in ("pred", "gt"):
-                    for r, d in enumerate(m[source]):
-                        prows.append(props_csv_row(source, model_info, bn, idx, r, d))
-        if polygons_path is not None:
-            from . import polygons as _poly
-            for idx, (rec, rings) in enumerate(_poly.region_polygons(mask, connectivity=region_connectivity)):
-                for f in _poly.polygons_to_geojson(rec, rings, pixel_size=props_pixel_size, image_id=f"{bn}/{idx}")["features"]:
-                    f["properties"].update(model_id=model_info[0], model_name=model_info[1], batch_num=bn, image_idx=idx)
-                    features.append(f)
-        if crack_graph_classes is not None:
-            for idx, per_class in enumerate(ev.crack_graph(mask, crack_graph_classes, pixel_size=props_pixel_size)):
-                for c, g in per_class.items():
-                    found = _cl.centerlines_to_geojson(g["branches"], g["points"], pixel_size=props_pixel_size,
-                                                       image_id=f"{bn}/{idx}", class_id=c)["features"]
-                    for f in found:
-                        f["properties"].update(model_id=model_info[0], model_name=model_info[1], batch_num=bn, image_idx=idx)
-                    lines += found
-                    brows += _cl.csv_rows(model_info, bn, idx, c, g["table"], g["summary"])
+        for r in active:
+            r.add(reports.Batch(bn, mask, gt, lowres, ev, model_info, region_connectivity, props_pixel_size))
     os.makedirs(os.path.dirname(os.path.abspath(csv_path)), exist_ok=True)
     write_metrics_csv(csv_path, rows)
-    stem = csv_path[:-len("_metrics.csv")] if csv_path.endswith("_metrics.csv") else os.path.splitext(csv_path)[0]
-    if distance_mode is not None:
-        if distance_csv_path is None:
-            distance_csv_path = stem + "_distance_metrics.csv"
-        write_distance_csv(distance_csv_path, drows)
-    if crack_classes:
-        write_crack_csv(crack_csv_path or stem + "_crack_metrics.csv", crows)
-    if region_classes:
-        if rstats:
-            for c, r in zip(region_classes, matches_from_stats(pool_region_stats(rstats))):
-                rrows.append(region_csv_row(model_info, "pooled", "", c, region_iou, region_coverage, r))
-        write_region_csv(region_csv_path or stem + "_region_metrics.csv", rrows)
-    if props_classes is not None:
-        write_props_csv(props_csv_path or stem + "_region_props.csv", prows)
-    if region_scores:
-        if region_classes and rstats:
-            n_gt = pool_region_stats(rstats)[:, 0]
-            for c, k in zip(region_classes, n_gt):
-                det = ranked.get(c, [])
-                ap = _conf.average_precision([s for s, _ in det], [f for _, f in det], int(k))
-                srows.append([model_info[0], model_info[1], "pooled", "", "", c, "", "", "", "", "", "", ap, int(k)])
-        _conf.write_csv(scores_csv_path or stem + "_region_scores.csv", _conf.SCORES_CSV_COLUMNS, srows)
-    if calibration_bins is not None:
-        _conf.write_csv(calibration_csv_path or stem + "_calibration.csv", _conf.CALIBRATION_CSV_COLUMNS,
-                        _conf.calibration_csv_rows(model_info, pooled_hist, calibration_bins))
-    if polygons_path is not None:
-        with open(polygons_path, "w") as f:
-            json.dump({"type": "FeatureCollection", "features": features}, f)
-    if crack_graph_classes is not None:
-        with open(crack_graph_path or stem + "_crack_graph.geojson", "w") as f:
-            json.dump({"type": "FeatureCollection", "features": lines}, f)
-        _cl.write_csv(crack_branches_csv_path or stem + "_crack_branches.csv", brows)
+    for r in active:
+        r.write(_stem(csv_path))
     return rows
+
+
