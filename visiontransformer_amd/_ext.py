@@ -4,8 +4,10 @@ A feature family has a header of its own (include/vitseg_<family>.h, with its ow
 family -> (header file, the words after "built before" in `ext_symbol`'s error, [(name, restype, argtypes)]).  `_lib.SIGNATURES`
 and include/vitseg.h do not grow with it.  Functions are bound on first use on the handle `_lib.lib()` loaded;
 tests/test_polygons_cpu.py compares the table with the header through the parser of tests/test_binding_cpu.py.
-EXT_SIGNATURES is pinned to the polygons family by that test; later families have the same kind of entry in EXT_FAMILIES
-(tests/test_centerlines_cpu.py), which `ext_symbol` consults after EXT_SIGNATURES.
+EXT_SIGNATURES is pinned to the polygons family by that test and EXT_FAMILIES to the centre-lines by
+tests/test_centerlines_cpu.py; `ext_symbol` consults them in that order and EXT_LATER last.  EXT_LATER is pinned by no test
+to one family: it is where the line simplification and every later family go, each with the same kind of entry, so no
+further table is needed.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ from ._lib import i32, i64, sz, vp
 
 POLYGONS_VERSION = 100   # include/vitseg_polygons.h VITSEG_POLYGONS_VERSION this binding was written against
 CENTERLINES_VERSION = 100   # include/vitseg_centerlines.h VITSEG_CENTERLINES_VERSION
+SIMPLIFY_VERSION = 100   # include/vitseg_simplify.h VITSEG_SIMPLIFY_VERSION
 
 EXT_SIGNATURES = {
     # region outlines: polygon rings with holes (polygons.py)
@@ -33,16 +36,25 @@ EXT_FAMILIES = {
         ("vitseg_centerlines", i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i64, vp, sz, vp]),
     ]),
 }
+EXT_LATER = {
+    # Douglas-Peucker over rings and polylines on the device (simplify.py); a later family adds its entry here
+    "simplify": ("vitseg_simplify.h", "the line simplification", [
+        ("vitseg_simplify_version", i32, []),
+        ("vitseg_simplify_scratch_bytes", sz, [i32, i32, i64]),
+        ("vitseg_simplify_lines", i32, [vp, i64, i32, vp, i32, i32, i32, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, sz, vp]),
+    ]),
+}
 EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
-                "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION)}
+                "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION),
+                "simplify": ("vitseg_simplify_version", SIMPLIFY_VERSION)}
 
 
 def ext_symbol(family: str, name: str):
-    """The entry point `name` of `family` on `_lib.lib()`'s handle, restype and argtypes set from EXT_SIGNATURES / EXT_FAMILIES on first
-    use;
+    """The entry point `name` of `family` on `_lib.lib()`'s handle, restype and argtypes set from EXT_SIGNATURES / EXT_FAMILIES /
+    EXT_LATER on first use;
     a RuntimeError naming the rebuild when the loaded library predates the family (or `name` is not in its table) or was built
     from another version of its header."""
-    _, what, rows = EXT_SIGNATURES[family] if family in EXT_SIGNATURES else EXT_FAMILIES[family]
+    _, what, rows = next(t for t in (EXT_SIGNATURES, EXT_FAMILIES, EXT_LATER) if family in t)[family]
     row = {n: (restype, argtypes) for n, restype, argtypes in rows}.get(name)
     fn = getattr(_lib.lib(), name, None) if row is not None else None
     if fn is None:

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _common, _ext, _lib
+from . import simplify as _simplify
 from .skeleton import MAX_BATCH, MAX_SIDE, ROUTES
 
 MAX_PIXELS = 1 << 29
@@ -92,24 +93,36 @@ def _launch(m: torch.Tensor, value: int, thin: bool, route: int, max_nodes: int,
     return counts, nodes, branches, points
 
 
-def _trace_value(m: torch.Tensor, value: int, thin: bool, route: int):
-    """One plane selection of a batch: a count query, then the call at the true sizes; [(nodes, branches, points)] per image."""
+def _trace_value(m: torch.Tensor, value: int, thin: bool, route: int, simplify=None):
+    """One plane selection of a batch: a count query, then the call at the true sizes; [(nodes, branches, points)] per image.
+    With `simplify` the points are thinned on the device and only the kept ones are copied back."""
     n = int(m.shape[0])
     cnt = _launch(m, value, thin, route, 0, 0, 0)[0].cpu().numpy()
     nodes_n, branches_n, points_n = cnt[:n], cnt[n:2 * n], cnt[2 * n:].view(np.int64)
-    _, nodes, branches, points = _launch(m, value, thin, route, int(nodes_n.max()), int(branches_n.max()), int(points_n.max()))
-    nodes, branches, points = nodes.cpu().numpy(), branches.cpu().numpy(), points.cpu().numpy()
+    counts, nodes, branches, points = _launch(m, value, thin, route, int(nodes_n.max()), int(branches_n.max()),
+                                              int(points_n.max()))
+    if simplify is not None:
+        thinned = _simplify.simplify_device(points, branches, counts[n:2 * n], _simplify.BRANCH_COLS, simplify)
+        kept_n, lines, points = _simplify.kept_to_host(*thinned)
+        nodes, branches = nodes.cpu().numpy(), branches.cpu().numpy()
+        full = branches[:, :, 3].copy()
+        branches[:, :, 2:4] = lines[:, :, 0:2]   # offset and count alone change: lengths and widths stay the full branch's
+        points_n = kept_n
+    else:
+        nodes, branches, points = nodes.cpu().numpy(), branches.cpu().numpy(), points.cpu().numpy()
     out = []
     for i in range(n):
         b = branches[i, :int(branches_n[i])]
         pts = points[i, :int(points_n[i])]
-        out.append((nodes[i, :int(nodes_n[i])].copy(), b.copy(),
-                    [np.ascontiguousarray(pts[int(o):int(o + c)]) for o, c in zip(b[:, 2], b[:, 3])]))
+        lists = [np.ascontiguousarray(pts[int(o):int(o + c)]) for o, c in zip(b[:, 2], b[:, 3])]
+        if simplify is not None:
+            lists = _simplify.Simplified(lists, simplify, full[i, :int(branches_n[i])])
+        out.append((nodes[i, :int(nodes_n[i])].copy(), b.copy(), lists))
     return out
 
 
 @torch.no_grad()
-def trace(mask, classes=None, thin: bool = True, route: str = "auto", device=None):
+def trace(mask, classes=None, thin: bool = True, route: str = "auto", device=None, simplify=None):
     """The centre-line graph of a mask uint8 / bool / long [n, H, W] or [H, W], numpy or torch.
     classes=None reads the mask as binary (non-zero = set) and returns, per image, a triple (nodes, branches, points); with a
     sequence of label values (0..255, distinct) it returns, per image, a dict class -> triple, each class traced on its own plane
@@ -123,16 +136,24 @@ def trace(mask, classes=None, thin: bool = True, route: str = "auto", device=Non
     synchronise the stream); thin=False takes the plane as a centre-line set as it is.  d2 is the exact squared distance to the
     nearest pixel outside the plane's set.  Each plane selection makes a count query and one call at the true sizes; the
     counts are the only host read.  A CUDA tensor stays on its device, anything else goes to `device` (default cuda:0).
-    Raises ValueError, before the library is asked for anything, for a bad mask, `classes`, `thin` or `route`."""
+    `simplify`: a tolerance in pixels (None: off, nothing else is launched).  Every branch's polyline is thinned on the device
+    by `simplify.simplify_device` (Douglas-Peucker with the segment distance; include/vitseg_simplify.h) and only the kept
+    points are copied back.  Both ends of a branch are kept, so branches still meet at their node pixels; a closed branch
+    keeps its start and at least three points.  The rows of `branches` change in offset and count alone -- links, width sum
+    and max_d2 stay the full branch's -- and `points` is a `simplify.Simplified` list that also holds the tolerance and
+    every branch's full point count, which `branch_table` and `centerlines_to_geojson` read.
+    Raises ValueError, before the library is asked for anything, for a bad mask, `classes`, `thin`, `route` or `simplify`."""
     m, single, classes = _checked(mask, classes, thin, route)
+    if simplify is not None:
+        _simplify.tol2_q8(simplify)
     if not m.is_cuda:
         m = m.to(device or "cuda:0")
     m = m.to(torch.uint8).contiguous()
     n = int(m.shape[0])
     if classes is None:
-        res = _trace_value(m, -1, bool(thin), ROUTES[route])
+        res = _trace_value(m, -1, bool(thin), ROUTES[route], simplify)
     else:
-        per_class = {c: _trace_value(m, c, bool(thin), ROUTES[route]) for c in classes}
+        per_class = {c: _trace_value(m, c, bool(thin), ROUTES[route], simplify) for c in classes}
         res = [{c: per_class[c][i] for c in classes} for i in range(n)]
     return res[0] if single else res
 
@@ -152,8 +173,11 @@ def branch_table(branches, pixel_size: float = 1.0, points=None) -> List[dict]:
                               `points`, the list `trace` returns with the rows; nan without it; a closed branch has chord 0;
       width_mean, width_max   2 (width_q16 / 65536) / points - 1 and 2 sqrt(max_d2) - 1, the width convention of
                               regions.props_from_records;
-      closed, start, end, points   kind == 1, the raster indices of the two ends, the number of points."""
+      closed, start, end, points   kind == 1, the raster indices of the two ends, the number of points.
+    With the `points` of `trace(..., simplify=tol)` the mean width divides by the branch's full point count, the chord is that
+    of the kept ends (the same two points) and `points` is the kept count."""
     rec = _rows(branches)
+    full = points.full if isinstance(points, _simplify.Simplified) else None
     ps = _common.pixel_size(pixel_size)
     if points is not None and len(points) != len(rec):
         raise ValueError(f"{len(rec)} branches for {len(points)} point lists")
@@ -171,7 +195,7 @@ def branch_table(branches, pixel_size: float = 1.0, points=None) -> List[dict]:
         out.append({
             "start": start, "end": end, "closed": kind == 1, "points": count, "length": length * ps, "chord": chord * ps,
             "tortuosity": nan if math.isnan(chord) else (length / chord if chord > 0 else float("inf")),
-            "width_mean": (2 * (q16 / 65536) / count - 1) * ps, "width_max": (2 * math.sqrt(max_d2) - 1) * ps,
+            "width_mean": (2 * (q16 / 65536) / (count if full is None else full[i]) - 1) * ps, "width_max": (2 * math.sqrt(max_d2) - 1) * ps,
         })
     return out
 
@@ -207,11 +231,13 @@ def centerlines_to_geojson(branches, points, *, pixel_size: float = 1.0, image_i
     the end; an open branch of one link has two coordinates.  `drop_collinear` leaves out the points at which the line does not
     turn (the properties are those of the full branch).  Properties: class (`class_id`), start, end (raster indices), closed,
     length, width_mean, width_max (`branch_table`, in units of pixel_size), points, image_id and, with `class_names` and a
-    `class_id`, class_name."""
+    `class_id`, class_name.  The `points` of `trace(..., simplify=tol)` (a `simplify.Simplified` list) add simplify_tolerance
+    and vertices_full, the branch's full point count; nothing else changes."""
     table = branch_table(branches, pixel_size, points)
+    thinned = isinstance(points, _simplify.Simplified)
     ps = _common.pixel_size(pixel_size)
     features = []
-    for d, pts in zip(table, points):
+    for i, (d, pts) in enumerate(zip(table, points)):
         p = np.asarray(pts).reshape(-1, 3)
         if d["closed"]:
             p = np.concatenate([p, p[:1]])
@@ -223,6 +249,8 @@ def centerlines_to_geojson(branches, points, *, pixel_size: float = 1.0, image_i
                  "image_id": image_id}
         if class_names is not None and class_id is not None:
             props["class_name"] = str(class_names[int(class_id)])
+        if thinned:
+            props.update(simplify_tolerance=points.tolerance, vertices_full=points.full[i])
         features.append({"type": "Feature", "geometry": {"type": "LineString", "coordinates": coords}, "properties": props})
     return {"type": "FeatureCollection", "features": features}
 

@@ -492,19 +492,24 @@ class Evaluator:
                 d[name] = _regions.props_from_records(r, pixel_size)
         return out
 
-    def crack_graph(self, pred: torch.Tensor, classes: Sequence[int], pixel_size: float = 1.0, route: str = "auto") -> List[dict]:
+    def crack_graph(self, pred: torch.Tensor, classes: Sequence[int], pixel_size: float = 1.0, route: str = "auto",
+                    simplify=None) -> List[dict]:
         """Per image: {class: dict(nodes=, branches=, points=, table=, summary=)} for the label values in `classes` -- the
         centre-line graph of the skeleton of {pred == class} (centerlines.trace: the int32 / int64 rows and the point lists),
         `centerlines.branch_table`'s dict per branch and `centerlines.summary`, lengths in units of `pixel_size`.  The
-        prediction alone is read: uint8 [n, H, W]."""
+        prediction alone is read: uint8 [n, H, W].  `simplify`: a tolerance in pixels, the polylines thinned on the device
+        (centerlines.trace); lengths and widths stay those of the full branches."""
         from . import centerlines as _cl
         if not isinstance(pred, torch.Tensor) or pred.dtype != torch.uint8 or pred.dim() != 3:
             raise ValueError(f"pred must be a uint8 tensor [n, H, W], got {getattr(pred, 'dtype', type(pred).__name__)}")
         if classes is None:
             raise ValueError("classes must be a sequence of label values")
         _common.pixel_size(pixel_size)
+        if simplify is not None:
+            from .simplify import tol2_q8
+            tol2_q8(simplify)
         out = []
-        for per_class in _cl.trace(pred.to(self.device), classes=classes, route=route):
+        for per_class in _cl.trace(pred.to(self.device), classes=classes, route=route, simplify=simplify):
             out.append({c: dict(nodes=nd, branches=br, points=pts, table=_cl.branch_table(br, pixel_size, pts),
                                 summary=_cl.summary(nd, br, pixel_size)) for c, (nd, br, pts) in per_class.items()})
         return out

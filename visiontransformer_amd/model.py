@@ -567,31 +567,36 @@ class ViTSegmentationModel(nn.Module):
     @torch.no_grad()
     def predict_polygons(self, x: torch.Tensor, *, background: int = 0, connectivity: int = 4,
                          interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,
-                         max_hole_area: int = 0, return_mask: bool = False):
+                         max_hole_area: int = 0, return_mask: bool = False, simplify=None):
         """The outlines of the regions of each image's predicted mask: a list of (records, polygons) pairs, `records` the int32
         [k, 7] rows of `predict_regions`, `polygons[i]` the rings of region i as int32 [v, 2] arrays of (y, x) pixel corners,
         the outer ring first, then the holes (polygons.region_polygons).  The forward, the mask and the outlining are enqueued
         on one stream; the host waits once, for the counts.  `min_area` / `fill_holes` / `max_hole_area` (defaults: off): the
         outlines, and the mask returned, are those of the mask cleaned by clean.clean_mask with this call's `connectivity` and
-        `background`.  `return_mask`: also the uint8 [B, H, W] device mask."""
-        from . import clean as _clean, polygons as _polygons
+        `background`.  `return_mask`: also the uint8 [B, H, W] device mask.  `simplify`: a tolerance in pixels, the rings thinned
+        on the device before the copy back (polygons.region_polygons)."""
+        from . import clean as _clean, polygons as _polygons, simplify as _simplify
+        if simplify is not None:
+            _simplify.tol2_q8(simplify)   # before the forward
         mask = self.predict_mask(x, interpolate_pos_encoding=interpolate_pos_encoding)
         if min_area or fill_holes or max_hole_area:
             mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area,
                                      connectivity=connectivity, background=background)
-        out = _polygons.region_polygons(mask, background=background, connectivity=connectivity)
+        out = _polygons.region_polygons(mask, background=background, connectivity=connectivity, simplify=simplify)
         return (out, mask) if return_mask else out
 
     @torch.no_grad()
     def predict_centerlines(self, x: torch.Tensor, classes, *, route: str = "auto", background: int = 0, connectivity: int = 4,
                             interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,
-                            max_hole_area: int = 0, return_mask: bool = False):
+                            max_hole_area: int = 0, return_mask: bool = False, simplify=None):
         """The centre-line graph of the label values `classes` in each image's predicted mask: a list of dicts class ->
         (nodes, branches, points), the rows of centerlines.trace on the skeleton of {mask == class}.  `min_area` /
         `fill_holes` / `max_hole_area` (defaults: off): the graph, and the mask returned, are those of the mask cleaned by
         clean.clean_mask with this call's `connectivity` and `background`.  `return_mask`: also the uint8 [B, H, W] device
-        mask."""
-        from . import centerlines as _centerlines, clean as _clean
+        mask.  `simplify`: a tolerance in pixels, the polylines thinned on the device before the copy back (centerlines.trace)."""
+        from . import centerlines as _centerlines, clean as _clean, simplify as _simplify
+        if simplify is not None:
+            _simplify.tol2_q8(simplify)   # before the forward
         if classes is None:
             raise ValueError("classes must be a sequence of label values")
         _centerlines.check_options(classes, True, route)   # before the forward
@@ -600,7 +605,7 @@ class ViTSegmentationModel(nn.Module):
         if min_area or fill_holes or max_hole_area:
             mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area,
                                      connectivity=connectivity, background=background)
-        out = _centerlines.trace(mask, classes=classes, route=route)
+        out = _centerlines.trace(mask, classes=classes, route=route, simplify=simplify)
         return (out, mask) if return_mask else out
 
     @torch.no_grad()

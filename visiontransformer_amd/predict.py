@@ -73,7 +73,7 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
             tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0,
             return_props: bool = False, props_classes=None, pixel_size: float = 1.0, return_scores: bool = False,
             return_confidence: bool = False, score_kind: str = "prob", low: float = 0.5, return_polygons: bool = False,
-            return_centerlines: bool = False, centerline_classes=None):
+            return_centerlines: bool = False, centerline_classes=None, simplify=None):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
@@ -105,9 +105,17 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     then the holes.  It reads the mask alone, so it goes with `sliding` and `tta`.
     `return_centerlines`: also, last of all, the dict class -> (nodes, branches, points) of centerlines.trace for the label
     values `centerline_classes` (required) of the (cleaned) mask: the centre-line graph of each class's skeleton.  It reads the
-    mask alone as well."""
+    mask alone as well.
+    `simplify`: a tolerance in pixels for the outlines and the centre-lines (None: as they are traced): both are thinned on
+    the device before they are copied back (simplify.simplify_device).  ValueError without `return_polygons` or
+    `return_centerlines`."""
     from . import clean as _clean
     _clean.check_options(min_area, fill_holes, max_hole_area)
+    if simplify is not None:
+        from .simplify import tol2_q8
+        tol2_q8(simplify)
+        if not (return_polygons or return_centerlines):
+            raise ValueError("simplify needs return_polygons or return_centerlines: it thins their geometry")
     if return_centerlines:
         from . import centerlines as _centerlines
         if centerline_classes is None:
@@ -165,10 +173,10 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     polygons = None
     if return_polygons:
         from .polygons import region_polygons
-        polygons = region_polygons(mask_dev)
+        polygons = region_polygons(mask_dev, simplify=simplify)
     graph = None
     if return_centerlines:
-        graph = _centerlines.trace(mask_dev, classes=centerline_classes)
+        graph = _centerlines.trace(mask_dev, classes=centerline_classes, simplify=simplify)
     mask = mask_dev.cpu().numpy()
     res = [mask]
     if index_to_color is not None:

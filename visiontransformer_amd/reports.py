@@ -9,6 +9,7 @@ from collections import namedtuple
 from typing import Optional, Sequence
 
 from . import centerlines, confidence, polygons
+from .simplify import tol2_q8
 from ._common import write_csv
 from .metrics import (CRACK_CSV_COLUMNS, DISTANCE_CSV_COLUMNS, REGION_CSV_COLUMNS, crack_csv_row, distance_csv_row,
                       matches_from_stats, pool_region_stats, region_csv_row)
@@ -182,10 +183,17 @@ class RegionProps(Report):
 class Outlines(Report):
     """polygons_path: the outlines of every predicted region (polygons.region_polygons at region_connectivity, coordinates in
     units of props_pixel_size) as one GeoJSON FeatureCollection, each feature carrying its image as image_id "<batch>/<index>"
-    and its batch_num / image_idx."""
+    and its batch_num / image_idx.  `simplify`: a tolerance in pixels, the rings thinned on the device; the features then also
+    carry simplify_tolerance and vertices_full."""
+
+    def __init__(self, path=None, simplify=None):
+        super().__init__(path)
+        if simplify is not None:
+            tol2_q8(simplify)
+        self.simplify = simplify
 
     def add(self, b: Batch) -> None:
-        for idx, (rec, rings) in enumerate(polygons.region_polygons(b.mask, connectivity=b.connectivity)):
+        for idx, (rec, rings) in enumerate(polygons.region_polygons(b.mask, connectivity=b.connectivity, simplify=self.simplify)):
             found = polygons.polygons_to_geojson(rec, rings, pixel_size=b.pixel_size, image_id=f"{b.bn}/{idx}")["features"]
             self.rows += _tagged(found, b, idx)
 
@@ -196,15 +204,19 @@ class Outlines(Report):
 class CrackGraph(Report):
     """crack_graph_classes: the centre-line graph of each class (Evaluator.crack_graph, lengths and coordinates in units of
     props_pixel_size) as one FeatureCollection of LineStrings, tagged like the outlines, and as a CSV file: one row per branch,
-    then a summary row per image and class."""
+    then a summary row per image and class.  `simplify`: a tolerance in pixels, the polylines thinned on the device; the
+    features then also carry simplify_tolerance and vertices_full, the CSV rows the kept point count."""
     suffix, columns = "_crack_branches.csv", centerlines.CSV_COLUMNS
 
-    def __init__(self, classes, graph_path=None, path=None):
+    def __init__(self, classes, graph_path=None, path=None, simplify=None):
         super().__init__(path, centerlines.check_options(classes))
-        self.graph_path, self.lines = graph_path, []
+        if simplify is not None:
+            tol2_q8(simplify)
+        self.graph_path, self.lines, self.simplify = graph_path, [], simplify
 
     def add(self, b: Batch) -> None:
-        for idx, per_class in enumerate(b.ev.crack_graph(b.mask, self.classes, pixel_size=b.pixel_size)):
+        kw = {} if self.simplify is None else dict(simplify=self.simplify)
+        for idx, per_class in enumerate(b.ev.crack_graph(b.mask, self.classes, pixel_size=b.pixel_size, **kw)):
             for c, g in per_class.items():
                 found = centerlines.centerlines_to_geojson(g["branches"], g["points"], pixel_size=b.pixel_size,
                                                            image_id=f"{b.bn}/{idx}", class_id=c)["features"]

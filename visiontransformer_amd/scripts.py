@@ -12,6 +12,7 @@ from typing import List, Optional
 import torch
 
 from . import clean, reports, synth
+from . import simplify as _simplify
 from .metrics import Evaluator, csv_row, write_metrics_csv
 from .tta import parse_sizes
 
@@ -287,12 +288,26 @@ def add_evaluation_arguments(ap) -> None:
     add_confidence_arguments(ap)
     add_polygon_arguments(ap)
     add_crack_graph_arguments(ap)
+    ap.add_argument("--simplify", type=float, metavar="TOL",
+                    help="thin the rings of --region-polygons and the polylines of --crack-graph on the device before they are "
+                         "written (Douglas-Peucker, tolerance TOL in pixels; ends, ring starts and areas are kept); the features "
+                         "gain simplify_tolerance and vertices_full")
 
 
 def evaluation_options(ap, a, csv_path: str) -> dict:
     """The keywords of `evaluate_to_csv` from the flags of `add_evaluation_arguments`, for the metrics file `csv_path`;
-    `confidence_options`' refusals go through ap.error."""
-    return dict(distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None,
+    `confidence_options`' refusals go through ap.error, and so does --simplify without --region-polygons or --crack-graph or
+    with a tolerance `simplify.tol2_q8` refuses.  `simplify_tolerance` is in the dict only when the flag is given."""
+    thin = {}
+    if getattr(a, "simplify", None) is not None:
+        if not a.region_polygons and a.crack_graph is None:
+            ap.error("--simplify thins the geometry of --region-polygons and --crack-graph: give one of them")
+        try:
+            _simplify.tol2_q8(a.simplify)
+        except ValueError as e:
+            ap.error(f"--simplify: {e}")
+        thin = dict(simplify_tolerance=a.simplify)
+    return dict(**thin, distance_mode=a.distance_metrics, crack_classes=True if a.crack_metrics else None,
                 tta=a.tta, tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge,
                 region_classes=True if a.region_metrics else None, region_iou=a.region_iou, region_coverage=a.region_coverage,
                 region_connectivity=a.region_connectivity, props_classes=parse_props_classes(a.region_props),
@@ -309,7 +324,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                     region_scores: bool = False, score_kind: str = "prob", score_low: float = 0.5,
                     calibration_bins: Optional[int] = None, scores_csv_path: Optional[str] = None,
                     calibration_csv_path: Optional[str] = None, polygons_path: Optional[str] = None, crack_graph_classes=None,
-                    crack_graph_path: Optional[str] = None, crack_branches_csv_path: Optional[str] = None) -> List[list]:
+                    crack_graph_path: Optional[str] = None, crack_branches_csv_path: Optional[str] = None,
+                    simplify_tolerance=None) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image; returns those rows.  Predictions and class
@@ -326,7 +342,11 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
       calibration_bins, score_kind            reports.Calibration (ValueError with tta)
       props_classes (also "all")              reports.RegionProps
       polygons_path                           reports.Outlines
-      crack_graph_classes                     reports.CrackGraph"""
+      crack_graph_classes                     reports.CrackGraph
+      simplify_tolerance                      the rings / polylines of the two above thinned on the device (pixels; ValueError
+                                              without either)"""
+    if simplify_tolerance is not None and polygons_path is None and crack_graph_classes is None:
+        raise ValueError("simplify_tolerance needs polygons_path or crack_graph_classes: it thins their geometry")
     min_area, fill_holes, max_hole_area = clean.check_options(min_area, fill_holes, max_hole_area)
     if region_scores or calibration_bins is not None:
         reports.check_scoring(tta, score_kind, score_low)
@@ -341,8 +361,9 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         reports.RegionScores(model_info, score_kind, score_low, regions, scores_csv_path) if region_scores else None,
         reports.Calibration(model_info, calibration_bins, score_kind, calibration_csv_path) if calibration_bins is not None else None,
         reports.RegionProps(props_csv_path, props_classes) if props_classes is not None else None,
-        reports.Outlines(polygons_path) if polygons_path is not None else None,
-        reports.CrackGraph(crack_graph_classes, crack_graph_path, crack_branches_csv_path) if crack_graph_classes is not None else None,
+        reports.Outlines(polygons_path, simplify_tolerance) if polygons_path is not None else None,
+        reports.CrackGraph(crack_graph_classes, crack_graph_path, crack_branches_csv_path,
+                           simplify_tolerance) if crack_graph_classes is not None else None,
     ]
     active = [r for r in active if r is not None]
     seg = getattr(model, "model", model)
