@@ -425,31 +425,33 @@ def test_bf16_training_step_close_to_reference(name):
     print(f"{name}: bf16 vs fp32 gradients, worst per-tensor relative L2 error {worst:.3e}, worst cosine {worst_cos:.5f}")
 
 
-def _dropout_case():
-    cfg = ViTSegConfig(3, 16, 192, 2, 3, image_size=96)
+def _dropout_case(image_size=96):
+    cfg = ViTSegConfig(3, 16, 192, 2, 3, image_size=image_size)
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(cfg, seed=61).items()}
     x = torch.from_numpy(synth.make_images(cfg, 2, seed=8))
-    y = torch.from_numpy(synth.make_targets(cfg, 2, seed=8, size=96))
+    y = torch.from_numpy(synth.make_targets(cfg, 2, seed=8, size=image_size))
     return cfg, sd, x, y
 
 
+@pytest.mark.parametrize("image_size", [96, 208, 224])   # Np = 36 (below one key block), 169 and 196 (ragged, above one)
 @pytest.mark.parametrize("route", ["small", "large"])
-def test_dropout_training_step_matches_oracle_with_identical_masks(route):
+def test_dropout_training_step_matches_oracle_with_identical_masks(route, image_size):
     """Train-mode dropout (p = 0.1 at the four HF sites).  torch's RNG stream cannot be matched, but the build's
     masks are a pure function of (seed, layer, site, element): tests/dropout_ref.py regenerates them in numpy and
     injects them into the oracle, so forward AND backward can be compared exactly like the p = 0 case.  Both routes of the
-    fp32 step (small-batch kernels / `no_small`: large-batch kernels) draw the same masks."""
+    fp32 step (small-batch kernels / `no_small`: large-batch kernels) draw the same masks.  At the larger sizes `no_small` is the
+    only way the fp32 large-batch attention pair with dropout meets injected masks at a ragged length above one key block."""
     from dropout_ref import Masks
     from visiontransformer_amd.params import arena_views
-    cfg, sd, x, y = _dropout_case()
-    m = ViTSegmentationModel(3, 16, 192, 2, 3, image_size=96, dropout=0.1, device=DEV).train()
+    cfg, sd, x, y = _dropout_case(image_size)
+    m = ViTSegmentationModel(3, 16, 192, 2, 3, image_size=image_size, dropout=0.1, device=DEV).train()
     m.load_state_dict(sd)
     seed64 = (m.dropout_seed * 0x9E3779B97F4A7C15 + 1 * 0x100000001B3 + 0) & (2 ** 64 - 1)  # first training forward
     with _lib.option("no_small", int(route == "large")):
         loss = m.ce_loss(x.to(DEV), y.to(DEV))
         loss.backward()
     masks = Masks(0.1, seed64, 2, cfg.num_patches, 3)
-    assert abs(float((masks.rows(0, 0, (2, 37, 192)) > 0).float().mean()) - 0.9) < 0.01
+    assert abs(float((masks.rows(0, 0, (2, cfg.num_patches + 1, 192)) > 0).float().mean()) - 0.9) < 0.01
     leaf = {k: v.double().requires_grad_(True) for k, v in sd.items()}
     ref = O.ce_loss(O.forward(x.double(), leaf, cfg, drop=masks), y)
     ref.backward()
@@ -689,15 +691,19 @@ def test_attention_backward_bf16(B, Np, A, p):
         mk = Masks(p, seed, B, Np, A)
         mask = mk.attn(3, (B, A, N, N)).double()      # reference token order (CLS first), layer 3 -> stream 3 * 8 + 1
     ctx_ref = torch.empty(Mt, D, dtype=torch.float64)
+    lse_ref = torch.empty(B, A, N, dtype=torch.float64)
     outs = []
     for b in range(B):
         r = torch.cat([torch.tensor([B * Np + b]), torch.arange(b * Np, (b + 1) * Np)])
         q, k, v = [x[r][:, i * D:(i + 1) * D].reshape(N, A, 64).transpose(0, 1) for i in range(3)]
-        s = torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1)
+        sc = q @ k.transpose(-1, -2) * 0.125
+        s = torch.softmax(sc, dim=-1)
         if mask is not None:
             s = s * mask[b]
         o = (s @ v).transpose(0, 1).reshape(N, D)
         ctx_ref[r] = o.detach()
+        l2 = torch.logsumexp(sc.detach(), dim=-1) * 1.4426950408889634           # [A, N] reference order, log2 domain
+        lse_ref[b] = torch.cat([l2[:, 1:], l2[:, :1]], dim=1)                    # kernel order: CLS last
         outs.append((o * dctx.double()[r]).sum())
     torch.stack(outs).sum().backward()
     qd, dd = _dev(qkv, name="qkv"), _dev(dctx, name="dctx")
@@ -728,6 +734,10 @@ def test_attention_backward_bf16(B, Np, A, p):
     _after(snap, ctx, lse, scr, dqkv2, mw)
     assert torch.equal(dqkv.view(torch.int16), dqkv2.view(torch.int16))
     assert (ctx.float().cpu().double() - ctx_ref).abs().max().item() < 4e-2
+    # the log-sum-exp the backward rebuilds P from: fp32 out of exact products of bf16 values and fp32 sums, held to the fp32
+    # gate of test_attention_small_forward_and_backward_for_training (tests/test_gpu_attention_keys.py LSE_GATE)
+    lse_err = (lse.cpu().double().view(B, A, N) - lse_ref).abs().max().item()
+    assert lse_err < 2e-5, lse_err
     # P, dS and the outputs are rounded to bf16 (2^-9): a few 1e-3 relative to the gradient scale, per slot
     for i, name in enumerate(("dq", "dk", "dv")):
         a, r_ = got[:, i * D:(i + 1) * D], ref[:, i * D:(i + 1) * D]

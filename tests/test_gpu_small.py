@@ -258,7 +258,9 @@ def test_attention_small(B, Np, A):
 
 
 @pytest.mark.parametrize("f16", [0, 1])
-@pytest.mark.parametrize("B,Np,A", [(1, 196, 12), (4, 196, 3), (2, 784, 2), (3, 16, 2), (2, 127, 1)])
+@pytest.mark.parametrize("B,Np,A", [(1, 196, 12), (4, 196, 3), (2, 784, 2), (3, 16, 2), (2, 127, 1),
+                                    # the ragged lengths of test_attention_small: below one block, either side of 128, the last short one
+                                    (1, 4, 1), (1, 31, 1), (2, 129, 2), (1, 200, 3), (1, 399, 1)])
 def test_attention_small_16bit_form(B, Np, A, f16):
     """The key-split attention kernel with its products on the wide MFMA (q, k, P, v rounded to bf16 / fp16 in registers; fp32
     softmax and accumulation), as the 16-bit form of the route runs it: against fp64 attention on the fp32 inputs within the
