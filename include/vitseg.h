@@ -58,7 +58,7 @@ typedef struct vitseg_config {
                                 * VITSEG_F16, whose GEMMs step K in 64-value slices: other values give VITSEG_ESHAPE
                                 * from vitseg_query_workspace, vitseg_train_workspace and every entry point) */
     int32_t num_channels;      /* 3 */
-    float layer_norm_eps;      /* 1e-12, configuration_vit.py:58 */
+    float layer_norm_eps;      /* 1e-12, configuration_vit.py:58; any finite value >= 0 (timm checkpoints: 1e-6), else VITSEG_EINVAL */
 } vitseg_config;
 
 /* Parameter tensors, in arena order.  Per-layer tensors take a layer index. */
@@ -788,6 +788,13 @@ int vitseg_op_attention_bwd_bf16(const void* qkv, const void* dctx, void* ctx_ou
 size_t vitseg_op_layernorm_bwd_scratch_floats(int rows, int D);
 int vitseg_op_layernorm_bwd_f32(const float* x, const float* w, const float* g, const float* dres_in, float* dres_out,
                                 float* dw, float* db, float* scratch, int rows, int D, float eps, void* stream);
+/* the form the bf16 training step uses: g as bf16 [rows, D], the same fp32 arithmetic.  br_out != NULL (needs br_dbias): also
+ * the gradient entering the NEXT dropped residual branch of the backward walk, as the bf16 operand of that branch's GEMMs --
+ * br_out [rows, D] = bf16(mask * dres_out) (hidden dropout of csrc/common.hpp with the given stream id; dropout_p == 0: no mask)
+ * and br_dbias [D] = the column sums of the ROUNDED values.  br_out == NULL: br_dbias must be NULL and dropout_p 0. */
+int vitseg_op_layernorm_bwd_bf16(const float* x, const float* w, const void* g, const float* dres_in, float* dres_out,
+                                 float* dw, float* db, float* scratch, int rows, int D, float eps, void* br_out, float* br_dbias,
+                                 float dropout_p, uint32_t dropout_seed, uint32_t dropout_stream, void* stream);
 /* the form the fp32 training step of the small-batch route uses (same arithmetic and bits for dres_out / dw / db): g arrives as
  * g_splits K-chunk slabs, g = slab 0 + slab 1 + ... (slab s at g + s * g_stride floats; 1 = plain); br_dbias != NULL: also the
  * gradient entering the NEXT dropped residual branch of the backward walk -- br_out = mask * dres_out (written only when

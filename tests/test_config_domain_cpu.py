@@ -109,6 +109,28 @@ def test_limit_edges():
     assert _lib.query_workspace(cfg(C=255, A=32, I=8192), 1, _lib.BF16) > 0   # inference keeps the whole domain
 
 
+def test_layer_norm_eps_domain():
+    """`check_config` takes any finite eps >= 0 (0 as torch.nn.LayerNorm does, -0.0 is 0) and refuses a NaN, an infinite or a
+    negative one with VITSEG_EINVAL -- in every query that checks a config, before anything is sized or launched."""
+    import dataclasses
+    import math
+    base = ViTSegConfig(2, 16, 128, 2, 2, image_size=64, intermediate_size=256)
+    for eps in (0.0, -0.0, 1e-45, 1e-12, 1e-6, 1e-5, 1.0, 100.0, 3.0e38):
+        cfg = dataclasses.replace(base, layer_norm_eps=eps)
+        assert _lib.param_count(cfg) == _lib.param_count(base)
+        assert _lib.query_workspace(cfg, 2, _lib.BF16) == _lib.query_workspace(base, 2, _lib.BF16)
+        assert _lib.train_workspace(cfg, 2, _lib.F32) == _lib.train_workspace(base, 2, _lib.F32)
+    for eps in (math.nan, math.inf, -math.inf, -1e-45, -1e-12, -1.0):
+        cfg = dataclasses.replace(base, layer_norm_eps=eps)
+        for query in (lambda: _lib.param_count(cfg), lambda: _lib.query_workspace(cfg, 2, _lib.F32),
+                      lambda: _lib.query_workspace(cfg, 2, _lib.F16, image_size=128), lambda: _lib.train_workspace(cfg, 2, _lib.BF16)):
+            with pytest.raises(RuntimeError, match="layer_norm_eps"):
+                query()
+        c = _lib.CConfig.from_config(cfg)
+        n = C.c_size_t(0)
+        assert _lib.lib().vitseg_param_count(C.byref(c), C.byref(n)) == _lib.EINVAL
+
+
 @pytest.mark.parametrize("precision", [_lib.F32, _lib.BF16])
 def test_backward_refuses_bad_loss_arguments_before_any_launch(precision):
     """`vitseg_backward` needs exactly one of `target` (fused CE) and `grad_logits`, and `loss` with `target`.  Both

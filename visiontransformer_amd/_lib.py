@@ -209,6 +209,7 @@ SIGNATURES = {
         ("vitseg_op_transpose_layers_bf16", i32, [vp, vp, psz, pint, pint, sz, i32, vp]),
         ("vitseg_op_dropout_rows", i32, [vp, vp, i32, i32, i32, f32, u32, u32, vp]),
         ("vitseg_op_layernorm_h16", i32, [vp, vp, vp, vp, i32, i32, f32, i32, vp]),
+        ("vitseg_op_layernorm_bwd_bf16", i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, f32, u32, u32, vp]),
     ]),
     # sliding-window inference (model.predict_mask_windowed): the window grid, the tile gather, the forward that stops at the
     # low-res head output and the overlapping-tile blend

@@ -30,6 +30,9 @@ inline int check_config(const vitseg_config* c, Shape* s) {
                      "intermediate_size %d must be a multiple of 4", c->intermediate_size);
     VITSEG_CHECK_ARG(c->num_layers >= 1, VITSEG_ESHAPE, "num_layers %d", c->num_layers);
     VITSEG_CHECK_ARG(c->num_channels == 3, VITSEG_ESHAPE, "num_channels %d (reference: 3)", c->num_channels);
+    // 0 is valid (torch.nn.LayerNorm takes it); the comparison is false for a NaN
+    VITSEG_CHECK_ARG(c->layer_norm_eps >= 0.f && c->layer_norm_eps <= 3.402823466e38f, VITSEG_EINVAL,
+                     "layer_norm_eps %g must be finite and >= 0", (double)c->layer_norm_eps);
     s->C = c->num_classes;
     s->P = c->patch_size;
     s->D = c->hidden_size;

@@ -565,6 +565,16 @@ int vitseg_op_layernorm_bwd_f32(const float* x, const float* w, const float* g, 
                                 float* dw, float* db, float* scratch, int rows, int D, float eps, void* stream) {
     return launch_layernorm_bwd(x, w, g, 0, dres_in, dres_out, dw, db, scratch, rows, D, eps, (hipStream_t)stream);
 }
+// the bf16 training step's form: g as bf16; br_out != NULL: the next branch's dropped bf16 gradient + its bias gradient
+int vitseg_op_layernorm_bwd_bf16(const float* x, const float* w, const void* g, const float* dres_in, float* dres_out,
+                                 float* dw, float* db, float* scratch, int rows, int D, float eps, void* br_out, float* br_dbias,
+                                 float dropout_p, uint32_t dropout_seed, uint32_t dropout_stream, void* stream) {
+    VITSEG_CHECK_ARG(x && w && g && dres_out && dw && db && scratch && rows > 0, VITSEG_EINVAL, "layernorm_bwd_bf16: bad arguments");
+    VITSEG_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, VITSEG_EINVAL, "layernorm_bwd_bf16: dropout_p %f", dropout_p);
+    VITSEG_CHECK_ARG(br_out || (!br_dbias && dropout_p == 0.f), VITSEG_EINVAL, "layernorm_bwd_bf16: br_dbias / dropout_p need br_out");
+    const DropArgs d = drop_args(dropout_p, dropout_seed, dropout_stream);
+    return launch_layernorm_bwd(x, w, g, 1, dres_in, dres_out, dw, db, scratch, rows, D, eps, (hipStream_t)stream, br_out, d, br_dbias);
+}
 // the small-batch training step's form: g as K-chunk slabs, the next branch's dropped gradient + bias gradient (small.hpp)
 int vitseg_op_layernorm_bwd_f32_small(const float* x, const float* w, const float* g, size_t g_stride, int g_splits,
                                       const float* dres_in, float* dres_out, float* dw, float* db, float* scratch, int rows,

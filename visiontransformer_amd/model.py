@@ -147,10 +147,11 @@ class _CEDiceLossFn(torch.autograd.Function):
 class ViTSegmentationModel(nn.Module):
     def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, *,
                  image_size: int = 224, intermediate_size: int = 3072, precision: str = "fp32",
-                 dropout: float = 0.1, device=None):
+                 dropout: float = 0.1, layer_norm_eps: float = 1e-12, device=None):
         super().__init__()
+        # layer_norm_eps: 1e-12 is the reference's (configuration_vit.py:58); a checkpoint trained with another (timm: 1e-6) sets it
         self.cfg = ViTSegConfig(num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads,
-                                image_size=image_size, intermediate_size=intermediate_size)
+                                image_size=image_size, intermediate_size=intermediate_size, layer_norm_eps=float(layer_norm_eps))
         self.precision = _PRECISION[precision]
         # hidden_dropout_prob = attention_probs_dropout_prob = 0.1 in the reference (classes.py:233-234); active only
         # in train() mode with autograd on, like nn.Dropout.  `dropout_seed` + a step counter select the masks.
