@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--data")
     scripts.add_ce_loss_arguments(ap)
     scripts.add_augment_arguments(ap)
+    scripts.add_optim_arguments(ap)
     ap.add_argument("--ckpt-dir", default="logs/vit-model/version_0/checkpoints")
     ap.add_argument("--resume")
     a = ap.parse_args()
@@ -37,7 +38,7 @@ def main():
     torch.cuda.set_device(local)
     P, D, L, A = CONFIGURATIONS[a.model_id]
     model = LightningViTModel(a.num_classes, P, D, L, A, image_size=a.image_size, device=dev,
-                              **scripts.ce_loss_options(a))
+                              **scripts.ce_loss_options(a), **scripts.optim_options(a))
     cfg = model.model.cfg
     model.augment = scripts.augmenter_from_args(a, cfg, dev)
     if a.data:
@@ -50,6 +51,7 @@ def main():
     lo, hi = vdist.shard_range(xs.shape[0], rank, world)
     xs, ys = xs[lo:hi], ys[lo:hi]
     batches = [(xs[i:i + a.batch_size], ys[i:i + a.batch_size]) for i in range(0, xs.shape[0], a.batch_size)]
+    scripts.set_total_steps(model, a.epochs, len(batches), 4)
     rows = trainer.fit(model, batches, batches, max_epochs=a.epochs, accumulate_grad_batches=4, patience=a.patience,
                        ckpt_dir=a.ckpt_dir, log_dir="logs/vit-model/version_0", resume_from=a.resume, device=dev)
     if rank == 0:

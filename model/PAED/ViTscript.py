@@ -32,15 +32,17 @@ def main():
     ap.add_argument("--exact-sdf", action="store_true",
                     help="exact SDFs of the synthetic masks (vitseg_sdf) instead of smooth stand-ins")
     scripts.add_augment_arguments(ap)
+    scripts.add_optim_arguments(ap)
     a = ap.parse_args()
     rank, world, local = vdist.init()
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
     model = PAEDTrainer(1, a.patch_size, a.hidden_size, a.layers, a.heads, image_size=a.image_size, precision=a.precision,
-                        device=dev)
+                        device=dev, **scripts.optim_options(a))
     model.augment = scripts.augmenter_from_args(a, model.model.cfg, dev)
     batches = scripts.paed_binary_batches(model.model.cfg, a.batches * a.batch_size, a.batch_size, a.data, seed=rank,
                                           sdf="exact" if a.exact_sdf else "standin")
+    scripts.set_total_steps(model, a.epochs, len(batches), 4)
     log_dir = f"logs/vit-model/version_{a.version}"
     trainer.fit(model, batches, batches, max_epochs=a.epochs, accumulate_grad_batches=4, patience=6,
                 ckpt_dir=log_dir + "/checkpoints", log_dir=log_dir, device=dev)

@@ -29,14 +29,16 @@ def main():
     ap.add_argument("--resume", help="checkpoint to continue from (default: the latest of --version, if any)")
     ap.add_argument("--data")
     scripts.add_augment_arguments(ap)
+    scripts.add_optim_arguments(ap)
     a = ap.parse_args()
     rank, world, local = vdist.init()
     dev = f"cuda:{local}"
     torch.cuda.set_device(local)
     model = LightningViTModel(17, a.patch_size, a.hidden_size, a.layers, a.heads, image_size=a.image_size,
-                              precision=a.precision, device=dev)
+                              precision=a.precision, device=dev, **scripts.optim_options(a))
     model.augment = scripts.augmenter_from_args(a, model.model.cfg, dev)
     batches = scripts.ce_batches(model.model.cfg, a.batches * a.batch_size, a.batch_size, a.data, first=rank * a.batches * a.batch_size)
+    scripts.set_total_steps(model, a.epochs, len(batches), 1)
     log_dir = f"logs/vit-model/version_{a.version}"
     resume = a.resume or scripts.get_latest_checkpoint(a.version, os.getcwd())
     rows = trainer.fit(model, batches, batches, max_epochs=a.epochs, accumulate_grad_batches=1, patience=5,

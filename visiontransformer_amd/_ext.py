@@ -14,11 +14,12 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _lib
-from ._lib import i32, i64, sz, vp
+from ._lib import f32, i32, i64, sz, vp
 
 POLYGONS_VERSION = 100   # include/vitseg_polygons.h VITSEG_POLYGONS_VERSION this binding was written against
 CENTERLINES_VERSION = 100   # include/vitseg_centerlines.h VITSEG_CENTERLINES_VERSION
 SIMPLIFY_VERSION = 100   # include/vitseg_simplify.h VITSEG_SIMPLIFY_VERSION
+OPTIM_VERSION = 100   # include/vitseg_optim.h VITSEG_OPTIM_VERSION
 
 EXT_SIGNATURES = {
     # region outlines: polygon rings with holes (polygons.py)
@@ -43,10 +44,20 @@ EXT_LATER = {
         ("vitseg_simplify_scratch_bytes", sz, [i32, i32, i64]),
         ("vitseg_simplify_lines", i32, [vp, i64, i32, vp, i32, i32, i32, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, sz, vp]),
     ]),
+    # Adam / AdamW over the arena with groups by chunk, clipping, step skip and a weight EMA (optim.py)
+    "optim": ("vitseg_optim.h", "the fine-tuning optimiser", [
+        ("vitseg_optim_version", i32, []),
+        ("vitseg_optim_scratch_bytes", sz, [sz, i32]),
+        ("vitseg_optim_check_groups", i32, [vp, i32, vp, sz]),
+        ("vitseg_optim_grad_norm", i32, [vp, sz, vp, vp, i32, f32, vp, sz, vp]),
+        ("vitseg_optim_prepare", i32, [vp, vp, i32, sz, i32, f32, f32, f32, f32, f32, vp, sz, vp]),
+        ("vitseg_optim_step", i32, [vp, vp, vp, vp, vp, sz, vp, vp, f32, f32, f32, f32, f32, vp, sz, vp]),
+    ]),
 }
 EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
                 "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION),
-                "simplify": ("vitseg_simplify_version", SIMPLIFY_VERSION)}
+                "simplify": ("vitseg_simplify_version", SIMPLIFY_VERSION),
+                "optim": ("vitseg_optim_version", OPTIM_VERSION)}
 
 
 def ext_symbol(family: str, name: str):

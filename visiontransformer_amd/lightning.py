@@ -32,8 +32,14 @@ class LightningViTModel(nn.Module):
         `*_dice` beside `*_loss`.  With 0 the steps call exactly what they call without the argument.
         `augment`: an `augment.Augmenter`; the training step (alone) warps and colour-jitters the batch with it, the mask
         going straight to the input's size as the class bytes the fused loss reads (one launch, in place of `_resize_target`).
-        With None the steps launch exactly what they launch without the argument."""
+        With None the steps launch exactly what they launch without the argument.
+        `layer_decay`, `no_decay`, `freeze`, `head_lr_mult` (optim.arena_groups), `max_grad_norm`, `skip_nonfinite`, `ema_decay`
+        (optim.FusedAdam), `weight_decay` (FusedAdamW in place of FusedAdam), `warmup_steps` with `total_steps`
+        (optim.warmup_cosine, stepped per optimiser step): what `configure_optimizers` builds.  Without them it returns exactly
+        what it returns without the arguments."""
         super().__init__()
+        from .optim import pop_options
+        self.optim_options = pop_options(kw)
         self.model = ViTSegmentationModel(num_classes, patch_size, hidden_size, num_hidden_layers,
                                           num_attention_heads, **kw)
         self.interpolate_pos_encoding = bool(interpolate_pos_encoding)
@@ -105,7 +111,10 @@ class LightningViTModel(nn.Module):
         return loss
 
     def configure_optimizers(self):
-        from .optim import FusedAdam
+        from .optim import FusedAdam, configure
+        if self.optim_options:
+            opt, sched = configure(self.model, 1e-5, self.optim_options)
+            return opt if sched is None else {"optimizer": opt, "lr_scheduler": sched}
         return FusedAdam(self.parameters(), lr=1e-5)  # Adam(lr=1e-5), classes.py:296-297
 
     # checkpoint schema: every key prefixed with "model." like the reference module tree

@@ -172,8 +172,13 @@ def iou_score(preds, targets, num_classes=17):
 class _Base(nn.Module):
     def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, augment=None, **kw):
         """`augment`: an `augment.Augmenter` the training step (alone) applies to its batch; None: the steps launch exactly
-        what they launch without the argument."""
+        what they launch without the argument.
+        `layer_decay`, `no_decay`, `freeze`, `head_lr_mult`, `max_grad_norm`, `skip_nonfinite`, `ema_decay`, `weight_decay`,
+        `warmup_steps`, `total_steps`: the optimiser `configure_optimizers` builds (optim.configure); without them it returns
+        exactly what it returns without the arguments."""
         super().__init__()
+        from .optim import pop_options
+        self.optim_options = pop_options(kw)
         self.model = ViTSegmentationModel(num_classes, patch_size, hidden_size, num_hidden_layers,
                                           num_attention_heads, **kw)
         self.augment = augment
@@ -230,7 +235,10 @@ class LightningViTModel(_Base):
             return self._step(batch, "valid")
 
     def configure_optimizers(self):
-        from .optim import FusedAdam
+        from .optim import FusedAdam, configure
+        if self.optim_options:   # FusedAdamW when a weight_decay is given
+            opt, sched = configure(self.model, 1e-4, self.optim_options)
+            return opt if sched is None else {"optimizer": opt, "lr_scheduler": sched}
         return FusedAdam(self.parameters(), lr=1e-4)  # :486-487
 
 
@@ -268,8 +276,13 @@ class PAEDTrainer(_Base):
             return self._forward_step_paed(batch, batch_idx, "val")[0]
 
     def configure_optimizers(self):
-        from .optim import FusedAdamW
-        opt = FusedAdamW(self.model.parameters(), lr=1e-4)  # AdamW(lr=1e-4), :536-548 -- one launch over the arena
+        from .optim import FusedAdamW, configure
+        if self.optim_options:   # with warmup_steps the per-step warm-up + cosine takes the place of ReduceLROnPlateau
+            opt, sched = configure(self.model, 1e-4, self.optim_options, decoupled=True)
+            if sched is not None:
+                return {"optimizer": opt, "lr_scheduler": sched}
+        else:
+            opt = FusedAdamW(self.model.parameters(), lr=1e-4)  # AdamW(lr=1e-4), :536-548 -- one launch over the arena
         sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, patience=30)
         return {"optimizer": opt, "lr_scheduler": {"scheduler": sched, "monitor": "val_IoU", "interval": "epoch",
                                                    "frequency": 1}}

@@ -119,6 +119,63 @@ def augmenter_from_args(a, cfg, device):
     return Augmenter(cfg.image_size, device=device, seed=a.aug_seed, **kw)
 
 
+def add_optim_arguments(ap) -> None:
+    """The optimiser options of the training scripts (optim.arena_groups, optim.FusedAdam, optim.warmup_cosine)."""
+    ap.add_argument("--layer-decay", type=float, default=None,
+                    help="layer-wise learning-rate decay in (0, 1]: the head trains at the full rate, every layer below at this "
+                         "factor times the rate of the one above, the embeddings lowest")
+    ap.add_argument("--no-decay", nargs="?", const="default", default=None, metavar="LIST|default",
+                    help="no weight decay on these tensors: comma-separated among bias,norm,cls,pos (default: all four)")
+    ap.add_argument("--freeze", default=None, metavar="embeddings|backbone|K",
+                    help="do not train the embeddings, everything but the head, or the embeddings and the first K layers")
+    ap.add_argument("--head-lr-mult", type=float, default=None, help="the head's learning rate is this many times the base rate")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global L2 norm of the gradient to this")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="skip an optimiser step whose gradient norm is inf or NaN")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights with this decay; validation and ema_state_dict use it")
+    ap.add_argument("--weight-decay", type=float, default=None, help="AdamW's decoupled weight decay (FusedAdamW)")
+    ap.add_argument("--warmup-steps", type=int, default=None,
+                    help="optimiser steps of linear warm-up, followed by a cosine decay over the rest of the run")
+
+
+def optim_options(a, total_steps=None) -> dict:
+    """Keyword arguments for LightningViTModel / PAEDTrainer from the flags of `add_optim_arguments` (empty: the reference's
+    optimiser).  `total_steps`: the optimiser steps of the run, passed on with --warmup-steps."""
+    kw = {}
+    if a.layer_decay is not None:
+        kw["layer_decay"] = a.layer_decay
+    if a.no_decay is not None:
+        kw["no_decay"] = "default" if a.no_decay == "default" else tuple(t.strip() for t in a.no_decay.split(",") if t.strip())
+    if a.freeze is not None:
+        kw["freeze"] = int(a.freeze) if a.freeze.lstrip("-").isdigit() else a.freeze
+    if a.head_lr_mult is not None:
+        kw["head_lr_mult"] = a.head_lr_mult
+    if a.max_grad_norm is not None:
+        kw["max_grad_norm"] = a.max_grad_norm
+    if a.skip_nonfinite:
+        kw["skip_nonfinite"] = True
+    if a.ema_decay is not None:
+        kw["ema_decay"] = a.ema_decay
+    if a.weight_decay is not None:
+        kw["weight_decay"] = a.weight_decay
+    if a.warmup_steps is not None:
+        kw["warmup_steps"] = a.warmup_steps
+        if total_steps is not None:
+            kw["total_steps"] = int(total_steps)
+    return kw
+
+
+def optimizer_steps(epochs: int, batches_per_epoch: int, accumulate_grad_batches: int) -> int:
+    """The optimiser steps `trainer.fit` takes: one per accumulation window, the epoch's incomplete last window included."""
+    return int(epochs) * -(-int(batches_per_epoch) // int(accumulate_grad_batches))
+
+
+def set_total_steps(model, epochs: int, batches_per_epoch: int, accumulate_grad_batches: int) -> None:
+    """Tells a module built with --warmup-steps how long the run is, once its batches are known (before trainer.fit)."""
+    if "warmup_steps" in model.optim_options:
+        model.optim_options["total_steps"] = optimizer_steps(epochs, batches_per_epoch, accumulate_grad_batches)
+
+
 def ce_batches(cfg, n_images: int, batch_size: int, data: Optional[str] = None, seed: int = 0, first: int = 0):
     """[(images [b,3,S,S] float, masks [b,256,256] long)]: StructuralDamageDataset items (model/CE/classes.py:60-89)."""
     if data:

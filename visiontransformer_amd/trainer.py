@@ -8,6 +8,9 @@ accumulated locally over the micro-batches of an optimizer step and summed over 
 (`model.no_sync()` around the others, as DDP's no_sync).  Checkpoints carry the optimizer state (Adam moments and step
 count, Lightning's `optimizer_states`), so a resumed run continues with the update the uninterrupted run would have made.
 No per-step host synchronisation: losses stay device scalars until the epoch's row is written.
+A scheduler whose Lightning dict says `"interval": "step"` (optim.warmup_cosine) is stepped after every optimiser step and
+travels in the checkpoint (`lr_schedulers`); with an optimiser that keeps an EMA of the weights (optim.FusedAdam(ema_decay=))
+validation runs on the EMA weights (`swap_ema`) and the checkpoint gains `ema_state_dict`.
 """
 from __future__ import annotations
 
@@ -36,6 +39,8 @@ def fit(model, train_batches: Iterable, val_batches: Optional[Iterable] = None, 
         opt = opt["optimizer"]
     from .optim import FusedAdam
     fused = isinstance(opt, FusedAdam)             # its step() folds the 1 / world of data parallelism into the kernel
+    per_step = sched is not None and sched.get("interval") == "step"
+    has_ema = fused and opt.ema_decay is not None
     net = getattr(model, "model", model)           # the ViTSegmentationModel that owns the arena
     start_epoch, step = 0, 0
     if resume_from:
@@ -47,6 +52,8 @@ def fit(model, train_batches: Iterable, val_batches: Optional[Iterable] = None, 
                 for k, v in st.items():
                     if torch.is_tensor(v):
                         st[k] = v.to(device)
+        if per_step and ck.get("lr_schedulers"):
+            sched["scheduler"].load_state_dict(ck["lr_schedulers"][0])
         start_epoch, step = int(ck.get("epoch", -1)) + 1, int(ck.get("global_step", 0))
     rows, best, bad = [], float("inf"), 0
     takes_scale = "grad_scale" in inspect.signature(model.training_step).parameters
@@ -80,6 +87,8 @@ def fit(model, train_batches: Iterable, val_batches: Optional[Iterable] = None, 
                     if world > 1:
                         net.arena.grad.mul_(1.0 / world)
                     opt.step()
+                if per_step:
+                    sched["scheduler"].step()
                 opt.zero_grad(set_to_none=True)
                 step += 1
                 pending.append(dict(epoch=epoch, step=step, train_loss_step=ld))
@@ -89,14 +98,15 @@ def fit(model, train_batches: Iterable, val_batches: Optional[Iterable] = None, 
         row = dict(epoch=epoch, step=step, train_loss_epoch=(float(ep_loss) / n_micro if n_micro else 0.0))
         if val_batches is not None:
             model.eval()
-            vs = [model.validation_step(tuple(t.to(device) for t in batch), i) for i, batch in enumerate(val_batches)]
+            with (opt.swap_ema() if has_ema else contextlib.nullcontext()):   # evaluate the EMA weights
+                vs = [model.validation_step(tuple(t.to(device) for t in batch), i) for i, batch in enumerate(val_batches)]
             v = float(torch.stack([t.detach().float().reshape(()) for t in vs]).mean()) if vs else 0.0
             if world > 1:
                 t = torch.tensor([v], device=device)
                 dist.all_reduce(t)
                 v = float(t) / world
             row["valid_loss"] = v
-            if sched is not None:
+            if sched is not None and not per_step:
                 sched["scheduler"].step(v)
         rows.append(row)
         if rank == 0 and ckpt_dir:
@@ -104,9 +114,14 @@ def fit(model, train_batches: Iterable, val_batches: Optional[Iterable] = None, 
             osd = opt.state_dict()
             osd = {"state": {k: {kk: (vv.cpu() if torch.is_tensor(vv) else vv) for kk, vv in st.items()}
                              for k, st in osd["state"].items()}, "param_groups": osd["param_groups"]}
-            torch.save({"state_dict": {k: t.cpu() for k, t in model.state_dict().items()}, "epoch": epoch,
-                        "global_step": step, "optimizer_states": [osd]},
-                       os.path.join(ckpt_dir, f"epoch={epoch}-step={step}.ckpt"))
+            ck = {"state_dict": {k: t.cpu() for k, t in model.state_dict().items()}, "epoch": epoch,
+                  "global_step": step, "optimizer_states": [osd]}
+            if per_step:
+                ck["lr_schedulers"] = [sched["scheduler"].state_dict()]
+            if has_ema:
+                with opt.swap_ema():
+                    ck["ema_state_dict"] = {k: t.cpu() for k, t in model.state_dict().items()}
+            torch.save(ck, os.path.join(ckpt_dir, f"epoch={epoch}-step={step}.ckpt"))
         if rank == 0 and log_dir:
             os.makedirs(log_dir, exist_ok=True)
             cols = ["epoch", "step", "train_loss_step", "train_loss_epoch", "valid_loss"]
