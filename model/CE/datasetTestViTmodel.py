@@ -6,6 +6,7 @@ write test/<model>/<model>_metrics.csv (per-image accuracy / mean IoU / mean Dic
 the schema model/CE/compareModels.py:27-47 reads.  Plots are host-side reporting and not produced.
 
     python model/CE/datasetTestViTmodel.py --ids 1 --num-classes 17 --num-batches 3 [--data eval.pt]
+    ... --pr-curve 1 --pr-tolerance 2       # also <model>_pr_curve.csv: class 1's precision-recall curve, ODS, OIS, AP
 """
 import argparse
 import os

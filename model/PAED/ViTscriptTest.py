@@ -5,6 +5,7 @@ model.eval(), logits.sigmoid(), argmax over the class dim (:184-193), per-image 
 the time per image into test/<model>/<model>_metrics.csv.
 
     python model/PAED/ViTscriptTest.py --ids 0 --num-batches 3
+    ... --pr-curve 0 --pr-tolerance 2       # also <model>_pr_curve.csv: the crack class' precision-recall curve, ODS, OIS, AP
 """
 import argparse
 import os

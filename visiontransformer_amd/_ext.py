@@ -20,6 +20,7 @@ POLYGONS_VERSION = 100   # include/vitseg_polygons.h VITSEG_POLYGONS_VERSION thi
 CENTERLINES_VERSION = 100   # include/vitseg_centerlines.h VITSEG_CENTERLINES_VERSION
 SIMPLIFY_VERSION = 100   # include/vitseg_simplify.h VITSEG_SIMPLIFY_VERSION
 OPTIM_VERSION = 100   # include/vitseg_optim.h VITSEG_OPTIM_VERSION
+CURVES_VERSION = 100   # include/vitseg_curves.h VITSEG_CURVES_VERSION
 
 EXT_SIGNATURES = {
     # region outlines: polygon rings with holes (polygons.py)
@@ -53,11 +54,18 @@ EXT_LATER = {
         ("vitseg_optim_prepare", i32, [vp, vp, i32, sz, i32, f32, f32, f32, f32, f32, vp, sz, vp]),
         ("vitseg_optim_step", i32, [vp, vp, vp, vp, vp, sz, vp, vp, f32, f32, f32, f32, f32, vp, sz, vp]),
     ]),
+    # precision-recall counts of a probability map over all thresholds, with a pixel tolerance (curves.py)
+    "curves": ("vitseg_curves.h", "the precision-recall curves", [
+        ("vitseg_curves_version", i32, []),
+        ("vitseg_pr_counts_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_pr_counts", i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    ]),
 }
 EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
                 "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION),
                 "simplify": ("vitseg_simplify_version", SIMPLIFY_VERSION),
-                "optim": ("vitseg_optim_version", OPTIM_VERSION)}
+                "optim": ("vitseg_optim_version", OPTIM_VERSION),
+                "curves": ("vitseg_curves_version", CURVES_VERSION)}
 
 
 def ext_symbol(family: str, name: str):

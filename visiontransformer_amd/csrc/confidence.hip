@@ -12,7 +12,7 @@
 //   STAGED   the few low-res rows the chunk's output rows interpolate between are copied to LDS for all classes first
 //            (upsample_kernel<STAGED>'s scheme); when C * rows * g floats do not fit (g == S at a large S, C near 255) the
 //            kernel reads them from global memory instead.
-//   sigmoid  one exact sigmoid per pixel for prob, two for margin: the best other class is found on the raw values.
+//   sigmoid  one exact sigmoid per pixel for prob, two for margin (conf_score.hpp, shared with curves.hip).
 //   rows     the pre-reduction of props.hip: a lane whose V pixels share a label joins the run of equal labels around it
 //            (run_reduce.hpp), the run's head adds once; the runs of up to NK regions per workgroup -- those found at NK
 //            pixels spread over the chunk -- add into LDS and reach their rows as one atomic per field, region and workgroup
@@ -21,9 +21,9 @@
 //   hist     the same runs keyed by bin add into a 32-bit LDS table (a chunk's sum_q stays below 2^32), flushed with one
 //            64-bit atomic per non-empty word.
 // All global accumulators are 64-bit integer atomicAdd / atomicMax: order-independent bits.
+#include "conf_score.hpp"
 #include "kernels.hpp"
 #include "run_reduce.hpp"
-#include "tail_math.hpp"
 
 namespace vitseg {
 namespace {
@@ -133,42 +133,8 @@ __global__ __launch_bounds__(256) void confidence_kernel(const ConfArgs a) {
                 cls[e] = mb[e];
                 taps(X + e, scale, g, x0[e], x1[e], wx0[e], wx1[e]);
             }
-            auto value = [&](int c, int e) {   // the decoder tail's fma placement
-                const float* z = zb + (size_t)c * plane;
-                const float top = __fmaf_rn(z[rt + x0[e]], wx0[e], __fmul_rn(z[rt + x1[e]], wx1[e]));
-                const float bot = __fmaf_rn(z[rb + x0[e]], wx0[e], __fmul_rn(z[rb + x1[e]], wx1[e]));
-                return __fmaf_rn(top, wy0, __fmul_rn(bot, wy1));
-            };
             float p[V];
-            if (a.kind == VITSEG_CONF_PROB) {
-#pragma unroll
-                for (int e = 0; e < V; ++e) {   // (the class is clamped before it indexes: a value >= C reads class C - 1, unused)
-                    const float sg = sigmoid_aten(value(min(cls[e], C - 1), e));
-                    p[e] = cls[e] < C ? sg : 0.f;
-                }
-            } else {
-                float vc[V], other[V];
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    vc[e] = 0.f;
-                    other[e] = -INFINITY;
-                }
-                for (int c = 0; c < C; ++c) {
-#pragma unroll
-                    for (int e = 0; e < V; ++e) {
-                        const float v = value(c, e);
-                        if (c == cls[e])
-                            vc[e] = v;
-                        else
-                            other[e] = fmaxf(other[e], v);
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < V; ++e)
-                    p[e] = cls[e] < C ? fminf(fmaxf(__fsub_rn(sigmoid_aten(vc[e]), sigmoid_aten(other[e])), 0.f), 1.f) : 0.f;
-            }
-#pragma unroll
-            for (int e = 0; e < V; ++e) q[e] = min(max((int)rintf(__fmul_rn(p[e], 65535.0f)), 0), 65535);
+            score_pixels<V>(zb, plane, C, a.kind, rt, rb, wy0, wy1, x0, x1, wx0, wx1, cls, p, q);
             if (a.conf) {
                 typename Vec<V>::f32 o;
                 float* ob = (float*)&o;

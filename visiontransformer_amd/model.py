@@ -521,6 +521,21 @@ class ViTSegmentationModel(nn.Module):
         return mask, _conf.confidence_map(lowres, mask, kind=kind, quantised=quantised)
 
     @torch.no_grad()
+    def pr_counts(self, x: torch.Tensor, gt, cls: int = 1, bins: int = 256, tolerance=0, ignore_label=None, kind: str = "prob",
+                  interpolate_pos_encoding: bool = False):
+        """The precision-recall counts of class `cls`' score map against the ground truth `gt` (uint8 [B, H, W]) over all
+        thresholds (curves.pr_counts: int64 numpy [B, bins, 3] of (pred, hit, found), `tolerance` in pixels): the forward that
+        stops at the head output (vitseg_forward_lowres) and one launch that re-generates the scores from it; neither the
+        full-size logits nor a mask are written.  `curves.summary` turns the counts into ODS, OIS and AP."""
+        from . import curves as _curves
+        _curves.check_options(cls, bins, tolerance, ignore_label)
+        interp = bool(interpolate_pos_encoding)
+        self._check_input(x, interp)
+        S, B = self._size_in(x, interp), int(x.shape[0])
+        lowres = self._window_lowres(x.to(torch.float32), False, S, S, "uniform", B)["lowres"]
+        return _curves.pr_counts(lowres, gt, cls=cls, bins=bins, tolerance=tolerance, ignore_label=ignore_label, kind=kind)
+
+    @torch.no_grad()
     def predict_regions(self, x: torch.Tensor, *, background: int = 0, connectivity: int = 4, return_mask: bool = False,
                         interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,
                         max_hole_area: int = 0, props: bool = False, skeleton_classes=None, scores: bool = False,

@@ -8,7 +8,9 @@ import json
 from collections import namedtuple
 from typing import Optional, Sequence
 
-from . import centerlines, confidence, polygons
+import numpy as np
+
+from . import centerlines, confidence, curves, polygons
 from .simplify import tol2_q8
 from ._common import write_csv
 from .metrics import (CRACK_CSV_COLUMNS, DISTANCE_CSV_COLUMNS, REGION_CSV_COLUMNS, crack_csv_row, distance_csv_row,
@@ -28,9 +30,10 @@ def every_class_but_0(classes, num_classes: int):
 
 
 def check_scoring(tta, score_kind, score_low) -> None:
-    """What the two confidence reports refuse: the scores are those of one forward, scoring merged views is not built."""
+    """What the confidence reports and the curve refuse: the scores are those of one forward, scoring merged views is not built."""
     if tta is not None:
-        raise ValueError("region_scores / calibration_bins with tta are not supported: the scores are those of one forward")
+        raise ValueError("region_scores / calibration_bins / pr_curve with tta are not supported: the scores are those of one "
+                         "forward")
     if score_kind not in confidence.KINDS:
         raise ValueError(f"score_kind must be one of {sorted(confidence.KINDS)}, got {score_kind!r}")
     confidence.low_to_q(score_low)
@@ -163,6 +166,28 @@ class Calibration(Report):
 
     def write(self, stem: str) -> None:
         self.rows = confidence.calibration_csv_rows(self.model_info, self.hist, self.bins)
+        super().write(stem)
+
+
+class PRCurve(Report):
+    """pr_curve: the precision-recall curve of one class' score map over all thresholds (curves.pr_counts of the low-res head
+    output against the resized ground truth, at `bins` thresholds and a tolerance in pixels), the integers of all images added
+    before any ratio: one row per threshold, then the rows ODS, OIS and AP.  It scores the probability map, not the mask."""
+    needs_lowres = True
+    suffix, columns = "_pr_curve.csv", curves.CSV_COLUMNS
+
+    def __init__(self, model_info: Sequence, cls: int = 1, bins: int = 256, tolerance=0, kind: str = "prob", path=None):
+        super().__init__(path)
+        curves.check_options(cls, bins, tolerance)
+        self.model_info, self.cls, self.bins, self.tolerance, self.kind, self.counts = model_info, cls, bins, tolerance, kind, []
+
+    def add(self, b: Batch) -> None:
+        self.counts.append(curves.pr_counts(b.lowres, b.ev.resized_gt(b.gt, b.mask), cls=self.cls, bins=self.bins,
+                                            tolerance=self.tolerance, kind=self.kind))
+
+    def write(self, stem: str) -> None:
+        counts = np.concatenate(self.counts) if self.counts else np.zeros((0, self.bins, 3), np.int64)
+        self.rows = curves.csv_rows(self.model_info, counts, self.cls, self.tolerance)
         super().write(stem)
 
 

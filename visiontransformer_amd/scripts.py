@@ -11,7 +11,7 @@ from typing import List, Optional
 
 import torch
 
-from . import clean, reports, synth
+from . import clean, curves, reports, synth
 from . import simplify as _simplify
 from .metrics import Evaluator, csv_row, write_metrics_csv
 from .tta import parse_sizes
@@ -316,6 +316,30 @@ def crack_graph_options(a, metrics_csv_path: str) -> dict:
                 crack_branches_csv_path=stem + "_crack_branches.csv")
 
 
+def add_curve_arguments(ap) -> None:
+    """--pr-curve / --pr-bins / --pr-tolerance of the evaluation scripts (--score-kind is the confidence flags')."""
+    ap.add_argument("--pr-curve", nargs="?", const=1, type=int, metavar="CLASS",
+                    help="also write <model>_pr_curve.csv: the precision-recall curve of CLASS' score map (default 1) over all "
+                         "thresholds, pooled over all images, then the rows ODS, OIS and AP; the score is --score-kind's")
+    ap.add_argument("--pr-bins", type=int, default=256, help="thresholds of the curve (1..1024)")
+    ap.add_argument("--pr-tolerance", type=float, default=0.0,
+                    help="a predicted pixel within this many pixels of a true one is no error, and a true pixel is found by a "
+                         "prediction as near (0..16; the crack benchmarks use 2 to 5; 0: the plain pixel curve)")
+
+
+def curve_options(ap, a) -> dict:
+    """The keywords of `evaluate_to_csv` from the parsed flags: none without --pr-curve; refused when arguments are parsed
+    (ap.error): the flag with --tta, a class, bin count or tolerance `curves.check_options` refuses."""
+    if a.pr_curve is None:
+        return {}
+    try:
+        reports.check_scoring(getattr(a, "tta", None), a.score_kind, a.score_low)
+        curves.check_options(a.pr_curve, a.pr_bins, a.pr_tolerance)
+    except ValueError as e:
+        ap.error(f"--pr-curve: {e}")
+    return dict(pr_curve=a.pr_curve, pr_bins=a.pr_bins, pr_tolerance=a.pr_tolerance)
+
+
 def add_evaluation_arguments(ap) -> None:
     """Every flag the two evaluation scripts (model/CE/datasetTestViTmodel.py, model/PAED/ViTscriptTest.py) share."""
     ap.add_argument("--distance-metrics", nargs="?", const="sets", choices=["sets", "borders"],
@@ -345,6 +369,7 @@ def add_evaluation_arguments(ap) -> None:
     add_confidence_arguments(ap)
     add_polygon_arguments(ap)
     add_crack_graph_arguments(ap)
+    add_curve_arguments(ap)
     ap.add_argument("--simplify", type=float, metavar="TOL",
                     help="thin the rings of --region-polygons and the polylines of --crack-graph on the device before they are "
                          "written (Douglas-Peucker, tolerance TOL in pixels; ends, ring starts and areas are kept); the features "
@@ -369,7 +394,7 @@ def evaluation_options(ap, a, csv_path: str) -> dict:
                 region_classes=True if a.region_metrics else None, region_iou=a.region_iou, region_coverage=a.region_coverage,
                 region_connectivity=a.region_connectivity, props_classes=parse_props_classes(a.region_props),
                 props_pixel_size=a.pixel_size, **clean.arguments(a), **confidence_options(ap, a),
-                **polygon_options(a, csv_path), **crack_graph_options(a, csv_path))
+                **polygon_options(a, csv_path), **crack_graph_options(a, csv_path), **curve_options(ap, a))
 
 
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
@@ -382,7 +407,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                     calibration_bins: Optional[int] = None, scores_csv_path: Optional[str] = None,
                     calibration_csv_path: Optional[str] = None, polygons_path: Optional[str] = None, crack_graph_classes=None,
                     crack_graph_path: Optional[str] = None, crack_branches_csv_path: Optional[str] = None,
-                    simplify_tolerance=None) -> List[list]:
+                    simplify_tolerance=None, pr_curve: Optional[int] = None, pr_bins: int = 256, pr_tolerance=0,
+                    pr_curve_csv_path: Optional[str] = None) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image; returns those rows.  Predictions and class
@@ -401,11 +427,12 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
       polygons_path                           reports.Outlines
       crack_graph_classes                     reports.CrackGraph
       simplify_tolerance                      the rings / polylines of the two above thinned on the device (pixels; ValueError
-                                              without either)"""
+                                              without either)
+      pr_curve, pr_bins, pr_tolerance, score_kind   reports.PRCurve of class pr_curve (ValueError with tta)"""
     if simplify_tolerance is not None and polygons_path is None and crack_graph_classes is None:
         raise ValueError("simplify_tolerance needs polygons_path or crack_graph_classes: it thins their geometry")
     min_area, fill_holes, max_hole_area = clean.check_options(min_area, fill_holes, max_hole_area)
-    if region_scores or calibration_bins is not None:
+    if region_scores or calibration_bins is not None or pr_curve is not None:
         reports.check_scoring(tta, score_kind, score_low)
     crack_classes, region_classes, props_classes, crack_graph_classes = (
         reports.every_class_but_0(c, num_classes) for c in (crack_classes, region_classes, props_classes, crack_graph_classes))
@@ -421,9 +448,12 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         reports.Outlines(polygons_path, simplify_tolerance) if polygons_path is not None else None,
         reports.CrackGraph(crack_graph_classes, crack_graph_path, crack_branches_csv_path,
                            simplify_tolerance) if crack_graph_classes is not None else None,
+        reports.PRCurve(model_info, pr_curve, pr_bins, pr_tolerance, score_kind, pr_curve_csv_path) if pr_curve is not None else None,
     ]
     active = [r for r in active if r is not None]
     seg = getattr(model, "model", model)
+    if pr_curve is not None and pr_curve >= seg.cfg.num_classes:
+        raise ValueError(f"pr_curve must be one of the model's {seg.cfg.num_classes} classes, got {pr_curve}")
     ev = Evaluator(num_classes, device)
     rows = []
     model.eval()
