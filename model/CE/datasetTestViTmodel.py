@@ -7,6 +7,7 @@ the schema model/CE/compareModels.py:27-47 reads.  Plots are host-side reporting
 
     python model/CE/datasetTestViTmodel.py --ids 1 --num-classes 17 --num-batches 3 [--data eval.pt]
     ... --pr-curve 1 --pr-tolerance 2       # also <model>_pr_curve.csv: class 1's precision-recall curve, ODS, OIS, AP
+    ... --threshold 0.31 --threshold-low 0.2   # every file scores the mask decided by threshold (hysteresis) instead of the argmax
 """
 import argparse
 import os

@@ -6,6 +6,7 @@ the time per image into test/<model>/<model>_metrics.csv.
 
     python model/PAED/ViTscriptTest.py --ids 0 --num-batches 3
     ... --pr-curve 0 --pr-tolerance 2       # also <model>_pr_curve.csv: the crack class' precision-recall curve, ODS, OIS, AP
+    ... --threshold 0.31 --threshold-low 0.2 --threshold-class 0   # every file scores the mask decided by threshold (hysteresis) instead of the argmax
 """
 import argparse
 import os

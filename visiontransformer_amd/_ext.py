@@ -21,6 +21,7 @@ CENTERLINES_VERSION = 100   # include/vitseg_centerlines.h VITSEG_CENTERLINES_VE
 SIMPLIFY_VERSION = 100   # include/vitseg_simplify.h VITSEG_SIMPLIFY_VERSION
 OPTIM_VERSION = 100   # include/vitseg_optim.h VITSEG_OPTIM_VERSION
 CURVES_VERSION = 100   # include/vitseg_curves.h VITSEG_CURVES_VERSION
+DECIDE_VERSION = 100   # include/vitseg_decide.h VITSEG_DECIDE_VERSION
 
 EXT_SIGNATURES = {
     # region outlines: polygon rings with holes (polygons.py)
@@ -60,12 +61,19 @@ EXT_LATER = {
         ("vitseg_pr_counts_scratch_bytes", sz, [i32, i32, i32]),
         ("vitseg_pr_counts", i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     ]),
+    # a class decided by threshold, with hysteresis (decide.py)
+    "decide": ("vitseg_decide.h", "the threshold decision", [
+        ("vitseg_decide_version", i32, []),
+        ("vitseg_decide_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_decide", i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    ]),
 }
 EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
                 "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION),
                 "simplify": ("vitseg_simplify_version", SIMPLIFY_VERSION),
                 "optim": ("vitseg_optim_version", OPTIM_VERSION),
-                "curves": ("vitseg_curves_version", CURVES_VERSION)}
+                "curves": ("vitseg_curves_version", CURVES_VERSION),
+                "decide": ("vitseg_decide_version", DECIDE_VERSION)}
 
 
 def ext_symbol(family: str, name: str):

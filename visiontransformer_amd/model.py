@@ -535,6 +535,43 @@ class ViTSegmentationModel(nn.Module):
         lowres = self._window_lowres(x.to(torch.float32), False, S, S, "uniform", B)["lowres"]
         return _curves.pr_counts(lowres, gt, cls=cls, bins=bins, tolerance=tolerance, ignore_label=ignore_label, kind=kind)
 
+    def _lowres_and_threshold(self, x: torch.Tensor, cls, threshold, low, connectivity, kind, over_argmax, interp: bool = False):
+        """(lowres fp32 [B, C, g, g], mask uint8 [B, S, S]) of one encoder pass: the forward that stops at the head output and
+        decide.threshold_mask on it -- over `_lowres_and_mask`'s argmax mask with `over_argmax`, else over nothing (no other
+        mask is written).  A kept pixel states decide.check_model_options' value."""
+        from . import decide as _decide
+        value = _decide.check_model_options(self.cfg.num_classes, cls, threshold, low, connectivity, kind)
+        if over_argmax:
+            lowres, base = self._lowres_and_mask(x, interp)
+        else:
+            self._check_input(x, interp)
+            S, B = self._size_in(x, interp), int(x.shape[0])
+            lowres, base = self._window_lowres(x.to(torch.float32), False, S, S, "uniform", B)["lowres"], None
+        mask = _decide.threshold_mask(lowres, cls=cls, threshold=threshold, low=low, connectivity=connectivity, kind=kind,
+                                      base=base, value=value, size=self._size_in(x, interp))
+        return lowres, mask
+
+    @torch.no_grad()
+    def predict_threshold(self, x: torch.Tensor, cls: int = 1, threshold=0.5, low=None, connectivity: int = 4,
+                          kind: str = "prob", over_argmax: bool = False, interpolate_pos_encoding: bool = False,
+                          min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0):
+        """uint8 [B, H, W]: class `cls` decided by threshold instead of by the argmax (decide.threshold_mask).  A pixel is kept
+        when its score (`kind`, as in `predict_confidence`) reaches `threshold` -- e.g. `curves.ods(...)["threshold"]` --, or,
+        with `low`, when it reaches `low` and is `connectivity`-connected through such pixels to one that reaches `threshold`
+        (hysteresis).  Kept pixels state `cls` (1 for a one-class model), the others 0; with `over_argmax` the others keep
+        what `predict_mask` states, except that a pixel it gave to `cls` becomes 0.  The encoder runs once and the scores are
+        re-generated from the low-res head output: the full-size logits are never written.  `min_area` / `fill_holes` /
+        `max_hole_area` (defaults: off): the mask is then cleaned by clean.clean_mask with this call's `connectivity`, on the
+        same stream."""
+        from . import clean as _clean
+        min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
+        _, mask = self._lowres_and_threshold(x, cls, threshold, low, connectivity, kind, bool(over_argmax),
+                                             bool(interpolate_pos_encoding))
+        if _clean.active(min_area, fill_holes):
+            mask = _clean.clean_mask(mask, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area,
+                                     connectivity=connectivity)
+        return mask
+
     @torch.no_grad()
     def predict_regions(self, x: torch.Tensor, *, background: int = 0, connectivity: int = 4, return_mask: bool = False,
                         interpolate_pos_encoding: bool = False, min_area: int = 0, fill_holes: bool = False,

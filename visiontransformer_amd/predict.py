@@ -73,7 +73,9 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
             tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0,
             return_props: bool = False, props_classes=None, pixel_size: float = 1.0, return_scores: bool = False,
             return_confidence: bool = False, score_kind: str = "prob", low: float = 0.5, return_polygons: bool = False,
-            return_centerlines: bool = False, centerline_classes=None, simplify=None):
+            return_centerlines: bool = False, centerline_classes=None, simplify=None, threshold=None, threshold_low=None,
+            threshold_class: int = 1, threshold_connectivity: int = 4, threshold_kind: str = "prob",
+            threshold_over_argmax: bool = False):
     """uint8 class-index mask [S, S] (numpy) for one image; optionally also an RGB rendering
     `index_to_color[mask]` (testViTModel.py:139-143) and/or the fp32 logits [C, S, S].  S = `serve_size`, else the
     one `load_model` was given, else the model's image size; another size than the model's runs with the position table
@@ -108,7 +110,13 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     mask alone as well.
     `simplify`: a tolerance in pixels for the outlines and the centre-lines (None: as they are traced): both are thinned on
     the device before they are copied back (simplify.simplify_device).  ValueError without `return_polygons` or
-    `return_centerlines`."""
+    `return_centerlines`.
+    `threshold` (default None: the argmax, as before): class `threshold_class` is decided by its score instead
+    (ViTSegmentationModel.predict_threshold): a pixel is kept when its score (`threshold_kind`) reaches `threshold`, with
+    `threshold_low` also when it reaches that and is `threshold_connectivity`-connected through such pixels to one that reaches
+    `threshold`; the others become 0 or, with `threshold_over_argmax`, keep the argmax mask's class.  The mask, its colour
+    rendering, boxes, props, scores, polygons and centre-lines are those of the decided mask; the clean-up runs after it.  With
+    `sliding` or `tta` it raises ValueError before anything runs: those paths keep no single low-res map."""
     from . import clean as _clean
     _clean.check_options(min_area, fill_holes, max_hole_area)
     if simplify is not None:
@@ -130,7 +138,18 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
         if score_kind not in _conf.KINDS:
             raise ValueError(f"score_kind must be one of {sorted(_conf.KINDS)}, got {score_kind!r}")
         _conf.low_to_q(low)
+    deciding = threshold is not None
+    if deciding or threshold_low is not None:
+        from . import decide as _decide
+        if sliding or tta is not None:
+            raise ValueError("threshold with sliding=True or tta= is not supported: the scores are those of one forward of the "
+                             "resized image")
+        if not deciding:
+            raise ValueError("threshold_low needs threshold")
     seg = model.model if isinstance(model, LightningViTModel) else model
+    if deciding:
+        decide_args = (threshold_class, threshold, threshold_low, threshold_connectivity, threshold_kind)
+        value = _decide.check_model_options(seg.cfg.num_classes, *decide_args)
     S = serve_size if serve_size is not None else getattr(model, "serve_size", None)
     S = seg.cfg.image_size if S is None else int(S)
     if tta is not None and sliding:
@@ -145,6 +164,10 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
                              f"{tuple(img.shape[:2])[0]}x{tuple(img.shape[:2])[1]}")
         out = seg.predict_mask_windowed(img[None].to(seg.arena.device), stride=stride, weights=weights, window_size=S,
                                         return_logits=return_logits)
+    elif deciding and not return_logits:   # one encoder pass that keeps the low-res head output
+        x = preprocess(image, S, seg.arena.device)
+        with torch.no_grad():
+            lowres, out = seg._lowres_and_threshold(x, *decide_args, bool(threshold_over_argmax), S != seg.cfg.image_size)
     elif scoring and not return_logits:   # one encoder pass that keeps the low-res head output; predict_mask's mask
         x = preprocess(image, S, seg.arena.device)
         with torch.no_grad():
@@ -152,8 +175,11 @@ def predict(image, model: Union[LightningViTModel, ViTSegmentationModel], *, ind
     else:
         x = preprocess(image, S, seg.arena.device)
         out = seg.predict_mask(x, return_logits=return_logits, interpolate_pos_encoding=S != seg.cfg.image_size)
-        if scoring:
+        if scoring or deciding:
             lowres = out[1]   # the full-size logits are there already: scored as they stand (g == S)
+        if deciding:
+            out = (_decide.threshold_mask(lowres, threshold_class, threshold, threshold_low, threshold_connectivity, threshold_kind,
+                                          base=out[0] if threshold_over_argmax else None, value=value, size=S), out[1])
     mask_dev = (out[0] if return_logits else out)[0]
     if _clean.active(min_area, fill_holes):
         mask_dev = _clean.clean_mask(mask_dev, min_area=min_area, fill_holes=fill_holes, max_hole_area=max_hole_area)

@@ -12,6 +12,7 @@ from typing import List, Optional
 import torch
 
 from . import clean, curves, reports, synth
+from . import decide as _decide
 from . import simplify as _simplify
 from .metrics import Evaluator, csv_row, write_metrics_csv
 from .tta import parse_sizes
@@ -340,6 +341,25 @@ def curve_options(ap, a) -> dict:
     return dict(pr_curve=a.pr_curve, pr_bins=a.pr_bins, pr_tolerance=a.pr_tolerance)
 
 
+def threshold_options(ap, a) -> dict:
+    """The keywords of `evaluate_to_csv` from the parsed flags: none without --threshold; refused when arguments are parsed
+    (ap.error): another threshold flag without --threshold, the flags with --tta, thresholds `decide.check_options` refuses (a
+    low one above the high one among them) and a class the model lacks."""
+    if a.threshold is None:
+        if a.threshold_low is not None or a.threshold_over_argmax:
+            ap.error("--threshold-low / --threshold-over-argmax need --threshold")
+        return {}
+    if getattr(a, "tta", None):
+        ap.error("--threshold cannot be combined with --tta: the scores are those of one forward")
+    try:   # (both scripts have --num-classes; a parser without it leaves the class to evaluate_to_csv)
+        _decide.check_model_options(getattr(a, "num_classes", 255), a.threshold_class, a.threshold, a.threshold_low,
+                                    a.threshold_connectivity, a.score_kind)
+    except ValueError as e:
+        ap.error(f"--threshold: {e}")
+    return dict(threshold=a.threshold, threshold_low=a.threshold_low, threshold_class=a.threshold_class,
+                threshold_connectivity=a.threshold_connectivity, threshold_over_argmax=a.threshold_over_argmax)
+
+
 def add_evaluation_arguments(ap) -> None:
     """Every flag the two evaluation scripts (model/CE/datasetTestViTmodel.py, model/PAED/ViTscriptTest.py) share."""
     ap.add_argument("--distance-metrics", nargs="?", const="sets", choices=["sets", "borders"],
@@ -370,6 +390,7 @@ def add_evaluation_arguments(ap) -> None:
     add_polygon_arguments(ap)
     add_crack_graph_arguments(ap)
     add_curve_arguments(ap)
+    _decide.add_arguments(ap)
     ap.add_argument("--simplify", type=float, metavar="TOL",
                     help="thin the rings of --region-polygons and the polylines of --crack-graph on the device before they are "
                          "written (Douglas-Peucker, tolerance TOL in pixels; ends, ring starts and areas are kept); the features "
@@ -394,7 +415,8 @@ def evaluation_options(ap, a, csv_path: str) -> dict:
                 region_classes=True if a.region_metrics else None, region_iou=a.region_iou, region_coverage=a.region_coverage,
                 region_connectivity=a.region_connectivity, props_classes=parse_props_classes(a.region_props),
                 props_pixel_size=a.pixel_size, **clean.arguments(a), **confidence_options(ap, a),
-                **polygon_options(a, csv_path), **crack_graph_options(a, csv_path), **curve_options(ap, a))
+                **polygon_options(a, csv_path), **crack_graph_options(a, csv_path), **curve_options(ap, a),
+                **threshold_options(ap, a))
 
 
 def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int, num_batches: int, device,
@@ -408,7 +430,8 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
                     calibration_csv_path: Optional[str] = None, polygons_path: Optional[str] = None, crack_graph_classes=None,
                     crack_graph_path: Optional[str] = None, crack_branches_csv_path: Optional[str] = None,
                     simplify_tolerance=None, pr_curve: Optional[int] = None, pr_bins: int = 256, pr_tolerance=0,
-                    pr_curve_csv_path: Optional[str] = None) -> List[list]:
+                    pr_curve_csv_path: Optional[str] = None, threshold=None, threshold_low=None, threshold_class: int = 1,
+                    threshold_connectivity: int = 4, threshold_over_argmax: bool = False) -> List[list]:
     """The per-image loop of datasetTestViTmodel.py:163-227 / ViTscriptTest.py:160-227: model.eval(), logits.sigmoid(),
     argmax over the class dim, ground truth NEAREST-resized to the prediction, accuracy / mean IoU / mean Dice / class
     sets per image, one CSV row each with the batch's average time per image; returns those rows.  Predictions and class
@@ -428,7 +451,12 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
       crack_graph_classes                     reports.CrackGraph
       simplify_tolerance                      the rings / polylines of the two above thinned on the device (pixels; ValueError
                                               without either)
-      pr_curve, pr_bins, pr_tolerance, score_kind   reports.PRCurve of class pr_curve (ValueError with tta)"""
+      pr_curve, pr_bins, pr_tolerance, score_kind   reports.PRCurve of class pr_curve (ValueError with tta)
+      threshold, threshold_low, threshold_class, threshold_connectivity, threshold_over_argmax, score_kind
+                                              every file scores the mask of `predict_threshold` (decide.threshold_mask: class
+                                              threshold_class kept where its score reaches `threshold`, with hysteresis down to
+                                              `threshold_low`), decided inside the time per image, before the clean-up
+                                              (ValueError with tta, or for a class the model lacks)"""
     if simplify_tolerance is not None and polygons_path is None and crack_graph_classes is None:
         raise ValueError("simplify_tolerance needs polygons_path or crack_graph_classes: it thins their geometry")
     min_area, fill_holes, max_hole_area = clean.check_options(min_area, fill_holes, max_hole_area)
@@ -454,6 +482,13 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
     seg = getattr(model, "model", model)
     if pr_curve is not None and pr_curve >= seg.cfg.num_classes:
         raise ValueError(f"pr_curve must be one of the model's {seg.cfg.num_classes} classes, got {pr_curve}")
+    if threshold is None and threshold_low is not None:
+        raise ValueError("threshold_low needs threshold")
+    if threshold is not None:
+        if tta is not None:
+            raise ValueError("threshold with tta is not supported: the scores are those of one forward")
+        _decide.check_model_options(seg.cfg.num_classes, threshold_class, threshold, threshold_low, threshold_connectivity,
+                                    score_kind)
     ev = Evaluator(num_classes, device)
     rows = []
     model.eval()
@@ -467,6 +502,9 @@ def evaluate_to_csv(model, batches, model_info, csv_path: str, num_classes: int,
         with torch.no_grad():
             if tta is not None:
                 mask = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge)
+            elif threshold is not None:
+                lowres, mask = seg._lowres_and_threshold(x, threshold_class, threshold, threshold_low, threshold_connectivity,
+                                                         score_kind, threshold_over_argmax)
             elif any(r.needs_lowres for r in active):
                 lowres, mask = seg._lowres_and_mask(x)
             else:

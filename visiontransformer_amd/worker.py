@@ -114,14 +114,19 @@ class ModelSlot:
 
 def gpu_slot(model_id_or_config, num_classes: int, checkpoint: Optional[str] = None, *, image_size: int = 224,
              precision: str = "fp32", device: str = "cuda:0", serve_size: Optional[int] = None, tta=None, tta_sizes=None,
-             tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0) -> ModelSlot:
+             tta_merge: str = "logits", min_area: int = 0, fill_holes: bool = False, max_hole_area: int = 0,
+             threshold=None, threshold_low=None, threshold_class: int = 1, threshold_connectivity: int = 4,
+             threshold_kind: str = "prob", threshold_over_argmax: bool = False) -> ModelSlot:
     """ModelSlot running on libvitseg: device pre-processing of every image (sizes may differ per job), one batched
     forward + fused sigmoid/argmax.  `image_size`: the checkpoint's; `serve_size` (default the same): the side images are
     resized to, with the position table resampled to its grid when the two differ.  `tta` (default None: one look):
     a test-time-augmentation preset or op sequence; every batch then goes through `predict_mask_tta` with the views at
     `tta_sizes` (default the served size) merged by `tta_merge`.  `min_area` / `fill_holes` / `max_hole_area` (defaults:
     off): every batch's masks are cleaned on the device (clean.clean_mask) before they leave it; a bad value is refused
-    here, not at the first job."""
+    here, not at the first job.  `threshold` (default None: the argmax): every batch's masks are
+    `predict_threshold`'s -- class `threshold_class` kept where its score (`threshold_kind`) reaches `threshold`, with
+    `threshold_low` by hysteresis over `threshold_connectivity`-connected pixels, over the argmax mask with
+    `threshold_over_argmax` --, decided before the clean-up; refused here with `tta`, or for a class the model lacks."""
     import torch
     from . import clean as _clean
     min_area, fill_holes, max_hole_area = _clean.check_options(min_area, fill_holes, max_hole_area)
@@ -135,6 +140,14 @@ def gpu_slot(model_id_or_config, num_classes: int, checkpoint: Optional[str] = N
         from . import tta as _tta
         _tta.view_list(tta, tta_sizes, None, S, seg.cfg.patch_size)
         _tta.merge_mode(tta_merge)
+    if threshold is not None or threshold_low is not None:
+        from . import decide as _decide
+        if threshold is None:
+            raise ValueError("threshold_low needs threshold")
+        if tta is not None:
+            raise ValueError("threshold with tta is not supported: the scores are those of one forward")
+        _decide.check_model_options(seg.cfg.num_classes, threshold_class, threshold, threshold_low, threshold_connectivity,
+                                    threshold_kind)
 
     def predict_batch(images):
         x = torch.empty((len(images), 3, S, S), dtype=torch.float32, device=device)
@@ -143,6 +156,9 @@ def gpu_slot(model_id_or_config, num_classes: int, checkpoint: Optional[str] = N
         with torch.no_grad():
             if tta is not None:
                 m = seg.predict_mask_tta(x, tta=tta, sizes=tta_sizes, merge=tta_merge)
+            elif threshold is not None:
+                m = seg.predict_threshold(x, threshold_class, threshold, threshold_low, threshold_connectivity, threshold_kind,
+                                          over_argmax=threshold_over_argmax, interpolate_pos_encoding=S != image_size)
             else:
                 m = seg.predict_mask(x, interpolate_pos_encoding=S != image_size)
             if _clean.active(min_area, fill_holes):
@@ -289,7 +305,7 @@ def parse_model_spec(spec: str) -> dict:
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from . import clean as _clean
+    from . import clean as _clean, decide as _decide
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8001)
@@ -303,6 +319,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tta-sizes", default=None, help="comma-separated view sizes, e.g. 160,224 (default: the served size)")
     ap.add_argument("--tta-merge", default="logits", choices=["logits", "probs"])
     _clean.add_arguments(ap)
+    _decide.add_arguments(ap)
+    ap.add_argument("--threshold-kind", default="prob", choices=["prob", "margin"],
+                    help="the score --threshold cuts: the sigmoid of the class, or its lead over the best other class")
     return ap
 
 
@@ -316,7 +335,10 @@ def main(argv=None):
         m = parse_model_spec(spec)
         slots[m["model_id"]] = gpu_slot(m["config_id"], m["num_classes"], m["checkpoint"], image_size=m["image_size"],
                                         serve_size=m["serve_size"], precision=a.precision, tta=a.tta,
-                                        tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge, **_clean.arguments(a))
+                                        tta_sizes=parse_sizes(a.tta_sizes), tta_merge=a.tta_merge, **_clean.arguments(a),
+                                        threshold=a.threshold, threshold_low=a.threshold_low, threshold_class=a.threshold_class,
+                                        threshold_connectivity=a.threshold_connectivity, threshold_kind=a.threshold_kind,
+                                        threshold_over_argmax=a.threshold_over_argmax)
     srv = Worker(slots, a.backend, a.token, max_batch=a.max_batch).serve(a.host, a.port)
     log.info("listening on %s:%d/enqueue/ -> %s", a.host, a.port, a.backend)
     srv.serve_forever()
