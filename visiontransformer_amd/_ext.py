@@ -22,6 +22,16 @@ SIMPLIFY_VERSION = 100   # include/vitseg_simplify.h VITSEG_SIMPLIFY_VERSION
 OPTIM_VERSION = 100   # include/vitseg_optim.h VITSEG_OPTIM_VERSION
 CURVES_VERSION = 100   # include/vitseg_curves.h VITSEG_CURVES_VERSION
 DECIDE_VERSION = 100   # include/vitseg_decide.h VITSEG_DECIDE_VERSION
+HARDLOSS_VERSION = 100   # include/vitseg_hardloss.h VITSEG_HARDLOSS_VERSION
+
+
+class CHardOptions(C.Structure):
+    """struct vitseg_hard_options (include/vitseg_hardloss.h)."""
+    _fields_ = [("gamma", C.c_float), ("loss_thresh", C.c_float), ("min_kept", C.c_int64), ("keep_q16", C.c_int32),
+                ("reserved", C.c_int32), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+phard = C.POINTER(CHardOptions)
 
 EXT_SIGNATURES = {
     # region outlines: polygon rings with holes (polygons.py)
@@ -67,13 +77,22 @@ EXT_LATER = {
         ("vitseg_decide_scratch_bytes", sz, [i32, i32, i32]),
         ("vitseg_decide", i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
     ]),
+    # focal cross-entropy and online hard example mining on the fused loss path (model.ce_loss)
+    "hardloss": ("vitseg_hardloss.h", "the hard-pixel losses", [
+        ("vitseg_hardloss_version", i32, []),
+        ("vitseg_hard_loss_scratch_bytes", sz, [i32, i32]),
+        ("vitseg_hard_ce_loss", i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, _lib.popt, phard, f32, vp, vp, vp]),
+        ("vitseg_backward_hard", i32, [_lib.pcfg, i32, vp, vp, vp, i32, i32, f32, _lib.u64, vp, i32, vp, vp, vp, f32, vp, vp, sz,
+                                       vp, _lib.popt, phard, vp]),
+    ]),
 }
 EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
                 "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION),
                 "simplify": ("vitseg_simplify_version", SIMPLIFY_VERSION),
                 "optim": ("vitseg_optim_version", OPTIM_VERSION),
                 "curves": ("vitseg_curves_version", CURVES_VERSION),
-                "decide": ("vitseg_decide_version", DECIDE_VERSION)}
+                "decide": ("vitseg_decide_version", DECIDE_VERSION),
+                "hardloss": ("vitseg_hardloss_version", HARDLOSS_VERSION)}
 
 
 def ext_symbol(family: str, name: str):

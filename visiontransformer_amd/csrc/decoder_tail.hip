@@ -408,37 +408,7 @@ __global__ __launch_bounds__(1024) void ce_finish_kernel(const double* __restric
 // With no label ignored, no weights and eps = 0 every product below is by 1 or adds +0: the bits of ce_loss_kernel.
 constexpr int CE_COUNT_PER_THREAD = 4;   // targets per thread of the count pass (block = 1024 consecutive targets)
 
-// the fixed-order sum of ce_finish_kernel: 4 independent strided chains per thread, then a tree; the result is in red[0]
-__device__ __forceinline__ void ce_fixed_order_sum(const double* __restrict__ partial, int n, double* red) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int i = threadIdx.x;
-    for (; i + 3 * 1024 < n; i += 4 * 1024) {
-        s0 += partial[i];
-        s1 += partial[i + 1024];
-        s2 += partial[i + 2 * 1024];
-        s3 += partial[i + 3 * 1024];
-    }
-    for (; i < n; i += 1024) s0 += partial[i];
-    red[threadIdx.x] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-}
-
-struct CeOpt {
-    const float* weight;   // [C] or null (all ones)
-    long long ignore;      // read only when has_ignore
-    int has_ignore;
-    float eps;
-};
-
-// class weights of the block in LDS (C <= 255); every thread of the block calls this
-__device__ __forceinline__ void ce_stage_weights(float* wsh, const float* __restrict__ weight, int C) {
-    if ((int)threadIdx.x < C) wsh[threadIdx.x] = weight ? weight[threadIdx.x] : 1.f;
-    __syncthreads();
-}
+// (ce_fixed_order_sum, CeOpt and ce_stage_weights: tail_math.hpp, shared with hardloss.hip)
 
 template <typename TargetT>
 __global__ __launch_bounds__(256) void ce_count_kernel(const TargetT* __restrict__ target, CeOpt o, double* __restrict__ partial,

@@ -14,14 +14,15 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .model import ViTSegmentationModel, check_ce_options, check_dice_options
+from .model import ViTSegmentationModel, check_ce_options, check_dice_options, check_hard_options
 
 
 class LightningViTModel(nn.Module):
     def __init__(self, num_classes, patch_size, hidden_size, num_hidden_layers, num_attention_heads, *,
                  interpolate_pos_encoding: bool = False, ignore_index=None, class_weight=None,
                  label_smoothing: float = 0.0, dice_weight: float = 0.0, dice_smooth: float = 1e-6,
-                 dice_include_background: bool = True, augment=None, **kw):
+                 dice_include_background: bool = True, augment=None, focal_gamma: float = 0.0, ohem_thresh=None,
+                 ohem_min_kept: int = 0, ohem_keep_fraction: float = 0.0, **kw):
         """`interpolate_pos_encoding`: inputs of other (square, multiple-of-P) sizes than `image_size` run with the
         position table resampled to their grid (ViTSegmentationModel.forward); targets are resized to the input's size.
         `ignore_index`, `class_weight`, `label_smoothing`: the arguments of the reference's `nn.CrossEntropyLoss()`
@@ -30,6 +31,11 @@ class LightningViTModel(nn.Module):
         `dice_weight` > 0 adds that many times the soft Dice loss of the softmax probabilities to the CE
         (ViTSegmentationModel.ce_dice_loss with `dice_smooth`, `dice_include_background`); both steps then log `*_ce` and
         `*_dice` beside `*_loss`.  With 0 the steps call exactly what they call without the argument.
+        `focal_gamma`, `ohem_thresh`, `ohem_min_kept`, `ohem_keep_fraction`: the focal factor and the online hard example
+        mining of ViTSegmentationModel.ce_loss.  The training step then logs `train_kept`, the device scalar hard pixels /
+        valid pixels; the validation step forms the same loss with OHEM off (the focal factor stays), so that `valid_loss` and
+        early stopping do not follow the hardest pixels alone.  Not with `dice_weight` or `label_smoothing` (ValueError).  With
+        all four at their defaults the steps call exactly what they call without the arguments.
         `augment`: an `augment.Augmenter`; the training step (alone) warps and colour-jitters the batch with it, the mask
         going straight to the input's size as the class bytes the fused loss reads (one launch, in place of `_resize_target`).
         With None the steps launch exactly what they launch without the argument.
@@ -51,6 +57,14 @@ class LightningViTModel(nn.Module):
         if self.dice_weight != 0.0:
             check_dice_options(num_classes, dice_weight, 1.0, dice_smooth, dice_include_background)
         self.dice_smooth, self.dice_include_background = dice_smooth, bool(dice_include_background)
+        self.hard = check_hard_options(focal_gamma, ohem_thresh, ohem_min_kept, ohem_keep_fraction) is not None
+        self.focal_gamma, self.ohem_thresh = focal_gamma, ohem_thresh
+        self.ohem_min_kept, self.ohem_keep_fraction = ohem_min_kept, ohem_keep_fraction
+        if self.hard and self.dice_weight != 0.0:
+            raise ValueError("focal_gamma / ohem_* cannot be combined with dice_weight: composing them with the Dice term needs "
+                             "a variant of the fused CE + Dice kernel and is out of scope")
+        if self.hard and label_smoothing != 0:
+            raise ValueError("focal_gamma / ohem_* cannot be combined with label_smoothing")
         self.augment = augment
         self.logged = {}
 
@@ -94,6 +108,16 @@ class LightningViTModel(nn.Module):
             if stage is not None:
                 self.logged[f"{stage}_ce"], self.logged[f"{stage}_dice"] = ce, dice
             return loss
+        if self.hard:
+            if stage == "train":
+                loss, stats = self.model.ce_loss(
+                    x, y, grad_scale=grad_scale, interpolate_pos_encoding=self.interpolate_pos_encoding,
+                    focal_gamma=self.focal_gamma, ohem_thresh=self.ohem_thresh, ohem_min_kept=self.ohem_min_kept,
+                    ohem_keep_fraction=self.ohem_keep_fraction, return_stats=True, **opts)
+                self.logged["train_kept"] = stats[2].double() / stats[0].double()
+                return loss
+            return self.model.ce_loss(x, y, grad_scale=grad_scale, interpolate_pos_encoding=self.interpolate_pos_encoding,
+                                      focal_gamma=self.focal_gamma, **opts)   # OHEM off
         if self.interpolate_pos_encoding:
             return self.model.ce_loss(x, y, grad_scale=grad_scale, interpolate_pos_encoding=True, **opts)
         return self.model.ce_loss(x, y, grad_scale=grad_scale, **opts)

@@ -9,6 +9,7 @@ nn.Parameter), a cached workspace tensor and the output tensor.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import numbers
 from collections import OrderedDict
 from typing import Dict, Optional
@@ -16,7 +17,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
-from . import _lib, params as _params
+from . import _ext, _lib, params as _params
 from .config import ViTSegConfig
 
 _PRECISION = {"fp32": _lib.F32, "f32": _lib.F32, "float32": _lib.F32, "bf16": _lib.BF16, "bfloat16": _lib.BF16,
@@ -81,6 +82,45 @@ def check_dice_options(num_classes: int, dice_weight=1.0, ce_weight=1.0, smooth=
     return out[0], out[1], out[2], bool(include_background)
 
 
+def check_hard_options(focal_gamma=0.0, ohem_thresh=None, ohem_min_kept=0, ohem_keep_fraction=0.0):
+    """Host-side validation of `ce_loss`'s focal / OHEM options (the kernels cannot raise).  Returns None when all four are
+    at their defaults -- the caller then takes the calls it took before -- else (gamma, loss_thresh, min_kept, keep_q16) as
+    vitseg_hard_options reads them: the fp32 exponent, the threshold as the fp32 CE value float32(-log(ohem_thresh)) (+inf
+    for None), the floor as a count and as rint(ohem_keep_fraction * 65536).
+    ValueError: a `focal_gamma` that is not a finite number >= 0 (in fp32), an `ohem_thresh` that is not None or a
+    probability in (0, 1], an `ohem_min_kept` that is not an integer in [0, 2^63), an `ohem_keep_fraction` outside [0, 1]."""
+    for name, v in (("focal_gamma", focal_gamma), ("ohem_thresh", ohem_thresh), ("ohem_keep_fraction", ohem_keep_fraction)):
+        if isinstance(v, (str, bytes, bool)):
+            raise ValueError(f"{name} must be a number, got {v!r}")
+    try:
+        gamma = float(torch.tensor(float(focal_gamma), dtype=torch.float32))   # what the kernels read
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"focal_gamma must be a finite number >= 0, got {focal_gamma!r}") from None
+    if not (0.0 <= gamma < float("inf")):   # (a NaN fails both comparisons)
+        raise ValueError(f"focal_gamma must be a finite number >= 0, got {focal_gamma!r}")
+    loss_thresh = float("inf")
+    if ohem_thresh is not None:
+        try:
+            t = float(ohem_thresh)
+        except (TypeError, ValueError):
+            raise ValueError(f"ohem_thresh must be None or a probability in (0, 1], got {ohem_thresh!r}") from None
+        if not (0.0 < t <= 1.0):
+            raise ValueError(f"ohem_thresh must be None or a probability in (0, 1], got {ohem_thresh!r}")
+        loss_thresh = float(torch.tensor(-math.log(t) + 0.0, dtype=torch.float32))   # (+ 0.0: -log(1) is -0.0)
+    if isinstance(ohem_min_kept, bool) or not isinstance(ohem_min_kept, numbers.Integral) or not 0 <= int(ohem_min_kept) < 2 ** 63:
+        raise ValueError(f"ohem_min_kept must be an integer in [0, 2^63), got {ohem_min_kept!r}")
+    try:
+        frac = float(ohem_keep_fraction)
+    except (TypeError, ValueError):
+        raise ValueError(f"ohem_keep_fraction must be a number in [0, 1], got {ohem_keep_fraction!r}") from None
+    if not (0.0 <= frac <= 1.0):
+        raise ValueError(f"ohem_keep_fraction must be a number in [0, 1], got {ohem_keep_fraction!r}")
+    keep_q16 = int(round(frac * 65536.0))   # round half to even: rint
+    if gamma == 0.0 and ohem_thresh is None and int(ohem_min_kept) == 0 and frac == 0.0:
+        return None
+    return gamma, loss_thresh, int(ohem_min_kept), keep_q16
+
+
 class _LogitsFn(torch.autograd.Function):
     """logits = forward(x) with libvitseg's backward: d loss / d logits -> d loss / d arena."""
 
@@ -120,6 +160,29 @@ class _CELossFn(torch.autograd.Function):
         if not ctx.prescaled:
             grads.mul_(dloss)   # in place: the buffer is ours until it is delivered
         return ctx.model._deliver_grad(grads), None, None, None, None, None, None
+
+
+class _HardCELossFn(torch.autograd.Function):
+    """`_CELossFn` for the focal / OHEM loss (vitseg_backward_hard): returns (loss, stats), stats the device int64[4]
+    {n_valid, k, |H|, bits of tau} (no gradient); the arena gradient is delivered the same way."""
+
+    @staticmethod
+    def forward(ctx, arena, model, x, target, grad_scale, interp, ce_opts, hard_opts):
+        drop = model._next_dropout()
+        model._forward_train(x, want_logits=False, drop=drop, interp=interp)
+        grads, (loss, stats) = model._backward(x, target=target, drop=drop, loss_scale=1.0 if grad_scale is None else grad_scale,
+                                               interp=interp, ce_opts=ce_opts, hard_opts=hard_opts)
+        ctx.grads, ctx.model = grads, model
+        ctx.prescaled = grad_scale is not None
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        grads, ctx.grads = ctx.grads, None
+        if not ctx.prescaled:
+            grads.mul_(dloss)   # in place: the buffer is ours until it is delivered
+        return ctx.model._deliver_grad(grads), None, None, None, None, None, None, None
 
 
 class _CEDiceLossFn(torch.autograd.Function):
@@ -436,10 +499,12 @@ class ViTSegmentationModel(nn.Module):
 
     def _backward(self, x: torch.Tensor, target: Optional[torch.Tensor] = None,
                   grad_logits: Optional[torch.Tensor] = None, drop=(0.0, 0), loss_scale: float = 1.0,
-                  interp: bool = False, ce_opts=None, dice_opts=None):
+                  interp: bool = False, ce_opts=None, dice_opts=None, hard_opts=None):
         """`ce_opts`: a `_lib.CCEOptions` from `_ce_options` (fused CE only), or None for the plain calls.  `dice_opts`: a
         `_lib.CDiceOptions` from `_dice_options` (fused loss only): the second value returned is then the device float[3]
-        {loss, CE, dice} of vitseg_backward_dice instead of the scalar loss."""
+        {loss, CE, dice} of vitseg_backward_dice instead of the scalar loss.  `hard_opts`: an `_ext.CHardOptions` from
+        `_hard_options` (fused loss only, not with `dice_opts`): the second value is then (loss, the device int64[4] stats
+        of vitseg_backward_hard)."""
         x = x.to(torch.float32).contiguous()
         B, S = x.shape[0], self._size_in(x, interp)
         ws = self._train_workspace(B, S)
@@ -458,6 +523,11 @@ class ViTSegmentationModel(nn.Module):
                 _lib.check(_lib.symbol("vitseg_backward_dice")(
                     cfg, S, *args, C.byref(ce_opts) if ce_opts is not None else None, C.byref(dice_opts), terms.data_ptr()))
                 loss = terms
+            elif hard_opts is not None:
+                stats = torch.zeros(4, dtype=torch.int64, device=x.device)
+                _lib.check(_ext.ext_symbol("hardloss", "vitseg_backward_hard")(
+                    cfg, S, *args, C.byref(ce_opts) if ce_opts is not None else None, C.byref(hard_opts), stats.data_ptr()))
+                loss = (loss, stats)
             elif ce_opts is not None:
                 _lib.check(_lib.symbol("vitseg_backward_opts")(cfg, S, *args, C.byref(ce_opts)))
             elif S == self.cfg.image_size:
@@ -960,9 +1030,27 @@ class ViTSegmentationModel(nn.Module):
         opts._tensors = (wdev, scratch)   # the struct holds raw addresses: an eviction must not free them under it
         return opts
 
+    def _hard_options(self, B: int, S: int, focal_gamma, ohem_thresh, ohem_min_kept, ohem_keep_fraction, force: bool = False):
+        """The `_ext.CHardOptions` of a `ce_loss` call (validated on the host), or None when the four options are at their
+        defaults and `force` is off (the calls without them).  Its scratch is cached per (batch, size)."""
+        checked = check_hard_options(focal_gamma, ohem_thresh, ohem_min_kept, ohem_keep_fraction)
+        if checked is None:
+            if not force:
+                return None
+            checked = (0.0, float("inf"), 0, 0)
+        dev = self.arena.device
+        nbytes = int(_ext.ext_symbol("hardloss", "vitseg_hard_loss_scratch_bytes")(B, S))
+        if nbytes == 0:
+            raise ValueError(f"the focal / OHEM loss takes fewer than 2^31 pixels a call, got {B} x {S} x {S}")
+        scratch = self._ce_cached("hard scratch", (B, S, dev), lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+        opts = _ext.CHardOptions(checked[0], checked[1], checked[2], checked[3], 0, scratch.data_ptr(), scratch.numel())
+        opts._tensors = (scratch,)   # the struct holds a raw address: an eviction must not free it under the struct
+        return opts
+
     def ce_loss(self, x: torch.Tensor, target: torch.Tensor, grad_scale: Optional[float] = None,
                 interpolate_pos_encoding: bool = False, ignore_index: Optional[int] = None, class_weight=None,
-                label_smoothing: float = 0.0) -> torch.Tensor:
+                label_smoothing: float = 0.0, focal_gamma: float = 0.0, ohem_thresh: Optional[float] = None,
+                ohem_min_kept: int = 0, ohem_keep_fraction: float = 0.0, return_stats: bool = False):
         """`nn.CrossEntropyLoss(weight=class_weight, ignore_index=ignore_index, label_smoothing=label_smoothing)(self(x),
         target)` (model/CE/classes.py:268,280 with the defaults) as a device scalar, without materialising the
         [B, C, S, S] logits: forward to the low-res map, then the fused upsample+CE kernel.
@@ -977,6 +1065,15 @@ class ViTSegmentationModel(nn.Module):
         synchronising copy per call): in a training loop pass a sequence or a CPU tensor.  `label_smoothing` in [0, 1].  When every pixel is ignored (or every kept pixel has weight 0) the loss is
         NaN, torch's 0 / 0.  Invalid options raise ValueError on the host.  With all three at their defaults the call is
         the plain one (the same kernels, the same bits).
+        `focal_gamma` > 0: the focal loss (Lin et al. 2017), each pixel's term times (1 - p_y)^gamma.  `ohem_thresh`,
+        `ohem_min_kept`, `ohem_keep_fraction`: online hard example mining as in HRNet's / mmsegmentation's OhemCrossEntropy --
+        the mean runs over the hard pixels alone, those whose true-class probability lies under `ohem_thresh` (a probability
+        in (0, 1], None = no threshold) and never fewer than max(ohem_min_kept, ceil(ohem_keep_fraction * valid pixels)), the
+        hardest of the call's batch (per rank under data parallelism); pixels tied with the last one kept are kept too.
+        Ranking is by the plain per-pixel CE; the denominator is the summed class weights of the hard pixels.  The selection
+        runs on the device (include/vitseg_hardloss.h).  These four cannot be combined with `label_smoothing`.  With them at
+        their defaults the call launches what it launched before.  `return_stats=True` returns (loss, stats), stats a device
+        int64[4] {valid pixels, k, hard pixels, the fp32 bits of the CE threshold tau}.
         `grad_scale` (optional): the gradient `loss.backward()` deposits is grad_scale * d loss / d params, folded into
         the CE gradient inside the kernel (e.g. 1 / accumulate_grad_batches); call `.backward()` on the returned loss
         itself then -- an upstream factor is ignored in this mode.  `interpolate_pos_encoding`: as in `forward`; the
@@ -988,6 +1085,12 @@ class ViTSegmentationModel(nn.Module):
         if tuple(target.shape) != (B, S, S) or target.dtype not in (torch.int64, torch.uint8):
             raise ValueError(f"target must be int64/uint8 [B, {S}, {S}], got {target.dtype} {tuple(target.shape)}")
         opts = self._ce_options(B, S, ignore_index, class_weight, label_smoothing)
+        hard = self._hard_options(B, S, focal_gamma, ohem_thresh, ohem_min_kept, ohem_keep_fraction, force=bool(return_stats))
+        if hard is not None:
+            if label_smoothing != 0:
+                raise ValueError("label_smoothing cannot be combined with focal_gamma / ohem_* / return_stats")
+            return self._hard_ce_loss(x, target.to(self.arena.device).contiguous(), grad_scale, interp, opts, hard,
+                                      bool(return_stats))
         if self._needs_grad():
             return _CELossFn.apply(self.arena, self, x, target.to(self.arena.device).contiguous(), grad_scale, interp, opts)
         with torch.no_grad():
@@ -1004,6 +1107,25 @@ class ViTSegmentationModel(nn.Module):
             else:
                 _lib.check(_lib.symbol("vitseg_ce_loss_opts")(*args, C.byref(opts), 1.0, stream))
         return loss
+
+    def _hard_ce_loss(self, x, target, grad_scale, interp, opts, hard, return_stats):
+        """`ce_loss` with the focal / OHEM options: vitseg_backward_hard under autograd, else vitseg_hard_ce_loss on the
+        inference forward's low-res logits."""
+        B, S = x.shape[0], self._size_in(x, interp)
+        if self._needs_grad():
+            loss, stats = _HardCELossFn.apply(self.arena, self, x, target, grad_scale, interp, opts, hard)
+        else:
+            with torch.no_grad():
+                _, _ = self._run(x, False, True, interp=interp)  # fills the low-res logits (mask output is a by-product)
+                low = self.debug_buffer(B, _lib.BUF_LOWRES, S)
+                scratch = torch.empty(_lib.lib().vitseg_ce_scratch_bytes(B, S), dtype=torch.uint8, device=low.device)
+                loss = torch.empty((), dtype=torch.float32, device=low.device)
+                stats = torch.zeros(4, dtype=torch.int64, device=low.device)
+                _lib.check(_ext.ext_symbol("hardloss", "vitseg_hard_ce_loss")(
+                    low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8), None, scratch.data_ptr(), loss.data_ptr(),
+                    B, self.cfg.num_classes, S // self.cfg.patch_size, S, C.byref(opts) if opts is not None else None,
+                    C.byref(hard), 1.0, None, stats.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        return (loss, stats) if return_stats else loss
 
     def _dice_options(self, B: int, S: int, dice_weight, ce_weight, smooth, include_background):
         """The `_lib.CDiceOptions` of a `ce_dice_loss` call (validated on the host); its scratch is cached per (batch, size)."""

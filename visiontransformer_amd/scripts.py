@@ -55,6 +55,12 @@ def add_ce_loss_arguments(ap) -> None:
                     help="train on CE + this many times the soft Dice loss of the softmax probabilities (0: CE alone)")
     ap.add_argument("--dice-smooth", type=float, default=1e-6)
     ap.add_argument("--dice-no-background", action="store_true", help="leave class 0 out of the Dice mean")
+    ap.add_argument("--focal-gamma", type=float, default=0.0, help="focal loss: damp each pixel's CE by (1 - p_y)^gamma (0: off)")
+    ap.add_argument("--ohem-thresh", type=float, default=None,
+                    help="OHEM: average over the pixels whose true-class probability lies under this value (0.7 in mmsegmentation)")
+    ap.add_argument("--ohem-min-kept", type=int, default=0, help="OHEM: never fewer than this many of the hardest pixels of a batch")
+    ap.add_argument("--ohem-keep-fraction", type=float, default=0.0,
+                    help="OHEM: never fewer than this fraction of the valid pixels of a batch")
 
 
 def ce_loss_options(a) -> dict:
@@ -71,6 +77,14 @@ def ce_loss_options(a) -> dict:
         kw["label_smoothing"] = a.label_smoothing
     if getattr(a, "dice_weight", 0.0):
         kw.update(dice_weight=a.dice_weight, dice_smooth=a.dice_smooth, dice_include_background=not a.dice_no_background)
+    if getattr(a, "focal_gamma", 0.0):
+        kw["focal_gamma"] = a.focal_gamma
+    if getattr(a, "ohem_thresh", None) is not None:
+        kw["ohem_thresh"] = a.ohem_thresh
+    if getattr(a, "ohem_min_kept", 0):
+        kw["ohem_min_kept"] = a.ohem_min_kept
+    if getattr(a, "ohem_keep_fraction", 0.0):
+        kw["ohem_keep_fraction"] = a.ohem_keep_fraction
     return kw
 
 
