@@ -209,6 +209,8 @@ CASES = {
                                     dict(frac=0.1, whole=0)),
     "logits at +-60": (1, 17, 14, 224, "big", dict(), dict()),
     "512": (2, 32, 32, 512, "randn", dict(), dict()),
+    # 3200 blocks of the Dice sum pass: the fixed-order reduce of their partials runs its four-chain loop (> 3072)
+    "512, 3200 sum blocks": (25, 2, 32, 512, "randn", dict(), dict()),
     # beyond the issue's list: a smooth that is visible in fp32, other weights, torch's ignore_index
     "smooth 1, weights 2 : 0.5": (2, 5, 7, 28, "randn", dict(smooth=1.0, dice_weight=0.5, ce_weight=2.0, ignore_index=-100,
                                                              include_background=False), dict(frac=0.1)),

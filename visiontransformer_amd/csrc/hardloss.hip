@@ -1,10 +1,11 @@
 // Hard-pixel losses on the fused path (include/vitseg_hardloss.h): focal cross-entropy and online hard example mining on the
-// logits regenerated from the low-res head output, as ce_loss_opts_kernel (decoder_tail.hip) regenerates them.
+// logits regenerated from the low-res head output.  The per-pixel pieces (Pixel, the label rule, the CE gradient term, the block
+// and fixed-order sums) are loss_pixel.hpp's, shared with loss_tail.hip; launch_fused_loss there decides when this chain runs.
 //
 //   ce_i = max(lse - up_y, +0);  q_i = -expm1f(-ce_i);  f_i = w[y] q_i^gamma ce_i;  m_i = q_i^gamma + gamma (1 - q_i) ce_i q_i^(gamma-1)
 //   H = { i valid : ce_i >= tau },  tau = min(loss_thresh, k-th largest ce);  loss = sum_H f / sum_H w[y]
 //
-// Focal alone: hard_count_kernel + hard_count_finish_kernel (den and n_valid from the targets), hard_focal_kernel (one thread
+// Focal alone: loss_tail.hip's count pass + hard_count_finish_kernel (den and n_valid from the targets), hard_focal_kernel (one thread
 // per pixel, loss partials and the gradient), hard_focal_finish_kernel.
 // With OHEM the gradient of one pixel depends on a rank over the whole batch, so the call is a chain on one stream:
 //   A.     hard_plane_kernel     one thread per pixel and step, 4096 pixels per block: ce_i to the fp32 plane (ignored
@@ -22,14 +23,14 @@
 // ranks above +inf.  Histograms and n_valid are integer atomics, the sums fp64 partials in a fixed order: the same bits on
 // every call.
 #include "hardloss.hpp"
-#include "tail_math.hpp"
+#include "loss_pixel.hpp"
 
 namespace vitseg {
 namespace {
 
 constexpr unsigned HARD_NAN = 0x7fc00000u;        // ce of a label outside [0, C) that is not ignored
 constexpr unsigned HARD_IGNORED = 0xbf800000u;    // -1.0f: an ignored pixel's entry of the plane
-constexpr int HARD_PPB = 1024;                    // pixels per block of the count and sum passes (4 per thread)
+constexpr int HARD_PPB = CE_COUNT_PPB;            // pixels per block of the count and sum passes (4 per thread)
 constexpr int HARD_HIST_PPB = 4096;               // pixels per block of pass A and of a histogram round (16 per thread): one
                                                   // flush of the block's bins per 4096 pixels, not per 256
 constexpr int HARD_BINS0 = 2048, HARD_BINS = 1024;   // 11 + 10 + 10 key bits
@@ -80,77 +81,9 @@ __device__ __forceinline__ float hard_ce(float lse, float picked, bool bad) {
     return bad ? __uint_as_float(HARD_NAN) : ce;
 }
 
-// the regenerated logits of one pixel: the taps, fma placement and online log-sum-exp of ce_loss_opts_kernel
-struct Pixel {
-    const float* Z;
-    int b, C, g, y0, y1, x0, x1;
-    float wy0, wy1, wx0, wx1;
-    __device__ __forceinline__ Pixel(const float* Z_, size_t idx, int C_, int g_, int S) : Z(Z_), C(C_), g(g_) {
-        const int X = (int)(idx % S), Y = (int)((idx / S) % S);
-        b = (int)(idx / ((size_t)S * S));
-        const float scale = (float)g / (float)S;
-        taps(Y, scale, g, y0, y1, wy0, wy1);
-        taps(X, scale, g, x0, x1, wx0, wx1);
-    }
-    __device__ __forceinline__ float logit(int c) const {
-        const float* zt = Z + (((size_t)b * C + c) * g + y0) * g;
-        const float* zb = Z + (((size_t)b * C + c) * g + y1) * g;
-        const float top = __fmaf_rn(zt[x0], wx0, __fmul_rn(zt[x1], wx1));
-        const float bot = __fmaf_rn(zb[x0], wx0, __fmul_rn(zb[x1], wx1));
-        return __fmaf_rn(top, wy0, __fmul_rn(bot, wy1));
-    }
-    __device__ __forceinline__ void lse_picked(int t, float& lse, float& picked) const {
-        float m = -INFINITY, ssum = 0.f;
-        picked = 0.f;
-        for (int c = 0; c < C; ++c) {  // online logsumexp
-            const float v = logit(c);
-            if (c == t) picked = v;
-            const float mn = fmaxf(m, v);
-            ssum = ssum * expf(m - mn) + expf(v - mn);
-            m = mn;
-        }
-        lse = m + logf(ssum);
-    }
-};
-
-__device__ __forceinline__ double block_sum4(double v, double* red /* shared [4] */) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    __syncthreads();   // red may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // ---- focal alone ----
 
-// ce_count_kernel with the number of valid pixels beside the summed weights: partial[0 .. nc) and partial[nc .. 2 nc)
-template <typename TargetT>
-__global__ __launch_bounds__(256) void hard_count_kernel(const TargetT* __restrict__ target, CeOpt o, double* __restrict__ partial,
-                                                         size_t npx, int C) {
-    __shared__ float wsh[256];
-    __shared__ double red[4];
-    ce_stage_weights(wsh, o.weight, C);
-    const size_t base = (size_t)blockIdx.x * HARD_PPB + threadIdx.x;
-    double local = 0.0, cnt = 0.0;
-#pragma unroll
-    for (int k = 0; k < HARD_PPB / 256; ++k) {
-        const size_t idx = base + (size_t)k * 256;
-        if (idx < npx) {
-            const long long tl = (long long)target[idx];
-            const bool ignored = o.has_ignore && tl == o.ignore;
-            const bool bad = tl < 0 || tl >= C;
-            local += ignored ? 0.0 : (bad ? 1.0 : (double)wsh[bad ? 0 : (int)tl]);
-            cnt += ignored ? 0.0 : 1.0;
-        }
-    }
-    const double a = block_sum4(local, red), n = block_sum4(cnt, red);
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = a;
-        partial[gridDim.x + blockIdx.x] = n;
-    }
-}
-
+// den and n_valid from the two rows of the count pass (launch_ce_count, with_valid)
 __global__ __launch_bounds__(1024) void hard_count_finish_kernel(const double* __restrict__ partial, int n, long long* __restrict__ st) {
     __shared__ double red[1024];
     ce_fixed_order_sum(partial, n, red);
@@ -163,7 +96,7 @@ __global__ __launch_bounds__(1024) void hard_count_finish_kernel(const double* _
     }
 }
 
-// ce_loss_opts_kernel without the smoothing term, with the focal factors: one thread per pixel
+// the weighted CE with the focal factors: one thread per pixel
 template <typename TargetT>
 __global__ __launch_bounds__(256) void hard_focal_kernel(const float* __restrict__ Z, const TargetT* __restrict__ target,
                                                          float* __restrict__ G, float* __restrict__ plane,
@@ -176,21 +109,15 @@ __global__ __launch_bounds__(256) void hard_focal_kernel(const float* __restrict
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     double local = 0.0;
     if (idx < npx) {
-        const long long tl = (long long)target[idx];
+        const Label l = classify_label((long long)target[idx], o, C);
         const Pixel px(Z, idx, C, g, S);
         const size_t gbase = (size_t)px.b * C * S * S + idx % ((size_t)S * S);   // element (b, 0, Y, X) of G
-        if (o.has_ignore && tl == o.ignore) {
-            if (plane) plane[idx] = __uint_as_float(HARD_IGNORED);
-            if (G)
-                for (int c = 0; c < C; ++c) G[gbase + (size_t)c * S * S] = 0.0f;
-        } else {
-            const bool bad = tl < 0 || tl >= C;
-            const int t = bad ? -1 : (int)tl;
+        if (l.kept) {   // the kept pixels first, the zeros of the ignored ones behind them (ce_loss_opts_kernel, loss_tail.hip)
             float lse, picked, mod, m;
-            px.lse_picked(t, lse, picked);
-            const float ce = hard_ce(lse, picked, bad);
+            px.lse_picked(l.t, lse, picked);
+            const float ce = hard_ce(lse, picked, l.bad);
             focal_terms(ce, gamma, mod, m);
-            const float wy = bad ? 1.f : wsh[t];
+            const float wy = l.bad ? 1.f : wsh[l.t];
             local = (double)(wy * mod) * (double)ce;
             if (plane) plane[idx] = ce;
             if (G) {
@@ -198,9 +125,13 @@ __global__ __launch_bounds__(256) void hard_focal_kernel(const float* __restrict
                 const float a = wy * m;
                 for (int c = 0; c < C; ++c) {
                     const float pc = expf(px.logit(c) - lse);
-                    G[gbase + (size_t)c * S * S] = bad ? NAN : (a * (pc - (c == t ? 1.f : 0.f))) * inv;
+                    G[gbase + (size_t)c * S * S] = l.bad ? NAN : ce_grad(a, pc, c == l.t, inv);
                 }
             }
+        } else {
+            if (plane) plane[idx] = __uint_as_float(HARD_IGNORED);
+            if (G)
+                for (int c = 0; c < C; ++c) G[gbase + (size_t)c * S * S] = 0.0f;
         }
     }
     const double sum = block_sum4(local, red);
@@ -242,15 +173,14 @@ __global__ __launch_bounds__(256) void hard_plane_kernel(const float* __restrict
         const size_t idx = base + (size_t)k * 256;
         bool valid = false;
         if (idx < npx) {
-            const long long tl = (long long)target[idx];
-            if (o.has_ignore && tl == o.ignore) {
+            const Label l = classify_label((long long)target[idx], o, C);
+            if (!l.kept) {
                 plane[idx] = __uint_as_float(HARD_IGNORED);
             } else {
-                const bool bad = tl < 0 || tl >= C;
                 const Pixel px(Z, idx, C, g, S);
                 float lse, picked;
-                px.lse_picked(bad ? -1 : (int)tl, lse, picked);
-                const float ce = hard_ce(lse, picked, bad);
+                px.lse_picked(l.t, lse, picked);
+                const float ce = hard_ce(lse, picked, l.bad);
                 plane[idx] = ce;
                 atomicAdd(&h[__float_as_uint(ce) >> 20], 1u);   // the sign bit is clear: a bin below 2048
                 valid = true;
@@ -352,7 +282,7 @@ __global__ __launch_bounds__(256) void hard_sum_kernel(const float* __restrict__
                                                        const long long* __restrict__ st, CeOpt o, float gamma,
                                                        double* __restrict__ partial, size_t npx, int C) {
     __shared__ float wsh[256];
-    __shared__ double red[4];
+    __shared__ double red[3][4];
     ce_stage_weights(wsh, o.weight, C);
     const unsigned tau = (unsigned)st[ST_TAU];
     const size_t base = (size_t)blockIdx.x * HARD_PPB + threadIdx.x;
@@ -363,9 +293,8 @@ __global__ __launch_bounds__(256) void hard_sum_kernel(const float* __restrict__
         if (idx < npx) {
             const float ce = plane[idx];
             if (hard_member(__float_as_uint(ce), tau)) {
-                const long long tl = (long long)target[idx];
-                const bool bad = tl < 0 || tl >= C;
-                const float wy = bad ? 1.f : wsh[(int)tl];
+                const Label l = classify_label((long long)target[idx], o, C);   // (a member of H is not ignored)
+                const float wy = l.bad ? 1.f : wsh[l.t];
                 float mod, m;
                 focal_terms(ce, gamma, mod, m);
                 lw += (double)wy;
@@ -374,7 +303,7 @@ __global__ __launch_bounds__(256) void hard_sum_kernel(const float* __restrict__
             }
         }
     }
-    const double sw = block_sum4(lw, red), sf = block_sum4(lf, red), sn = block_sum4(ln, red);
+    const double sw = block_sum4(lw, red[0]), sf = block_sum4(lf, red[1]), sn = block_sum4(ln, red[2]);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = sw;
         partial[gridDim.x + blockIdx.x] = sf;
@@ -425,31 +354,29 @@ __global__ __launch_bounds__(256) void hard_grad_kernel(const float* __restrict_
         for (int c = 0; c < C; ++c) G[gbase + (size_t)c * plane_px] = 0.0f;
         return;
     }
-    const long long tl = (long long)target[idx];
-    const bool bad = tl < 0 || tl >= C;
-    const int t = bad ? -1 : (int)tl;
+    const Label l = classify_label((long long)target[idx], o, C);   // (a member of H is not ignored)
     const Pixel px(Z, idx, C, g, S);
     float lse, picked, mod, m;
-    px.lse_picked(t, lse, picked);
+    px.lse_picked(l.t, lse, picked);
     focal_terms(ce, gamma, mod, m);
     const float inv = gscale / (float)((const double*)st)[ST_DEN];
-    const float a = (bad ? 1.f : wsh[t]) * m;
+    const float a = (l.bad ? 1.f : wsh[l.t]) * m;
     for (int c = 0; c < C; ++c) {
         const float pc = expf(px.logit(c) - lse);
-        G[gbase + (size_t)c * plane_px] = bad ? NAN : (a * (pc - (c == t ? 1.f : 0.f))) * inv;
+        G[gbase + (size_t)c * plane_px] = l.bad ? NAN : ce_grad(a, pc, c == l.t, inv);
     }
 }
 
-bool ohem_on(const vitseg_hard_options& h) { return !(h.loss_thresh == INFINITY && h.min_kept == 0 && h.keep_q16 == 0); }
-
 }  // namespace
+
+bool hard_ohem_on(const vitseg_hard_options& h) { return !(h.loss_thresh == INFINITY && h.min_kept == 0 && h.keep_q16 == 0); }
 
 size_t hard_loss_scratch_bytes(int B, int S) {
     if (B < 1 || S < 1 || (size_t)B * S * S >= ((size_t)1 << 31)) return 0;
     return layout(B, S).total;
 }
 
-int check_hard_options(const vitseg_hard_options& h, const vitseg_ce_options* ce, int B, int C, int S) {
+int check_hard_options(const vitseg_hard_options& h, int B, int C, int S) {
     VITSEG_CHECK_ARG(h.gamma >= 0.f && h.gamma < INFINITY, VITSEG_EINVAL, "hard loss: gamma %f is negative or not finite",
                      (double)h.gamma);   // (a NaN fails both)
     VITSEG_CHECK_ARG(h.loss_thresh >= 0.f, VITSEG_EINVAL, "hard loss: loss_thresh %f is negative or NaN", (double)h.loss_thresh);
@@ -461,23 +388,12 @@ int check_hard_options(const vitseg_hard_options& h, const vitseg_ce_options* ce
     VITSEG_CHECK_ARG(h.scratch && ((uintptr_t)h.scratch & 7) == 0, VITSEG_EINVAL, "hard loss: scratch is null or not 8-byte aligned");
     VITSEG_CHECK_ARG(h.scratch_bytes >= hard_loss_scratch_bytes(B, S), VITSEG_EINVAL, "hard loss: scratch %zu < required %zu",
                      h.scratch_bytes, hard_loss_scratch_bytes(B, S));
-    if (ce) {
-        if (int rc = check_ce_options(*ce, B, C, S)) return rc;
-        VITSEG_CHECK_ARG(ce->label_smoothing == 0.f, VITSEG_EINVAL,
-                         "hard loss: label smoothing %f cannot be combined with the focal / OHEM options", (double)ce->label_smoothing);
-    }
     return VITSEG_OK;
 }
 
-int launch_hard_ce_loss(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B,
-                        int C, int g, int S, const vitseg_ce_options* ce, const vitseg_hard_options& h, hipStream_t s,
-                        float gscale, float* pixel_loss, long long* stats) {
-    VITSEG_CHECK_ARG(Z && target && partial && loss, VITSEG_EINVAL, "hard loss: null pointer");
-    if (int rc = check_hard_options(h, ce, B, C, S)) return rc;
-    const bool ohem = ohem_on(h);
-    if (h.gamma == 0.f && !ohem && !pixel_loss && !stats)   // nothing to do: the existing launches, their bits
-        return ce ? launch_ce_loss_opts(Z, target, target_is_u8, G, partial, loss, B, C, g, S, *ce, s, gscale)
-                  : launch_ce_loss(Z, target, target_is_u8, G, partial, loss, B, C, g, S, s, gscale);
+int launch_hard_loss(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B, int C,
+                     int g, int S, const FusedLoss& f, hipStream_t s, float gscale) {
+    const vitseg_hard_options& h = *f.hard;
     const size_t npx = (size_t)B * S * S;
     const Layout l = layout(B, S);
     char* base = (char*)h.scratch;
@@ -485,39 +401,29 @@ int launch_hard_ce_loss(const float* Z, const void* target, int target_is_u8, fl
     unsigned* hist = (unsigned*)(base + l.hist);
     double* cpart = (double*)(base + l.cpart);
     double* spart = (double*)(base + l.spart);
-    float* plane = pixel_loss ? pixel_loss : (float*)(base + l.plane);
+    float* plane = f.pixel_loss ? f.pixel_loss : (float*)(base + l.plane);
     const unsigned nb = (unsigned)((npx + 255) / 256);
     const unsigned nh = (unsigned)((npx + HARD_HIST_PPB - 1) / HARD_HIST_PPB);
-    const CeOpt o = ce ? CeOpt{ce->class_weight, (long long)ce->ignore_index, ce->has_ignore_index != 0, 0.f}
-                       : CeOpt{nullptr, 0, 0, 0.f};
-    const uint8_t* t8 = (const uint8_t*)target;
-    const long long* t64 = (const long long*)target;
-    if (!ohem) {
-        if (target_is_u8)
-            hipLaunchKernelGGL(hard_count_kernel<uint8_t>, dim3(l.nc), dim3(256), 0, s, t8, o, cpart, npx, C);
-        else
-            hipLaunchKernelGGL(hard_count_kernel<long long>, dim3(l.nc), dim3(256), 0, s, t64, o, cpart, npx, C);
-        VITSEG_LAUNCH_CHECK("hard count");
+    const CeOpt o = ce_opt_of(f.ce, false);
+    if (!hard_ohem_on(h)) {
+        if (int rc = launch_ce_count(target, target_is_u8, o, cpart, npx, C, true, s)) return rc;
         hipLaunchKernelGGL(hard_count_finish_kernel, dim3(1), dim3(1024), 0, s, cpart, (int)l.nc, st);
         VITSEG_LAUNCH_CHECK("hard count finish");
-        if (target_is_u8)
-            hipLaunchKernelGGL(hard_focal_kernel<uint8_t>, dim3(nb), dim3(256), 0, s, Z, t8, G, pixel_loss, partial, st, o, h.gamma,
-                               B, C, g, S, gscale);
-        else
-            hipLaunchKernelGGL(hard_focal_kernel<long long>, dim3(nb), dim3(256), 0, s, Z, t64, G, pixel_loss, partial, st, o,
+        with_target_type(target, target_is_u8, [&](auto* t) {
+            hipLaunchKernelGGL(hard_focal_kernel<target_t<decltype(t)>>, dim3(nb), dim3(256), 0, s, Z, t, G, f.pixel_loss, partial, st, o,
                                h.gamma, B, C, g, S, gscale);
+        });
         VITSEG_LAUNCH_CHECK("hard focal");
-        hipLaunchKernelGGL(hard_focal_finish_kernel, dim3(1), dim3(1024), 0, s, partial, (int)nb, st, loss, stats);
+        hipLaunchKernelGGL(hard_focal_finish_kernel, dim3(1), dim3(1024), 0, s, partial, (int)nb, st, loss, f.stats);
         VITSEG_LAUNCH_CHECK("hard focal finish");
         return VITSEG_OK;
     }
     // the state row and the histogram are adjacent: n_valid and every bin start at 0 (each scan leaves the bins zeroed again)
     hipError_t e = hipMemsetAsync(base + l.state, 0, l.cpart - l.state, s);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(hard loss state)");
-    if (target_is_u8)
-        hipLaunchKernelGGL(hard_plane_kernel<uint8_t>, dim3(nh), dim3(256), 0, s, Z, t8, plane, hist, st, o, B, C, g, S);
-    else
-        hipLaunchKernelGGL(hard_plane_kernel<long long>, dim3(nh), dim3(256), 0, s, Z, t64, plane, hist, st, o, B, C, g, S);
+    with_target_type(target, target_is_u8, [&](auto* t) {
+        hipLaunchKernelGGL(hard_plane_kernel<target_t<decltype(t)>>, dim3(nh), dim3(256), 0, s, Z, t, plane, hist, st, o, B, C, g, S);
+    });
     VITSEG_LAUNCH_CHECK("hard plane");
     const float thresh = h.loss_thresh == 0.f ? 0.f : h.loss_thresh;   // -0 -> +0
     for (int round = 0; round < 3; ++round) {
@@ -528,20 +434,17 @@ int launch_hard_ce_loss(const float* Z, const void* target, int target_is_u8, fl
         hipLaunchKernelGGL(hard_scan_kernel, dim3(1), dim3(1024), 0, s, hist, st, thresh, (long long)h.min_kept, h.keep_q16, round);
         VITSEG_LAUNCH_CHECK("hard scan");
     }
-    if (target_is_u8)
-        hipLaunchKernelGGL(hard_sum_kernel<uint8_t>, dim3(l.ns), dim3(256), 0, s, plane, t8, st, o, h.gamma, spart, npx, C);
-    else
-        hipLaunchKernelGGL(hard_sum_kernel<long long>, dim3(l.ns), dim3(256), 0, s, plane, t64, st, o, h.gamma, spart, npx, C);
+    with_target_type(target, target_is_u8, [&](auto* t) {
+        hipLaunchKernelGGL(hard_sum_kernel<target_t<decltype(t)>>, dim3(l.ns), dim3(256), 0, s, plane, t, st, o, h.gamma, spart, npx, C);
+    });
     VITSEG_LAUNCH_CHECK("hard sum");
-    hipLaunchKernelGGL(hard_reduce_kernel, dim3(1), dim3(1024), 0, s, spart, (int)l.ns, st, loss, stats);
+    hipLaunchKernelGGL(hard_reduce_kernel, dim3(1), dim3(1024), 0, s, spart, (int)l.ns, st, loss, f.stats);
     VITSEG_LAUNCH_CHECK("hard reduce");
     if (G) {
-        if (target_is_u8)
-            hipLaunchKernelGGL(hard_grad_kernel<uint8_t>, dim3(nb), dim3(256), 0, s, Z, t8, plane, G, st, o, h.gamma, B, C, g, S,
-                               gscale);
-        else
-            hipLaunchKernelGGL(hard_grad_kernel<long long>, dim3(nb), dim3(256), 0, s, Z, t64, plane, G, st, o, h.gamma, B, C, g, S,
-                               gscale);
+        with_target_type(target, target_is_u8, [&](auto* t) {
+            hipLaunchKernelGGL(hard_grad_kernel<target_t<decltype(t)>>, dim3(nb), dim3(256), 0, s, Z, t, plane, G, st, o, h.gamma, B, C, g,
+                               S, gscale);
+        });
         VITSEG_LAUNCH_CHECK("hard gradient");
     }
     return VITSEG_OK;
@@ -560,8 +463,13 @@ int vitseg_hard_ce_loss(const float* lowres, const void* target, int target_is_u
                         float loss_scale, float* pixel_loss, int64_t* stats, void* stream) {
     VITSEG_CHECK_ARG(batch >= 1 && C >= 1 && g >= 1 && S >= g, VITSEG_EINVAL, "hard_ce_loss: bad shape");
     VITSEG_CHECK_ARG(hard, VITSEG_EINVAL, "hard_ce_loss: the hard options are null");
-    return vitseg::launch_hard_ce_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S, ce_opts,
-                                       *hard, (hipStream_t)stream, loss_scale, pixel_loss, (long long*)stats);
+    vitseg::FusedLoss f;
+    f.ce = ce_opts;
+    f.hard = hard;
+    f.pixel_loss = pixel_loss;
+    f.stats = (long long*)stats;
+    return vitseg::launch_fused_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S, f,
+                                     (hipStream_t)stream, loss_scale);
 }
 
 }  // extern "C"

@@ -1,7 +1,11 @@
 // Host-side launchers of the gfx950 kernels (one .hip file each).  All launchers only
 // enqueue work on `stream`; none allocates or synchronises.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
+
+struct vitseg_hard_options;   // include/vitseg_hardloss.h
 
 namespace vitseg {
 
@@ -134,26 +138,38 @@ int launch_window_gather(const void* src, int src_is_u8, int n, int H, int W, in
 int launch_window_blend(const float* lowres, const int* oy, int ny, const int* ox, int nx, const float* w, int n, int C, int g,
                         int S, int H, int W, float* logits, uint8_t* mask, hipStream_t s);
 
-// CE loss on the (virtually) upsampled logits (a13); optional full-resolution gradient G
+// The fused losses on the (virtually) upsampled logits (a13; loss_tail.hip, hardloss.hip); optional full-resolution gradient G.
+// Which loss: nothing set = the plain CE mean; ce = ignore_index / class weights / label smoothing (a count pass leaves the
+// mean's denominator on the device, ce->scratch, ce_opts_scratch_bytes); dice = ce_weight CE + dice_weight soft Dice (a sum
+// pass leaves I, P, T per class on the device, dice->scratch, dice_scratch_bytes); hard = focal CE / OHEM (hard->scratch,
+// hard_loss_scratch_bytes of hardloss.hpp).  ce goes with either; dice and hard exclude each other, and hard takes no smoothing.
+struct FusedLoss {
+    const vitseg_ce_options* ce = nullptr;
+    const vitseg_dice_options* dice = nullptr;
+    const vitseg_hard_options* hard = nullptr;
+    float* terms = nullptr;        // dice: device float[3] = {loss, CE, dice}, required
+    long long* stats = nullptr;    // hard: device int64[4] = {n_valid, k, |H|, bits of tau}, or null
+    float* pixel_loss = nullptr;   // hard: device fp32 [B, S, S], every pixel's CE, or null
+};
+// calls f with the target pointer in its own type: f(const uint8_t*) or f(const long long*); target_t<decltype(t)> names
+// that type for a kernel template
+template <typename P>
+using target_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+template <typename F>
+inline void with_target_type(const void* target, int target_is_u8, F&& f) {
+    if (target_is_u8)
+        f((const uint8_t*)target);
+    else
+        f((const long long*)target);
+}
 size_t ce_partial_count(int B, int S);
-int launch_ce_loss(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B,
-                   int C, int g, int S, hipStream_t s, float gscale = 1.0f);
-// ... with ignore_index / class weights / label smoothing (vitseg_ce_options): a count pass over the targets leaves the
-// mean's denominator on the device (opts.scratch, ce_opts_scratch_bytes), then the loss / gradient kernel with the options.
-// check_ce_options: the argument checks of the options alone (VITSEG_EINVAL), for callers that launch other work first.
 size_t ce_opts_scratch_bytes(int B, int S);
-int check_ce_options(const vitseg_ce_options& o, int B, int C, int S);
-int launch_ce_loss_opts(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B,
-                        int C, int g, int S, const vitseg_ce_options& opts, hipStream_t s, float gscale = 1.0f);
-// ... plus the soft-Dice region term (vitseg_dice_options): a sum pass and a fixed-order reduce leave I, P, T per class on
-// the device (dice.scratch, dice_scratch_bytes), then one kernel forms both gradients.  terms: device float[3] = {loss, CE,
-// dice}; loss_out (optional): the total once more.  ce may be null (the plain CE).  check_dice_options: the argument checks
-// of both option structs (VITSEG_EINVAL), for callers that launch other work first.
 size_t dice_scratch_bytes(int B, int C, int S);
-int check_dice_options(const vitseg_dice_options& d, const vitseg_ce_options* ce, int B, int C, int S);
-int launch_ce_dice_loss(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* terms,
-                        float* loss_out, int B, int C, int g, int S, const vitseg_ce_options* ce,
-                        const vitseg_dice_options& dice, hipStream_t s, float gscale = 1.0f);
+// the argument checks of the options alone (VITSEG_EINVAL), for callers that launch other work first
+int check_fused_loss(const FusedLoss& f, int B, int C, int S);
+// partial: ce_partial_count doubles.  loss: the device float of the total (with dice optional: terms[0] holds it too).
+int launch_fused_loss(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B, int C,
+                      int g, int S, const FusedLoss& f, hipStream_t s, float gscale = 1.0f);
 
 // CLS token rows of the embedding output: X[B*Np + b] = cls + pos[0]  (a3)
 int launch_cls_rows(const float* cls, const float* pos, float* X, int B, int Np, int D, hipStream_t s);

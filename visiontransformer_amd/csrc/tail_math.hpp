@@ -1,4 +1,5 @@
-// The decoder tail's exact per-pixel arithmetic, shared by decoder_tail.hip (one tile) and window.hip (overlapping tiles):
+// The decoder tail's exact per-pixel arithmetic, shared by decoder_tail.hip (one tile), window.hip (overlapping tiles) and,
+// for the taps, the losses on the regenerated logits (loss_pixel.hpp):
 // the bilinear taps of F.interpolate(mode='bilinear', align_corners=False) and ATen's fp32 sigmoid.
 #pragma once
 #include "common.hpp"
@@ -47,40 +48,6 @@ __device__ __forceinline__ float sigmoid_aten(float x) {
 __device__ __forceinline__ bool argmax_settled(float t1, float margin) {
     const float at = fabsf(t1);
     return (at <= 2.0f && margin >= 1e-4f) || (at <= 8.0f && margin >= 4e-3f);
-}
-
-// ---- shared by the cross-entropy kernels of decoder_tail.hip and hardloss.hip ----
-
-// the fixed-order sum of ce_finish_kernel: 4 independent strided chains per thread, then a tree; the result is in red[0]
-__device__ __forceinline__ void ce_fixed_order_sum(const double* __restrict__ partial, int n, double* red) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int i = threadIdx.x;
-    for (; i + 3 * 1024 < n; i += 4 * 1024) {
-        s0 += partial[i];
-        s1 += partial[i + 1024];
-        s2 += partial[i + 2 * 1024];
-        s3 += partial[i + 3 * 1024];
-    }
-    for (; i < n; i += 1024) s0 += partial[i];
-    red[threadIdx.x] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-}
-
-struct CeOpt {
-    const float* weight;   // [C] or null (all ones)
-    long long ignore;      // read only when has_ignore
-    int has_ignore;
-    float eps;
-};
-
-// class weights of the block in LDS (C <= 255); every thread of the block calls this
-__device__ __forceinline__ void ce_stage_weights(float* wsh, const float* __restrict__ weight, int C) {
-    if ((int)threadIdx.x < C) wsh[threadIdx.x] = weight ? weight[threadIdx.x] : 1.f;
-    __syncthreads();
 }
 
 }  // namespace vitseg

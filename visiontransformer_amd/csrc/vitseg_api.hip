@@ -301,8 +301,8 @@ size_t vitseg_ce_scratch_bytes(int batch, int S) { return ce_partial_count(batch
 int vitseg_ce_loss(const float* lowres, const void* target, int target_is_u8, float* grad_logits, void* scratch,
                    float* loss, int batch, int C, int g, int S, void* stream) {
     VITSEG_CHECK_ARG(batch >= 1 && C >= 1 && g >= 1 && S >= g, VITSEG_EINVAL, "ce_loss: bad shape");
-    return launch_ce_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S,
-                          (hipStream_t)stream);
+    return launch_fused_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S, FusedLoss{},
+                             (hipStream_t)stream);
 }
 
 size_t vitseg_ce_options_scratch_bytes(int batch, int S) {
@@ -313,11 +313,10 @@ int vitseg_ce_loss_opts(const float* lowres, const void* target, int target_is_u
                         float* loss, int batch, int C, int g, int S, const vitseg_ce_options* opts, float loss_scale,
                         void* stream) {
     VITSEG_CHECK_ARG(batch >= 1 && C >= 1 && g >= 1 && S >= g, VITSEG_EINVAL, "ce_loss: bad shape");
-    if (!opts)   // the plain kernels, as vitseg_ce_loss launches them
-        return launch_ce_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S,
-                              (hipStream_t)stream, loss_scale);
-    return launch_ce_loss_opts(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S, *opts,
-                               (hipStream_t)stream, loss_scale);
+    FusedLoss f;
+    f.ce = opts;   // null: the plain kernels, as vitseg_ce_loss launches them
+    return launch_fused_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, loss, batch, C, g, S, f,
+                             (hipStream_t)stream, loss_scale);
 }
 
 size_t vitseg_dice_options_scratch_bytes(int batch, int C, int S) {
@@ -329,8 +328,12 @@ int vitseg_ce_dice_loss(const float* lowres, const void* target, int target_is_u
                         const vitseg_dice_options* dice, float loss_scale, void* stream) {
     VITSEG_CHECK_ARG(batch >= 1 && C >= 1 && g >= 1 && S >= g, VITSEG_EINVAL, "ce_dice_loss: bad shape");
     VITSEG_CHECK_ARG(dice, VITSEG_EINVAL, "ce_dice_loss: the dice options are null");
-    return launch_ce_dice_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, terms, nullptr, batch, C, g, S, ce,
-                               *dice, (hipStream_t)stream, loss_scale);
+    FusedLoss f;
+    f.ce = ce;
+    f.dice = dice;
+    f.terms = terms;
+    return launch_fused_loss(lowres, target, target_is_u8, grad_logits, (double*)scratch, nullptr, batch, C, g, S, f,
+                             (hipStream_t)stream, loss_scale);
 }
 
 int vitseg_profile_enable(int on) {
