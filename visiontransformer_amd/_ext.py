@@ -23,6 +23,7 @@ OPTIM_VERSION = 100   # include/vitseg_optim.h VITSEG_OPTIM_VERSION
 CURVES_VERSION = 100   # include/vitseg_curves.h VITSEG_CURVES_VERSION
 DECIDE_VERSION = 100   # include/vitseg_decide.h VITSEG_DECIDE_VERSION
 HARDLOSS_VERSION = 100   # include/vitseg_hardloss.h VITSEG_HARDLOSS_VERSION
+CLDICE_VERSION = 100   # include/vitseg_cldice.h VITSEG_CLDICE_VERSION
 
 
 class CHardOptions(C.Structure):
@@ -32,6 +33,16 @@ class CHardOptions(C.Structure):
 
 
 phard = C.POINTER(CHardOptions)
+
+
+class CClDiceOptions(C.Structure):
+    """struct vitseg_cldice_options (include/vitseg_cldice.h)."""
+    _fields_ = [("weight", C.c_float), ("smooth", C.c_float), ("iters", C.c_int32), ("K", C.c_int32),
+                ("classes", C.POINTER(C.c_int32)), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("prob_planes", C.c_void_p), ("class_terms", C.c_void_p)]
+
+
+pcld = C.POINTER(CClDiceOptions)
 
 EXT_SIGNATURES = {
     # region outlines: polygon rings with holes (polygons.py)
@@ -85,6 +96,18 @@ EXT_LATER = {
         ("vitseg_backward_hard", i32, [_lib.pcfg, i32, vp, vp, vp, i32, i32, f32, _lib.u64, vp, i32, vp, vp, vp, f32, vp, vp, sz,
                                        vp, _lib.popt, phard, vp]),
     ]),
+    # the soft-clDice loss: the soft skeleton, the plane loss and the term on the fused loss path (cldice.py, model.ce_cldice_loss)
+    "cldice": ("vitseg_cldice.h", "the soft-clDice loss", [
+        ("vitseg_cldice_version", i32, []),
+        ("vitseg_soft_skeleton_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_soft_skeleton", i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
+        ("vitseg_soft_cldice_scratch_bytes", sz, [i32, i32, i32, i32]),
+        ("vitseg_soft_cldice", i32, [vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp]),
+        ("vitseg_cldice_scratch_bytes", sz, [i32, i32, i32, i32]),
+        ("vitseg_ce_cldice_loss", i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, _lib.popt, _lib.pdice, pcld, f32, vp]),
+        ("vitseg_backward_cldice", i32, [_lib.pcfg, i32, vp, vp, vp, i32, i32, f32, _lib.u64, vp, i32, vp, vp, vp, f32, vp, vp, sz,
+                                         vp, _lib.popt, _lib.pdice, pcld, vp]),
+    ]),
 }
 EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
                 "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION),
@@ -92,7 +115,8 @@ EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
                 "optim": ("vitseg_optim_version", OPTIM_VERSION),
                 "curves": ("vitseg_curves_version", CURVES_VERSION),
                 "decide": ("vitseg_decide_version", DECIDE_VERSION),
-                "hardloss": ("vitseg_hardloss_version", HARDLOSS_VERSION)}
+                "hardloss": ("vitseg_hardloss_version", HARDLOSS_VERSION),
+                "cldice": ("vitseg_cldice_version", CLDICE_VERSION)}
 
 
 def ext_symbol(family: str, name: str):

@@ -4,6 +4,7 @@
 // instead of being read back from HBM, so a loss costs one pass over the targets.  The per-pixel pieces: loss_pixel.hpp.
 #include <float.h>
 
+#include "cldice.hpp"
 #include "hardloss.hpp"
 #include "kernels.hpp"
 #include "loss_pixel.hpp"
@@ -218,13 +219,16 @@ constexpr DiceOpt CE_ALONE{1.f, 0.f, 0.f, 0, 1, 0};
 // The body of ce_loss_opts_kernel (!DICE) and ce_dice_kernel (DICE): the CE options and, DICE, the Dice gradient; one thread
 // per pixel, one store per element of G.  den: the device double of the count pass, or (DICE only) null: no CE options,
 // den_plain = B S S.  sums (DICE): I | P | T, C doubles each.  !DICE: den_plain, sums and d are not read, the CE term is
-// formed and its gradient is not scaled by a ce_weight.
-template <typename TargetT, bool DICE>
+// formed and its gradient is not scaled by a ce_weight.  CLD (with DICE; d may leave either term out): the soft-clDice term's
+// gradient by the softmax chain rule, p_j (g_j - sum_c g_c p_c), from the planes gcl [K, B, S, S] of g_c = d term / d p_c
+// (cldice.hip; already scaled by the term's weight and gscale) of the classes cmap lists, inside the same one store.
+template <typename TargetT, bool DICE, bool CLD = false>
 __device__ __forceinline__ void ce_opts_pixel(const float* __restrict__ Z, const TargetT* __restrict__ target,
                                               float* __restrict__ G, double* __restrict__ partial,
                                               double* __restrict__ spartial, const double* __restrict__ den, double den_plain,
                                               const double* __restrict__ sums, const CeOpt& o, const DiceOpt& d, int B, int C,
-                                              int g, int S, float gscale) {
+                                              int g, int S, float gscale, const float* __restrict__ gcl = nullptr,
+                                              const CldClassMap* cmap = nullptr) {
     __shared__ float wsh[256], a0sh[DICE ? 256 : 1], a1sh[DICE ? 256 : 1];   // a_c of a pixel whose label is not c / is c
     __shared__ double red[4], sred[4];
     const bool use_ce = !DICE || d.use_ce, use_dice = DICE && d.use_dice;
@@ -267,6 +271,10 @@ __device__ __forceinline__ void ce_opts_pixel(const float* __restrict__ Z, const
                 if (use_ce) inv = gscale / (float)(DICE && !den ? den_plain : *den);   // den == 0: inf, and 0 * inf = NaN as the arithmetic gives
                 if (use_dice)   // sum_k a_k p_k (a bad label: its P_c, hence a_c, are NaN already)
                     for (int c = 0; c < C; ++c) sap += (c == l.t ? a1sh[c] : a0sh[c]) * expf(px.logit(c) - lse);
+                float sgp = 0.f;   // sum_c g_c p_c over the listed classes
+                if (CLD)
+                    for (int c = 0; c < C; ++c)
+                        if (const int slot = cmap->slot[c]) sgp += gcl[(size_t)(slot - 1) * npx + idx] * expf(px.logit(c) - lse);
                 const float swf = (float)ss.sw;
                 const float dwg = d.dw * gscale;
                 for (int c = 0; c < C; ++c) {
@@ -280,6 +288,10 @@ __device__ __forceinline__ void ce_opts_pixel(const float* __restrict__ Z, const
                     if (use_dice) {
                         const float dv = dwg * (pc * ((c == l.t ? a1sh[c] : a0sh[c]) - sap));
                         out = use_ce ? out + dv : dv;
+                    }
+                    if (CLD) {
+                        const int slot = cmap->slot[c];
+                        out += pc * ((slot ? gcl[(size_t)(slot - 1) * npx + idx] : 0.f) - sgp);
                     }
                     G[at.out_index(c, C, S)] = l.bad ? NAN : out;
                 }
@@ -318,16 +330,39 @@ __global__ __launch_bounds__(256) void ce_dice_kernel(const float* __restrict__ 
     ce_opts_pixel<TargetT, true>(Z, target, G, partial, spartial, den, den_plain, sums, o, d, B, C, g, S, gscale);
 }
 
+template <typename TargetT>
+__global__ __launch_bounds__(256) void ce_cldice_kernel(const float* __restrict__ Z, const TargetT* __restrict__ target,
+                                                        float* __restrict__ G, double* __restrict__ partial,
+                                                        double* __restrict__ spartial, const double* __restrict__ den,
+                                                        double den_plain, const double* __restrict__ sums, CeOpt o, DiceOpt d,
+                                                        int B, int C, int g, int S, float gscale, const float* __restrict__ gcl,
+                                                        CldClassMap cmap) {
+    ce_opts_pixel<TargetT, true, true>(Z, target, G, partial, spartial, den, den_plain, sums, o, d, B, C, g, S, gscale, gcl, &cmap);
+}
+
+// terms of a vitseg_ce_cldice_loss call whose clDice term is left out: {loss, CE, dice, 0}; without the Dice options the
+// finish kernel wrote the total alone, to terms[0]
+__global__ void cld_terms_fill_kernel(float* __restrict__ terms, int have_dice, float* __restrict__ loss) {
+    if (!have_dice) {
+        terms[1] = terms[0];
+        terms[2] = 0.f;
+        if (loss) *loss = terms[0];
+    }
+    terms[3] = 0.f;
+}
+
 // The finish of the CE family, one block.  CE = (sum of partial + sum of spartial) / den, the two sums divided apart;
 // spartial: the smoothing partials, or null (eps == 0: they were not written); den: a device double, or null: den_plain
 // (= B S S, the plain mean).  1.0 / den_plain here and a host's 1.0 / (B S S) are the same correctly rounded fp64 division
 // of the same operands: the same bits.  dice from the 3 C sums in fp64.  The total is cw CE + dw dice; a term that was not
 // formed is an exact 0, and CE alone (CE_ALONE: cw = 1) is 1.0 * CE, the same double.  terms (optional) = {total, CE, dice};
-// loss_out (optional): the total.
+// loss_out (optional): the total.  extra (optional): {weight cldice, cldice} of cldice.hip: the first joins the total, the
+// second is terms[3].
 __global__ __launch_bounds__(1024) void ce_finish_kernel(const double* __restrict__ partial, const double* __restrict__ spartial,
                                                          int n, const double* __restrict__ den, double den_plain,
                                                          const double* __restrict__ sums, int C, DiceOpt d,
-                                                         float* __restrict__ terms, float* __restrict__ loss_out) {
+                                                         float* __restrict__ terms, float* __restrict__ loss_out,
+                                                         const double* __restrict__ extra = nullptr) {
     __shared__ double red[1024];
     double total = 0.0;
     if (d.use_ce) {
@@ -350,10 +385,12 @@ __global__ __launch_bounds__(1024) void ce_finish_kernel(const double* __restric
         double loss = 0.0;
         if (d.use_ce) loss = (double)d.cw * total;
         if (d.use_dice) loss += (double)d.dw * dice;
+        if (extra) loss += extra[0];
         if (terms) {
             terms[0] = (float)loss;
             terms[1] = (float)total;
             terms[2] = (float)dice;
+            if (extra) terms[3] = (float)extra[1];
         }
         if (loss_out) *loss_out = (float)loss;
     }
@@ -372,11 +409,11 @@ int check_ce_options(const vitseg_ce_options& o, int B, int C, int S) {
     return VITSEG_OK;
 }
 
-int check_dice_options(const vitseg_dice_options& d, int B, int C, int S) {
+int check_dice_options(const vitseg_dice_options& d, int B, int C, int S, bool other_term = false) {
     auto weight_ok = [](float v) { return v >= 0.f && v <= FLT_MAX; };   // (a NaN fails both)
     VITSEG_CHECK_ARG(weight_ok(d.ce_weight) && weight_ok(d.dice_weight), VITSEG_EINVAL,
                      "dice options: ce_weight %f / dice_weight %f must be finite and >= 0", (double)d.ce_weight, (double)d.dice_weight);
-    VITSEG_CHECK_ARG(d.ce_weight != 0.f || d.dice_weight != 0.f, VITSEG_EINVAL, "dice options: both weights are 0");
+    VITSEG_CHECK_ARG(other_term || d.ce_weight != 0.f || d.dice_weight != 0.f, VITSEG_EINVAL, "dice options: both weights are 0");
     VITSEG_CHECK_ARG(weight_ok(d.smooth), VITSEG_EINVAL, "dice options: smooth %f must be finite and >= 0", (double)d.smooth);
     VITSEG_CHECK_ARG(C >= 1 && C <= 255, VITSEG_EINVAL, "dice options: %d classes (1..255)", C);
     VITSEG_CHECK_ARG(d.include_background || C >= 2, VITSEG_EINVAL, "dice options: include_background = 0 needs C >= 2");
@@ -418,10 +455,14 @@ int launch_ce_count(const void* target, int target_is_u8, const CeOpt& o, double
 
 int check_fused_loss(const FusedLoss& f, int B, int C, int S) {
     VITSEG_CHECK_ARG(!(f.dice && f.hard), VITSEG_EINVAL, "fused loss: the dice and the hard options cannot be combined");
+    VITSEG_CHECK_ARG(!(f.cldice && f.hard), VITSEG_EINVAL, "fused loss: focal / OHEM with the clDice term are not built");
+    VITSEG_CHECK_ARG(!f.cldice || f.terms4, VITSEG_EINVAL, "fused loss: the clDice options need the four terms");
+    if (f.cldice)
+        if (int rc = check_cldice_options(*f.cldice, B, C, S)) return rc;
     if (f.hard)
         if (int rc = check_hard_options(*f.hard, B, C, S)) return rc;
     if (f.dice)
-        if (int rc = check_dice_options(*f.dice, B, C, S)) return rc;
+        if (int rc = check_dice_options(*f.dice, B, C, S, f.cldice && f.cldice->weight != 0.f)) return rc;
     if (f.ce)
         if (int rc = check_ce_options(*f.ce, B, C, S)) return rc;
     VITSEG_CHECK_ARG(!(f.hard && f.ce) || f.ce->label_smoothing == 0.f, VITSEG_EINVAL,
@@ -431,16 +472,26 @@ int check_fused_loss(const FusedLoss& f, int B, int C, int S) {
 
 int launch_fused_loss(const float* Z, const void* target, int target_is_u8, float* G, double* partial, float* loss, int B, int C,
                       int g, int S, const FusedLoss& f, hipStream_t s, float gscale) {
-    VITSEG_CHECK_ARG(Z && target && partial && (f.dice ? f.terms : loss), VITSEG_EINVAL, "%s: null pointer",
-                     f.dice ? "ce_dice_loss" : f.hard ? "hard loss" : "ce_loss");
+    VITSEG_CHECK_ARG(Z && target && partial && (f.dice || f.terms4 ? f.terms : loss), VITSEG_EINVAL, "%s: null pointer",
+                     f.terms4 ? "ce_cldice_loss" : f.dice ? "ce_dice_loss" : f.hard ? "hard loss" : "ce_loss");
     if (int rc = check_fused_loss(f, B, C, S)) return rc;
+    const bool cld_on = f.cldice && f.cldice->weight != 0.f;
+    if (f.terms4 && !cld_on) {   // the term is left out: the launches of the call without it, then the fourth entry
+        FusedLoss f3 = f;
+        f3.cldice = nullptr;
+        f3.terms4 = false;
+        if (int rc = launch_fused_loss(Z, target, target_is_u8, G, partial, f.dice ? loss : f.terms, B, C, g, S, f3, s, gscale)) return rc;
+        hipLaunchKernelGGL(cld_terms_fill_kernel, dim3(1), dim3(1), 0, s, f.terms, f.dice ? 1 : 0, loss);
+        VITSEG_LAUNCH_CHECK("cldice terms");
+        return VITSEG_OK;
+    }
     // the hard options at gamma 0 with OHEM off and no optional output ask for nothing beyond the CE below: its launches
     if (f.hard && (f.hard->gamma != 0.f || hard_ohem_on(*f.hard) || f.pixel_loss || f.stats))
         return launch_hard_loss(Z, target, target_is_u8, G, partial, loss, B, C, g, S, f, s, gscale);
     const size_t npx = (size_t)B * S * S;
     const unsigned nb = (unsigned)ce_partial_count(B, S), nc = (unsigned)ce_count_partial_count(B, S);
     const double den_plain = (double)npx;
-    if (!f.ce && !f.dice) {
+    if (!f.ce && !f.dice && !cld_on) {
         with_target_type(target, target_is_u8, [&](auto* t) {
             hipLaunchKernelGGL(ce_loss_kernel<target_t<decltype(t)>>, dim3(nb), dim3(256), 0, s, Z, t, G, partial, B, C, g, S, gscale);
         });
@@ -475,9 +526,15 @@ int launch_fused_loss(const float* Z, const void* target, int target_is_u8, floa
         hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * C), dim3(1024), 0, s, dpart, (int)nd, sums);
         VITSEG_LAUNCH_CHECK("dice_reduce");
     }
+    CldTerm cld{};
+    if (cld_on)
+        if (int rc = launch_cldice_term(Z, target, target_is_u8, o, B, C, g, S, *f.cldice, G != nullptr, gscale, s, &cld)) return rc;
     with_target_type(target, target_is_u8, [&](auto* t) {
         using T = target_t<decltype(t)>;
-        if (f.dice)
+        if (cld_on)
+            hipLaunchKernelGGL(ce_cldice_kernel<T>, dim3(nb), dim3(256), 0, s, Z, t, G, partial, spart, den, den_plain, sums, o, d, B, C, g,
+                               S, gscale, cld.gplanes, cld.map);
+        else if (f.dice)
             hipLaunchKernelGGL(ce_dice_kernel<T>, dim3(nb), dim3(256), 0, s, Z, t, G, partial, spart, den, den_plain, sums,
                                o, d, B, C, g, S, gscale);
         else
@@ -485,7 +542,8 @@ int launch_fused_loss(const float* Z, const void* target, int target_is_u8, floa
     });
     VITSEG_LAUNCH_CHECK("ce_loss_opts");
     hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(1024), 0, s, partial, d.use_ce && o.eps > 0.f ? (const double*)spart : nullptr,
-                       (int)nb, (const double*)den, den_plain, (const double*)sums, C, d, f.dice ? f.terms : nullptr, loss);
+                       (int)nb, (const double*)den, den_plain, (const double*)sums, C, d, f.dice || cld_on ? f.terms : nullptr, loss,
+                       cld_on ? cld.extra : nullptr);
     VITSEG_LAUNCH_CHECK("ce_finish");
     return VITSEG_OK;
 }

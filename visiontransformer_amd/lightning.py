@@ -22,7 +22,8 @@ class LightningViTModel(nn.Module):
                  interpolate_pos_encoding: bool = False, ignore_index=None, class_weight=None,
                  label_smoothing: float = 0.0, dice_weight: float = 0.0, dice_smooth: float = 1e-6,
                  dice_include_background: bool = True, augment=None, focal_gamma: float = 0.0, ohem_thresh=None,
-                 ohem_min_kept: int = 0, ohem_keep_fraction: float = 0.0, **kw):
+                 ohem_min_kept: int = 0, ohem_keep_fraction: float = 0.0, cldice_weight: float = 0.0, cldice_classes=None,
+                 cldice_iters: int = 3, cldice_smooth: float = 1.0, **kw):
         """`interpolate_pos_encoding`: inputs of other (square, multiple-of-P) sizes than `image_size` run with the
         position table resampled to their grid (ViTSegmentationModel.forward); targets are resized to the input's size.
         `ignore_index`, `class_weight`, `label_smoothing`: the arguments of the reference's `nn.CrossEntropyLoss()`
@@ -36,6 +37,10 @@ class LightningViTModel(nn.Module):
         valid pixels; the validation step forms the same loss with OHEM off (the focal factor stays), so that `valid_loss` and
         early stopping do not follow the hardest pixels alone.  Not with `dice_weight` or `label_smoothing` (ValueError).  With
         all four at their defaults the steps call exactly what they call without the arguments.
+        `cldice_weight` > 0 adds that many times the soft-clDice loss (ViTSegmentationModel.ce_cldice_loss with
+        `cldice_classes`, `cldice_iters`, `cldice_smooth`; `dice_weight` goes along); both steps then log `*_ce`, `*_dice` and
+        `*_cldice` beside `*_loss`, and validation forms the term too.  Not with `focal_gamma` / `ohem_*` (ValueError).  With 0
+        the steps call exactly what they call without the argument.
         `augment`: an `augment.Augmenter`; the training step (alone) warps and colour-jitters the batch with it, the mask
         going straight to the input's size as the class bytes the fused loss reads (one launch, in place of `_resize_target`).
         With None the steps launch exactly what they launch without the argument.
@@ -65,6 +70,15 @@ class LightningViTModel(nn.Module):
                              "a variant of the fused CE + Dice kernel and is out of scope")
         if self.hard and label_smoothing != 0:
             raise ValueError("focal_gamma / ohem_* cannot be combined with label_smoothing")
+        self.cldice_weight = float(cldice_weight)
+        self.cldice_classes = None if cldice_classes is None else tuple(int(c) for c in cldice_classes)
+        self.cldice_iters, self.cldice_smooth = cldice_iters, cldice_smooth
+        from .cldice import check_options as check_cldice_options
+        if self.cldice_weight != 0.0 or cldice_classes is not None:   # ValueError here, not at the first step
+            check_cldice_options(num_classes, cldice_weight, cldice_classes, cldice_iters, cldice_smooth)
+        if self.hard and self.cldice_weight != 0.0:
+            raise ValueError("focal_gamma / ohem_* cannot be combined with cldice_weight: focal and OHEM with the clDice term are "
+                             "not built")
         self.augment = augment
         self.logged = {}
 
@@ -101,6 +115,15 @@ class LightningViTModel(nn.Module):
         opts = {}
         if self.ignore_index is not None or self.class_weight is not None or self.label_smoothing != 0:
             opts = dict(ignore_index=self.ignore_index, class_weight=self.class_weight, label_smoothing=self.label_smoothing)
+        if self.cldice_weight != 0.0:
+            loss, ce, dice, cld = self.model.ce_cldice_loss(
+                x, y, cldice_weight=self.cldice_weight, cldice_classes=self.cldice_classes, cldice_iters=self.cldice_iters,
+                cldice_smooth=self.cldice_smooth, dice_weight=self.dice_weight, smooth=self.dice_smooth,
+                include_background=self.dice_include_background, grad_scale=grad_scale,
+                interpolate_pos_encoding=self.interpolate_pos_encoding, return_terms=True, **opts)
+            if stage is not None:
+                self.logged[f"{stage}_ce"], self.logged[f"{stage}_dice"], self.logged[f"{stage}_cldice"] = ce, dice, cld
+            return loss
         if self.dice_weight != 0.0:
             loss, ce, dice = self.model.ce_dice_loss(
                 x, y, dice_weight=self.dice_weight, smooth=self.dice_smooth, include_background=self.dice_include_background,

@@ -185,6 +185,28 @@ class _HardCELossFn(torch.autograd.Function):
         return ctx.model._deliver_grad(grads), None, None, None, None, None, None, None
 
 
+class _CEClDiceLossFn(torch.autograd.Function):
+    """`_CEDiceLossFn` with the soft-clDice term (vitseg_backward_cldice): returns the device float[4] {loss, CE, dice,
+    cldice}; only element 0 carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, arena, model, x, target, grad_scale, interp, ce_opts, dice_opts, cld_opts):
+        drop = model._next_dropout()
+        model._forward_train(x, want_logits=False, drop=drop, interp=interp)
+        grads, terms = model._backward(x, target=target, drop=drop, loss_scale=1.0 if grad_scale is None else grad_scale,
+                                       interp=interp, ce_opts=ce_opts, dice_opts=dice_opts, cld_opts=cld_opts)
+        ctx.grads, ctx.model = grads, model
+        ctx.prescaled = grad_scale is not None
+        return terms
+
+    @staticmethod
+    def backward(ctx, dterms):
+        grads, ctx.grads = ctx.grads, None
+        if not ctx.prescaled:
+            grads.mul_(dterms[0])   # in place: the buffer is ours until it is delivered
+        return ctx.model._deliver_grad(grads), None, None, None, None, None, None, None, None
+
+
 class _CEDiceLossFn(torch.autograd.Function):
     """`_CELossFn` for ce_weight CE + dice_weight dice (vitseg_backward_dice): returns the device float[3] {loss, CE, dice};
     only element 0 carries a gradient (the other two are reported values), delivered the same way."""
@@ -499,12 +521,14 @@ class ViTSegmentationModel(nn.Module):
 
     def _backward(self, x: torch.Tensor, target: Optional[torch.Tensor] = None,
                   grad_logits: Optional[torch.Tensor] = None, drop=(0.0, 0), loss_scale: float = 1.0,
-                  interp: bool = False, ce_opts=None, dice_opts=None, hard_opts=None):
+                  interp: bool = False, ce_opts=None, dice_opts=None, hard_opts=None, cld_opts=None):
         """`ce_opts`: a `_lib.CCEOptions` from `_ce_options` (fused CE only), or None for the plain calls.  `dice_opts`: a
         `_lib.CDiceOptions` from `_dice_options` (fused loss only): the second value returned is then the device float[3]
         {loss, CE, dice} of vitseg_backward_dice instead of the scalar loss.  `hard_opts`: an `_ext.CHardOptions` from
         `_hard_options` (fused loss only, not with `dice_opts`): the second value is then (loss, the device int64[4] stats
-        of vitseg_backward_hard)."""
+        of vitseg_backward_hard).  `cld_opts`: an `_ext.CClDiceOptions` from `_cldice_options` (fused loss only, `dice_opts`
+        optional, not with `hard_opts`): the second value is the device float[4] {loss, CE, dice, cldice} of
+        vitseg_backward_cldice."""
         x = x.to(torch.float32).contiguous()
         B, S = x.shape[0], self._size_in(x, interp)
         ws = self._train_workspace(B, S)
@@ -518,7 +542,13 @@ class ViTSegmentationModel(nn.Module):
                     grads.data_ptr(), _ptr(loss), float(loss_scale), handles, ws.data_ptr(), ws.numel(),
                     torch.cuda.current_stream().cuda_stream)
             cfg = C.byref(_lib.CConfig.from_config(self.cfg))
-            if dice_opts is not None:
+            if cld_opts is not None:
+                terms = torch.zeros(4, dtype=torch.float32, device=x.device)
+                _lib.check(_ext.ext_symbol("cldice", "vitseg_backward_cldice")(
+                    cfg, S, *args, C.byref(ce_opts) if ce_opts is not None else None,
+                    C.byref(dice_opts) if dice_opts is not None else None, C.byref(cld_opts), terms.data_ptr()))
+                loss = terms
+            elif dice_opts is not None:
                 terms = torch.zeros(3, dtype=torch.float32, device=x.device)
                 _lib.check(_lib.symbol("vitseg_backward_dice")(
                     cfg, S, *args, C.byref(ce_opts) if ce_opts is not None else None, C.byref(dice_opts), terms.data_ptr()))
@@ -1175,6 +1205,69 @@ class ViTSegmentationModel(nn.Module):
                     C.byref(opts) if opts is not None else None, C.byref(dopts), 1.0, torch.cuda.current_stream().cuda_stream))
         if return_terms:
             return terms[0], terms[1].detach(), terms[2].detach()
+        return terms[0]
+
+    def _cldice_options(self, B: int, S: int, weight, classes, iters, smooth):
+        """The `_ext.CClDiceOptions` of a `ce_cldice_loss` call (validated on the host); its scratch is cached per (batch,
+        size, classes, iters)."""
+        from .cldice import check_options
+        w, cls, it, sm = check_options(self.cfg.num_classes, weight, classes, iters, smooth)
+        dev = self.arena.device
+        nbytes = int(_ext.ext_symbol("cldice", "vitseg_cldice_scratch_bytes")(B, len(cls), S, it))
+        if nbytes == 0:
+            raise ValueError(f"clDice planes of {len(cls)} x {B} x {S} x {S} pixels are beyond one call (2^31 - 1)")
+        scratch = self._ce_cached("cldice scratch", (B, S, len(cls), it, dev), lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+        arr = (C.c_int32 * len(cls))(*cls)
+        opts = _ext.CClDiceOptions(w, sm, it, len(cls), arr, scratch.data_ptr(), scratch.numel(), None, None)
+        opts._tensors = (scratch, arr)   # the struct holds raw addresses
+        return opts
+
+    def ce_cldice_loss(self, x: torch.Tensor, target: torch.Tensor, *, cldice_weight: float = 0.5, cldice_classes=None,
+                       cldice_iters: int = 3, cldice_smooth: float = 1.0, dice_weight: float = 0.0, ce_weight: float = 1.0,
+                       smooth: float = 1e-6, include_background: bool = True, ignore_index: Optional[int] = None,
+                       class_weight=None, label_smoothing: float = 0.0, grad_scale: Optional[float] = None,
+                       interpolate_pos_encoding: bool = False, return_terms: bool = False):
+        """`ce_weight * CE + dice_weight * dice + cldice_weight * cldice` on `self(x)` as a device scalar, without
+        materialising the logits or their gradient.  CE and dice are `ce_dice_loss`'s.  cldice is the soft-clDice loss of
+        Shit et al. (CVPR 2021): per listed class the soft skeletons (`cldice_iters` rounds of min / max pooling) of the
+        softmax plane and of the 0/1 target plane give a centre-line precision and sensitivity over the call's batch, smoothed
+        by `cldice_smooth`, and cl = 1 - their harmonic mean; cldice is the mean of cl over `cldice_classes` (None: every
+        class but 0).  It is per class, as the Dice term is (the published code pools the foreground channels).  Pixels of
+        `ignore_index` take no part and get gradient 0.  The gradient is autograd's, ties included
+        (include/vitseg_cldice.h).  A weight of 0 leaves its term out (an exact 0).  The focal / OHEM options of `ce_loss`
+        cannot be combined with it.  `return_terms=True` returns (loss, ce, dice, cldice), the last three detached."""
+        interp = bool(interpolate_pos_encoding)
+        if interp:
+            self._check_input(x, True)
+        S, B = self._size_in(x, interp), x.shape[0]
+        if tuple(target.shape) != (B, S, S) or target.dtype not in (torch.int64, torch.uint8):
+            raise ValueError(f"target must be int64/uint8 [B, {S}, {S}], got {target.dtype} {tuple(target.shape)}")
+        cld = self._cldice_options(B, S, cldice_weight, cldice_classes, cldice_iters, cldice_smooth)
+        if cld.weight != 0.0 and float(dice_weight) == 0.0 and float(ce_weight) == 0.0:
+            # the term alone: both weights 0, which `check_dice_options` refuses for `ce_dice_loss` and the C entry takes here
+            dopts = self._dice_options(B, S, 0.0, 1.0, smooth, include_background)
+            dopts.ce_weight = 0.0
+        elif float(dice_weight) == 0.0 and float(ce_weight) == 1.0:
+            dopts = None
+        else:
+            dopts = self._dice_options(B, S, dice_weight, ce_weight, smooth, include_background)
+        opts = self._ce_options(B, S, ignore_index, class_weight, label_smoothing)
+        target = target.to(self.arena.device).contiguous()
+        if self._needs_grad():
+            terms = _CEClDiceLossFn.apply(self.arena, self, x, target, grad_scale, interp, opts, dopts, cld)
+        else:
+            with torch.no_grad():
+                _, _ = self._run(x, False, True, interp=interp)  # fills the low-res logits (mask output is a by-product)
+                low = self.debug_buffer(B, _lib.BUF_LOWRES, S)
+                scratch = torch.empty(_lib.lib().vitseg_ce_scratch_bytes(B, S), dtype=torch.uint8, device=low.device)
+                terms = torch.empty(4, dtype=torch.float32, device=low.device)
+                _lib.check(_ext.ext_symbol("cldice", "vitseg_ce_cldice_loss")(
+                    low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8), None, scratch.data_ptr(),
+                    terms.data_ptr(), B, self.cfg.num_classes, S // self.cfg.patch_size, S,
+                    C.byref(opts) if opts is not None else None, C.byref(dopts) if dopts is not None else None, C.byref(cld), 1.0,
+                    torch.cuda.current_stream().cuda_stream))
+        if return_terms:
+            return terms[0], terms[1].detach(), terms[2].detach(), terms[3].detach()
         return terms[0]
 
     @torch.no_grad()

@@ -61,6 +61,11 @@ def add_ce_loss_arguments(ap) -> None:
     ap.add_argument("--ohem-min-kept", type=int, default=0, help="OHEM: never fewer than this many of the hardest pixels of a batch")
     ap.add_argument("--ohem-keep-fraction", type=float, default=0.0,
                     help="OHEM: never fewer than this fraction of the valid pixels of a batch")
+    ap.add_argument("--cldice-weight", type=float, default=0.0,
+                    help="add this many times the soft-clDice loss (centre-line Dice on soft skeletons; 0: off)")
+    ap.add_argument("--cldice-classes", default=None, help="comma-separated classes the clDice term counts (default: all but 0)")
+    ap.add_argument("--cldice-iters", type=int, default=3, help="rounds of min / max pooling of the soft skeleton")
+    ap.add_argument("--cldice-smooth", type=float, default=1.0)
 
 
 def ce_loss_options(a) -> dict:
@@ -85,6 +90,13 @@ def ce_loss_options(a) -> dict:
         kw["ohem_min_kept"] = a.ohem_min_kept
     if getattr(a, "ohem_keep_fraction", 0.0):
         kw["ohem_keep_fraction"] = a.ohem_keep_fraction
+    if getattr(a, "cldice_weight", 0.0):
+        kw.update(cldice_weight=a.cldice_weight, cldice_iters=a.cldice_iters, cldice_smooth=a.cldice_smooth)
+        if a.cldice_classes:
+            try:
+                kw["cldice_classes"] = [int(v) for v in a.cldice_classes.split(",")]
+            except ValueError:
+                raise ValueError(f"--cldice-classes expects comma-separated class indices, got {a.cldice_classes!r}") from None
     return kw
 
 
