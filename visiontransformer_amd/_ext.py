@@ -24,6 +24,7 @@ CURVES_VERSION = 100   # include/vitseg_curves.h VITSEG_CURVES_VERSION
 DECIDE_VERSION = 100   # include/vitseg_decide.h VITSEG_DECIDE_VERSION
 HARDLOSS_VERSION = 100   # include/vitseg_hardloss.h VITSEG_HARDLOSS_VERSION
 CLDICE_VERSION = 100   # include/vitseg_cldice.h VITSEG_CLDICE_VERSION
+LOVASZ_VERSION = 100   # include/vitseg_lovasz.h VITSEG_LOVASZ_VERSION
 
 
 class CHardOptions(C.Structure):
@@ -43,6 +44,16 @@ class CClDiceOptions(C.Structure):
 
 
 pcld = C.POINTER(CClDiceOptions)
+
+
+class CLovaszOptions(C.Structure):
+    """struct vitseg_lovasz_options (include/vitseg_lovasz.h)."""
+    _fields_ = [("weight", C.c_float), ("K", C.c_int32), ("classes", C.POINTER(C.c_int32)), ("per_image", C.c_int32),
+                ("present_only", C.c_int32), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("prob_planes", C.c_void_p), ("grad_planes", C.c_void_p), ("class_terms", C.c_void_p)]
+
+
+plov = C.POINTER(CLovaszOptions)
 
 EXT_SIGNATURES = {
     # region outlines: polygon rings with holes (polygons.py)
@@ -108,6 +119,17 @@ EXT_LATER = {
         ("vitseg_backward_cldice", i32, [_lib.pcfg, i32, vp, vp, vp, i32, i32, f32, _lib.u64, vp, i32, vp, vp, vp, f32, vp, vp, sz,
                                          vp, _lib.popt, _lib.pdice, pcld, vp]),
     ]),
+    # the Lovasz-Softmax loss: the segmented sort on given planes and the term on the fused loss path (lovasz.py,
+    # model.ce_lovasz_loss)
+    "lovasz": ("vitseg_lovasz.h", "the Lovasz-Softmax loss", [
+        ("vitseg_lovasz_version", i32, []),
+        ("vitseg_lovasz_planes_scratch_bytes", sz, [i32, i32]),
+        ("vitseg_lovasz_planes", i32, [vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]),
+        ("vitseg_lovasz_scratch_bytes", sz, [i32, i32, i32]),
+        ("vitseg_ce_lovasz_loss", i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, _lib.popt, _lib.pdice, plov, f32, vp]),
+        ("vitseg_backward_lovasz", i32, [_lib.pcfg, i32, vp, vp, vp, i32, i32, f32, _lib.u64, vp, i32, vp, vp, vp, f32, vp, vp, sz,
+                                         vp, _lib.popt, _lib.pdice, plov, vp]),
+    ]),
 }
 EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
                 "centerlines": ("vitseg_centerlines_version", CENTERLINES_VERSION),
@@ -116,7 +138,8 @@ EXT_VERSIONS = {"polygons": ("vitseg_polygons_version", POLYGONS_VERSION),
                 "curves": ("vitseg_curves_version", CURVES_VERSION),
                 "decide": ("vitseg_decide_version", DECIDE_VERSION),
                 "hardloss": ("vitseg_hardloss_version", HARDLOSS_VERSION),
-                "cldice": ("vitseg_cldice_version", CLDICE_VERSION)}
+                "cldice": ("vitseg_cldice_version", CLDICE_VERSION),
+                "lovasz": ("vitseg_lovasz_version", LOVASZ_VERSION)}
 
 
 def ext_symbol(family: str, name: str):

@@ -7,6 +7,7 @@
 
 struct vitseg_hard_options;   // include/vitseg_hardloss.h
 struct vitseg_cldice_options;   // include/vitseg_cldice.h
+struct vitseg_lovasz_options;   // include/vitseg_lovasz.h
 
 namespace vitseg {
 
@@ -144,14 +145,16 @@ int launch_window_blend(const float* lowres, const int* oy, int ny, const int* o
 // mean's denominator on the device, ce->scratch, ce_opts_scratch_bytes); dice = ce_weight CE + dice_weight soft Dice (a sum
 // pass leaves I, P, T per class on the device, dice->scratch, dice_scratch_bytes); hard = focal CE / OHEM (hard->scratch,
 // hard_loss_scratch_bytes of hardloss.hpp); cldice = the soft-clDice term beside CE and Dice (cldice->scratch, cldice.hpp).  ce
-// goes with any; hard excludes dice and cldice and takes no smoothing.
+// goes with any; hard excludes dice and cldice and takes no smoothing; lovasz = the Lovasz-Softmax term beside CE and Dice
+// (lovasz->scratch, lovasz.hpp), which excludes cldice and hard.
 struct FusedLoss {
     const vitseg_ce_options* ce = nullptr;
     const vitseg_dice_options* dice = nullptr;
     const vitseg_hard_options* hard = nullptr;
     const vitseg_cldice_options* cldice = nullptr;
+    const vitseg_lovasz_options* lovasz = nullptr;
     float* terms = nullptr;        // dice: device float[3] = {loss, CE, dice}, required
-    bool terms4 = false;           // terms is float[4] = {loss, CE, dice, cldice} (vitseg_ce_cldice_loss; dice may then be null)
+    bool terms4 = false;           // terms is float[4] = {loss, CE, dice, cldice or lovasz} (vitseg_ce_cldice_loss, vitseg_ce_lovasz_loss; dice may then be null)
     long long* stats = nullptr;    // hard: device int64[4] = {n_valid, k, |H|, bits of tau}, or null
     float* pixel_loss = nullptr;   // hard: device fp32 [B, S, S], every pixel's CE, or null
 };

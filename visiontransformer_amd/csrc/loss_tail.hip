@@ -8,6 +8,7 @@
 #include "hardloss.hpp"
 #include "kernels.hpp"
 #include "loss_pixel.hpp"
+#include "lovasz.hpp"
 
 namespace vitseg {
 namespace {
@@ -457,12 +458,17 @@ int check_fused_loss(const FusedLoss& f, int B, int C, int S) {
     VITSEG_CHECK_ARG(!(f.dice && f.hard), VITSEG_EINVAL, "fused loss: the dice and the hard options cannot be combined");
     VITSEG_CHECK_ARG(!(f.cldice && f.hard), VITSEG_EINVAL, "fused loss: focal / OHEM with the clDice term are not built");
     VITSEG_CHECK_ARG(!f.cldice || f.terms4, VITSEG_EINVAL, "fused loss: the clDice options need the four terms");
+    VITSEG_CHECK_ARG(!(f.lovasz && (f.cldice || f.hard)), VITSEG_EINVAL,
+                     "fused loss: the Lovasz term with clDice or with focal / OHEM is not built");
+    VITSEG_CHECK_ARG(!f.lovasz || f.terms4, VITSEG_EINVAL, "fused loss: the Lovasz options need the four terms");
+    if (f.lovasz)
+        if (int rc = check_lovasz_options(*f.lovasz, B, C, S)) return rc;
     if (f.cldice)
         if (int rc = check_cldice_options(*f.cldice, B, C, S)) return rc;
     if (f.hard)
         if (int rc = check_hard_options(*f.hard, B, C, S)) return rc;
     if (f.dice)
-        if (int rc = check_dice_options(*f.dice, B, C, S, f.cldice && f.cldice->weight != 0.f)) return rc;
+        if (int rc = check_dice_options(*f.dice, B, C, S, (f.cldice && f.cldice->weight != 0.f) || (f.lovasz && f.lovasz->weight != 0.f))) return rc;
     if (f.ce)
         if (int rc = check_ce_options(*f.ce, B, C, S)) return rc;
     VITSEG_CHECK_ARG(!(f.hard && f.ce) || f.ce->label_smoothing == 0.f, VITSEG_EINVAL,
@@ -475,10 +481,12 @@ int launch_fused_loss(const float* Z, const void* target, int target_is_u8, floa
     VITSEG_CHECK_ARG(Z && target && partial && (f.dice || f.terms4 ? f.terms : loss), VITSEG_EINVAL, "%s: null pointer",
                      f.terms4 ? "ce_cldice_loss" : f.dice ? "ce_dice_loss" : f.hard ? "hard loss" : "ce_loss");
     if (int rc = check_fused_loss(f, B, C, S)) return rc;
-    const bool cld_on = f.cldice && f.cldice->weight != 0.f;
+    const bool lov_on = f.lovasz && f.lovasz->weight != 0.f;   // it leaves what clDice leaves: the same loss and finish kernels
+    const bool cld_on = (f.cldice && f.cldice->weight != 0.f) || lov_on;
     if (f.terms4 && !cld_on) {   // the term is left out: the launches of the call without it, then the fourth entry
         FusedLoss f3 = f;
         f3.cldice = nullptr;
+        f3.lovasz = nullptr;
         f3.terms4 = false;
         if (int rc = launch_fused_loss(Z, target, target_is_u8, G, partial, f.dice ? loss : f.terms, B, C, g, S, f3, s, gscale)) return rc;
         hipLaunchKernelGGL(cld_terms_fill_kernel, dim3(1), dim3(1), 0, s, f.terms, f.dice ? 1 : 0, loss);
@@ -527,8 +535,11 @@ int launch_fused_loss(const float* Z, const void* target, int target_is_u8, floa
         VITSEG_LAUNCH_CHECK("dice_reduce");
     }
     CldTerm cld{};
-    if (cld_on)
+    if (lov_on) {
+        if (int rc = launch_lovasz_term(Z, target, target_is_u8, o, B, C, g, S, *f.lovasz, G != nullptr, gscale, s, &cld)) return rc;
+    } else if (cld_on) {
         if (int rc = launch_cldice_term(Z, target, target_is_u8, o, B, C, g, S, *f.cldice, G != nullptr, gscale, s, &cld)) return rc;
+    }
     with_target_type(target, target_is_u8, [&](auto* t) {
         using T = target_t<decltype(t)>;
         if (cld_on)

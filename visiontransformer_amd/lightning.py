@@ -23,7 +23,8 @@ class LightningViTModel(nn.Module):
                  label_smoothing: float = 0.0, dice_weight: float = 0.0, dice_smooth: float = 1e-6,
                  dice_include_background: bool = True, augment=None, focal_gamma: float = 0.0, ohem_thresh=None,
                  ohem_min_kept: int = 0, ohem_keep_fraction: float = 0.0, cldice_weight: float = 0.0, cldice_classes=None,
-                 cldice_iters: int = 3, cldice_smooth: float = 1.0, **kw):
+                 cldice_iters: int = 3, cldice_smooth: float = 1.0, lovasz_weight: float = 0.0, lovasz_classes=None,
+                 lovasz_per_image: bool = False, **kw):
         """`interpolate_pos_encoding`: inputs of other (square, multiple-of-P) sizes than `image_size` run with the
         position table resampled to their grid (ViTSegmentationModel.forward); targets are resized to the input's size.
         `ignore_index`, `class_weight`, `label_smoothing`: the arguments of the reference's `nn.CrossEntropyLoss()`
@@ -41,6 +42,10 @@ class LightningViTModel(nn.Module):
         `cldice_classes`, `cldice_iters`, `cldice_smooth`; `dice_weight` goes along); both steps then log `*_ce`, `*_dice` and
         `*_cldice` beside `*_loss`, and validation forms the term too.  Not with `focal_gamma` / `ohem_*` (ValueError).  With 0
         the steps call exactly what they call without the argument.
+        `lovasz_weight` > 0 adds that many times the Lovasz-Softmax loss (ViTSegmentationModel.ce_lovasz_loss with
+        `lovasz_classes`, `lovasz_per_image`; `dice_weight` goes along); both steps then log `*_ce`, `*_dice` and `*_lovasz`
+        beside `*_loss`, and validation forms the term too.  Not with `cldice_weight`, `focal_gamma` / `ohem_*` (ValueError).
+        With 0 the steps call exactly what they call without the argument.
         `augment`: an `augment.Augmenter`; the training step (alone) warps and colour-jitters the batch with it, the mask
         going straight to the input's size as the class bytes the fused loss reads (one launch, in place of `_resize_target`).
         With None the steps launch exactly what they launch without the argument.
@@ -79,6 +84,17 @@ class LightningViTModel(nn.Module):
         if self.hard and self.cldice_weight != 0.0:
             raise ValueError("focal_gamma / ohem_* cannot be combined with cldice_weight: focal and OHEM with the clDice term are "
                              "not built")
+        self.lovasz_weight = float(lovasz_weight)
+        self.lovasz_classes = None if lovasz_classes is None else tuple(int(c) for c in lovasz_classes)
+        self.lovasz_per_image = bool(lovasz_per_image)
+        from .lovasz import check_options as check_lovasz_options
+        if self.lovasz_weight != 0.0 or lovasz_classes is not None:   # ValueError here, not at the first step
+            check_lovasz_options(num_classes, lovasz_weight, lovasz_classes, lovasz_per_image)
+        if self.lovasz_weight != 0.0 and self.cldice_weight != 0.0:
+            raise ValueError("lovasz_weight cannot be combined with cldice_weight: the two terms in one call are not built")
+        if self.hard and self.lovasz_weight != 0.0:
+            raise ValueError("focal_gamma / ohem_* cannot be combined with lovasz_weight: focal and OHEM with the Lovasz term are "
+                             "not built")
         self.augment = augment
         self.logged = {}
 
@@ -115,6 +131,15 @@ class LightningViTModel(nn.Module):
         opts = {}
         if self.ignore_index is not None or self.class_weight is not None or self.label_smoothing != 0:
             opts = dict(ignore_index=self.ignore_index, class_weight=self.class_weight, label_smoothing=self.label_smoothing)
+        if self.lovasz_weight != 0.0:
+            loss, ce, dice, lov = self.model.ce_lovasz_loss(
+                x, y, lovasz_weight=self.lovasz_weight, lovasz_classes=self.lovasz_classes,
+                lovasz_per_image=self.lovasz_per_image, dice_weight=self.dice_weight, smooth=self.dice_smooth,
+                include_background=self.dice_include_background, grad_scale=grad_scale,
+                interpolate_pos_encoding=self.interpolate_pos_encoding, return_terms=True, **opts)
+            if stage is not None:
+                self.logged[f"{stage}_ce"], self.logged[f"{stage}_dice"], self.logged[f"{stage}_lovasz"] = ce, dice, lov
+            return loss
         if self.cldice_weight != 0.0:
             loss, ce, dice, cld = self.model.ce_cldice_loss(
                 x, y, cldice_weight=self.cldice_weight, cldice_classes=self.cldice_classes, cldice_iters=self.cldice_iters,

@@ -186,8 +186,9 @@ class _HardCELossFn(torch.autograd.Function):
 
 
 class _CEClDiceLossFn(torch.autograd.Function):
-    """`_CEDiceLossFn` with the soft-clDice term (vitseg_backward_cldice): returns the device float[4] {loss, CE, dice,
-    cldice}; only element 0 carries a gradient."""
+    """`_CEDiceLossFn` with the soft-clDice term (vitseg_backward_cldice) or, `cld_opts` being an `_ext.CLovaszOptions`, the
+    Lovasz-Softmax term (vitseg_backward_lovasz): returns the device float[4] {loss, CE, dice, cldice or lovasz}; only
+    element 0 carries a gradient."""
 
     @staticmethod
     def forward(ctx, arena, model, x, target, grad_scale, interp, ce_opts, dice_opts, cld_opts):
@@ -528,7 +529,8 @@ class ViTSegmentationModel(nn.Module):
         `_hard_options` (fused loss only, not with `dice_opts`): the second value is then (loss, the device int64[4] stats
         of vitseg_backward_hard).  `cld_opts`: an `_ext.CClDiceOptions` from `_cldice_options` (fused loss only, `dice_opts`
         optional, not with `hard_opts`): the second value is the device float[4] {loss, CE, dice, cldice} of
-        vitseg_backward_cldice."""
+        vitseg_backward_cldice; an `_ext.CLovaszOptions` from `_lovasz_options` in its place: {loss, CE, dice, lovasz} of
+        vitseg_backward_lovasz."""
         x = x.to(torch.float32).contiguous()
         B, S = x.shape[0], self._size_in(x, interp)
         ws = self._train_workspace(B, S)
@@ -544,7 +546,9 @@ class ViTSegmentationModel(nn.Module):
             cfg = C.byref(_lib.CConfig.from_config(self.cfg))
             if cld_opts is not None:
                 terms = torch.zeros(4, dtype=torch.float32, device=x.device)
-                _lib.check(_ext.ext_symbol("cldice", "vitseg_backward_cldice")(
+                entry = (("lovasz", "vitseg_backward_lovasz") if isinstance(cld_opts, _ext.CLovaszOptions)
+                         else ("cldice", "vitseg_backward_cldice"))
+                _lib.check(_ext.ext_symbol(*entry)(
                     cfg, S, *args, C.byref(ce_opts) if ce_opts is not None else None,
                     C.byref(dice_opts) if dice_opts is not None else None, C.byref(cld_opts), terms.data_ptr()))
                 loss = terms
@@ -1265,6 +1269,71 @@ class ViTSegmentationModel(nn.Module):
                     low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8), None, scratch.data_ptr(),
                     terms.data_ptr(), B, self.cfg.num_classes, S // self.cfg.patch_size, S,
                     C.byref(opts) if opts is not None else None, C.byref(dopts) if dopts is not None else None, C.byref(cld), 1.0,
+                    torch.cuda.current_stream().cuda_stream))
+        if return_terms:
+            return terms[0], terms[1].detach(), terms[2].detach(), terms[3].detach()
+        return terms[0]
+
+    def _lovasz_options(self, B: int, S: int, weight, classes, per_image, present):
+        """The `_ext.CLovaszOptions` of a `ce_lovasz_loss` call (validated on the host); its scratch is cached per (batch,
+        size, number of classes)."""
+        from .lovasz import check_options
+        w, cls, pi, po = check_options(self.cfg.num_classes, weight, classes, per_image, present)
+        dev = self.arena.device
+        nbytes = int(_ext.ext_symbol("lovasz", "vitseg_lovasz_scratch_bytes")(B, len(cls), S))
+        if nbytes == 0:
+            raise ValueError(f"Lovasz planes of {len(cls)} x {B} x {S} x {S} pixels are beyond one call (2^31 - 1 pixels, 2^20 "
+                             "segments)")
+        scratch = self._ce_cached("lovasz scratch", (B, S, len(cls), dev), lambda: torch.empty(nbytes, dtype=torch.uint8, device=dev))
+        arr = (C.c_int32 * len(cls))(*cls)
+        opts = _ext.CLovaszOptions(w, len(cls), arr, pi, po, scratch.data_ptr(), scratch.numel(), None, None, None)
+        opts._tensors = (scratch, arr)   # the struct holds raw addresses
+        return opts
+
+    def ce_lovasz_loss(self, x: torch.Tensor, target: torch.Tensor, *, lovasz_weight: float = 0.5, lovasz_classes=None,
+                       lovasz_per_image: bool = False, lovasz_present: bool = True, dice_weight: float = 0.0,
+                       ce_weight: float = 1.0, smooth: float = 1e-6, include_background: bool = True,
+                       ignore_index: Optional[int] = None, class_weight=None, label_smoothing: float = 0.0,
+                       grad_scale: Optional[float] = None, interpolate_pos_encoding: bool = False, return_terms: bool = False):
+        """`ce_weight * CE + dice_weight * dice + lovasz_weight * lovasz` on `self(x)` as a device scalar, without
+        materialising the logits or their gradient.  CE and dice are `ce_dice_loss`'s.  lovasz is the Lovasz-Softmax loss of
+        Berman et al. (CVPR 2018), the convex surrogate of the Jaccard index: per listed class (`lovasz_classes`, None: every
+        class) the errors |y - p| of a segment are sorted descending (equal errors by pixel index) and weighted by the
+        Lovasz extension's gradient of the Jaccard loss; a segment is the call's batch, or each image with
+        `lovasz_per_image` (the term is then the mean over the images).  `lovasz_present` (the published
+        classes='present'): a class absent from a segment is left out of its mean.  Pixels of `ignore_index` take no rank
+        and get gradient 0.  A weight of 0 leaves its term out (an exact 0).  The clDice term and the focal / OHEM options of
+        `ce_loss` cannot be combined with it.  `return_terms=True` returns (loss, ce, dice, lovasz), the last three
+        detached.  Semantics in full: include/vitseg_lovasz.h."""
+        interp = bool(interpolate_pos_encoding)
+        if interp:
+            self._check_input(x, True)
+        S, B = self._size_in(x, interp), x.shape[0]
+        if tuple(target.shape) != (B, S, S) or target.dtype not in (torch.int64, torch.uint8):
+            raise ValueError(f"target must be int64/uint8 [B, {S}, {S}], got {target.dtype} {tuple(target.shape)}")
+        lov = self._lovasz_options(B, S, lovasz_weight, lovasz_classes, lovasz_per_image, lovasz_present)
+        if lov.weight != 0.0 and float(dice_weight) == 0.0 and float(ce_weight) == 0.0:
+            # the term alone: both weights 0, which `check_dice_options` refuses for `ce_dice_loss` and the C entry takes here
+            dopts = self._dice_options(B, S, 0.0, 1.0, smooth, include_background)
+            dopts.ce_weight = 0.0
+        elif float(dice_weight) == 0.0 and float(ce_weight) == 1.0:
+            dopts = None
+        else:
+            dopts = self._dice_options(B, S, dice_weight, ce_weight, smooth, include_background)
+        opts = self._ce_options(B, S, ignore_index, class_weight, label_smoothing)
+        target = target.to(self.arena.device).contiguous()
+        if self._needs_grad():
+            terms = _CEClDiceLossFn.apply(self.arena, self, x, target, grad_scale, interp, opts, dopts, lov)
+        else:
+            with torch.no_grad():
+                _, _ = self._run(x, False, True, interp=interp)  # fills the low-res logits (mask output is a by-product)
+                low = self.debug_buffer(B, _lib.BUF_LOWRES, S)
+                scratch = torch.empty(_lib.lib().vitseg_ce_scratch_bytes(B, S), dtype=torch.uint8, device=low.device)
+                terms = torch.empty(4, dtype=torch.float32, device=low.device)
+                _lib.check(_ext.ext_symbol("lovasz", "vitseg_ce_lovasz_loss")(
+                    low.data_ptr(), target.data_ptr(), int(target.dtype == torch.uint8), None, scratch.data_ptr(),
+                    terms.data_ptr(), B, self.cfg.num_classes, S // self.cfg.patch_size, S,
+                    C.byref(opts) if opts is not None else None, C.byref(dopts) if dopts is not None else None, C.byref(lov), 1.0,
                     torch.cuda.current_stream().cuda_stream))
         if return_terms:
             return terms[0], terms[1].detach(), terms[2].detach(), terms[3].detach()

@@ -66,6 +66,10 @@ def add_ce_loss_arguments(ap) -> None:
     ap.add_argument("--cldice-classes", default=None, help="comma-separated classes the clDice term counts (default: all but 0)")
     ap.add_argument("--cldice-iters", type=int, default=3, help="rounds of min / max pooling of the soft skeleton")
     ap.add_argument("--cldice-smooth", type=float, default=1.0)
+    ap.add_argument("--lovasz-weight", type=float, default=0.0,
+                    help="add this many times the Lovasz-Softmax loss (the surrogate of the class IoU; 0: off)")
+    ap.add_argument("--lovasz-classes", default=None, help="comma-separated classes the Lovasz term counts (default: all)")
+    ap.add_argument("--lovasz-per-image", action="store_true", help="sort and average the Lovasz term per image, not over the batch")
 
 
 def ce_loss_options(a) -> dict:
@@ -97,6 +101,13 @@ def ce_loss_options(a) -> dict:
                 kw["cldice_classes"] = [int(v) for v in a.cldice_classes.split(",")]
             except ValueError:
                 raise ValueError(f"--cldice-classes expects comma-separated class indices, got {a.cldice_classes!r}") from None
+    if getattr(a, "lovasz_weight", 0.0):
+        kw.update(lovasz_weight=a.lovasz_weight, lovasz_per_image=bool(a.lovasz_per_image))
+        if a.lovasz_classes:
+            try:
+                kw["lovasz_classes"] = [int(v) for v in a.lovasz_classes.split(",")]
+            except ValueError:
+                raise ValueError(f"--lovasz-classes expects comma-separated class indices, got {a.lovasz_classes!r}") from None
     return kw
 
 
